@@ -1,13 +1,18 @@
 #!/usr/bin/env python3
 """Benchmark of the per-timestep infection hot path (rows a1-a9 of SURVEY.md section 8) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--preset c3] [--agents A]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--preset c3] [--agents A] [--full] [--dump-outputs DIR]
 
 A "step" is one pass of the hot path (transmission update -> pass 1 -> pass 2 + epilogue +
 Gumbel decision + state update) over the synthetic contact world, with every input resident in
 HBM when the timed region starts.  Default workload = BASELINE.json configs[2]: 10 M agents, 8
 infection networks on 6 edge sets, 120 M network-edges (grad_june_amd/synthetic.py, seed 1234),
 in-kernel Philox noise.  Prints ONE JSON line (rank 0).
+
+A plain run sets up, warms up, times exactly K steps (one region) and prints the line.  --full adds what else
+the benchmark measures: repeats of the region, the quarantine / high-prevalence / full-step / sustained regions,
+the CPU baseline, and for N > 1 the per-launch times of K further event-bracketed steps.  --dump-outputs DIR
+writes what the last timed step computed as DIR/<name>.npy (see dump_outputs).
 
 N > 1: one process per GPU (torch.distributed, backend nccl = RCCL); the SAME world is
 partitioned across ranks (strong scaling) - see grad_june_amd/distributed.py.
@@ -94,9 +99,15 @@ def parse():
                          "carries both figures).  on: the validated graph without that trial")
     ap.add_argument("--prewarm-ms", type=float, default=100.0,
                     help="one GPU: milliseconds of stateless passes at the end of the set-up (0: none), see main()")
-    ap.add_argument("--repeats", type=int, default=5,
+    ap.add_argument("--full", action="store_true",
+                    help="everything the benchmark measures besides the headline region (see the module docstring); "
+                         "off by default, so that a plain run times the K steps and little else")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="one GPU: after the timed steps write what the last of them computed as DIR/<name>.npy")
+    ap.add_argument("--repeats", type=int, default=None,
                     help="the K-step timed region is run this many times back to back; `value` is the FIRST region, the "
-                         "others give min / median / max (one 11 ms region per run is a noisy round-over-round figure)")
+                         "others give min / median / max (one 11 ms region per run is a noisy round-over-round figure).  "
+                         "Default 5 with --full or --backward, else 1")
     ap.add_argument("--backward", action="store_true",
                     help="row f3: time forward and backward of a T-step differentiable run (the eight log_beta as "
                          "nn.Parameter, loss = cases of the last step) instead of the forward-only hot path")
@@ -130,7 +141,7 @@ def parse():
     ap.add_argument("--only-headline", action="store_true",
                     help="profiling runs: only the warm-up and the timed region(s) of the headline configuration (no "
                          "quarantine / high-prevalence / full-step regions, no CPU baseline), so that a profile's last "
-                         "dispatches are the timed steps")
+                         "dispatches are the timed steps.  What a run without --full always does")
     ap.add_argument("--sustained-seconds", type=float, default=2.0,
                     help="one GPU: after the timed regions, this many seconds of steps in blocks of 25 with the state reset "
                          "before every block - ms/step min / median / max and the last quarter's mean (0 = skip)")
@@ -477,6 +488,35 @@ def sustained_region(runner, seconds: float, ms_per_step_hint: float, start, t_s
                       "reset before every block, the reset copies lie outside the events"}
 
 
+DUMP_OUTPUTS = ("not_infected_probs", "new_infected", "is_infected", "susceptibility", "infection_time", "transmission")
+DUMP_SAMPLE_AGENTS = 1 << 20
+
+
+def dump_outputs(runner, world, path: str) -> None:
+    """--dump-outputs: what the last timed step handed its caller - the two outputs it wrote (not_infected_probs,
+    new_infected) and the state it updated in place - as ``path/<name>.npy`` (float32), agents in their original
+    numbering.  Worlds of more than 2^20 agents: the same 2^20 agents every run (a sample drawn with seed 0), whose
+    original ids are ``agent_id.npy`` (float64).  ``sums.npy``: each array of DUMP_OUTPUTS summed over all agents
+    (float64, in that order).  At most 2^20 * (6 * 4 + 8) bytes + 48 in all."""
+    A = world["n_agents"]
+    ids = np.arange(A)
+    if A > DUMP_SAMPLE_AGENTS:
+        ids = np.sort(np.random.default_rng(0).choice(A, DUMP_SAMPLE_AGENTS, replace=False))
+    rows = ids
+    if world.get("original_id") is not None:        # the runner's agent order -> original ids
+        pos = np.empty(A, dtype=np.int64)
+        pos[world["original_id"]] = np.arange(A)
+        rows = pos[ids]
+    rows = torch.from_numpy(rows).to(runner.probs.device)
+    arrays = {"not_infected_probs": runner.probs, "new_infected": runner.new_infected,
+              **{k: runner.state[k] for k in DUMP_OUTPUTS[2:]}}
+    os.makedirs(path, exist_ok=True)
+    for name in DUMP_OUTPUTS:
+        np.save(os.path.join(path, name + ".npy"), arrays[name].index_select(0, rows).float().cpu().numpy())
+    np.save(os.path.join(path, "sums.npy"), np.array([float(arrays[n].double().sum()) for n in DUMP_OUTPUTS]))
+    np.save(os.path.join(path, "agent_id.npy"), ids.astype(np.float64))
+
+
 def auto_parts(n_agents: int) -> int:
     """One GPU: agent partitions stepped in turn (distributed.PartitionedHotPath).  Round 2 switched to partitions of
     16 M agents above 48 M, unmeasured; the round-3 sweeps (profiles/r03_c3_40m_parts*.json, r03_c5_100m_parts*.json)
@@ -635,8 +675,15 @@ def main():
     if args.generator == "auto":
         n_default = DEFAULT_AGENTS[args.preset]
         args.generator = "torch" if (args.agents or n_default) > 40_000_000 else "numpy"
+    if not args.full:                          # a plain run: the headline region alone
+        args.only_headline = True
+    if args.repeats is None:
+        args.repeats = 5 if (args.full or args.backward) else 1
     if args.only_headline:
         args.no_cpu_baseline, args.high_prevalence = True, 0.0
+    if args.dump_outputs and (args.gpus > 1 or args.force_distributed or args.parts > 1 or args.backward):
+        raise SystemExit("--dump-outputs: a single-GPU run of the forward step (no --gpus > 1, --force-distributed, "
+                         "--parts > 1 or --backward)")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args))
     # stdout carries exactly ONE line, the JSON result: libraries that print to fd 1 (RCCL's version banner
@@ -855,11 +902,13 @@ def main():
     repeats = [elapsed]
     for _ in range(max(0, args.repeats - 1)):         # the same region again, back to back: run-to-run spread
         repeats.append(region()[0])
+    if args.dump_outputs:
+        dump_outputs(runner, world, args.dump_outputs)
     if args.no_events and not distributed:
         for _ in range(args.steps):
             runner.step(timed=True)
         sync()
-    if distributed:
+    if distributed and args.full:
         # per-launch durations for N > 1: the same K steps again in the sequential, event-bracketed form
         for _ in range(args.steps):
             runner.step(timed=True)
@@ -967,9 +1016,9 @@ def main():
     n_edges = network_edges(world, networks)
     b_step = algorithmic_bytes(world, networks)
     kb = kernel_bytes(world, networks)
-    dom = max((k for k in kt if k in kb), key=kt.get)
+    dom = max((k for k in kt if k in kb), key=kt.get, default=None)     # None: N > 1 without --full times no launch
     share_f = 1.0 / world_size         # each rank streams its own partition
-    achieved = kb[dom] * share_f / (kt[dom] * 1e-3) / 1e9
+    achieved = None if dom is None else kb[dom] * share_f / (kt[dom] * 1e-3) / 1e9
     rep_ms = [1e3 * r / args.steps for r in repeats]
     out = {
         "metric": "simulation steps/sec",
@@ -996,13 +1045,15 @@ def main():
         "edges_per_s": sps * n_edges,
         "algorithmic_bytes_per_step": b_step,
         "step_roofline_frac": b_step * sps / (HBM_PEAK_GBS * 1e9 * world_size),
-        "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS, "traffic": None,
-                     "algorithmic_bytes_per_launch": kb[dom] * share_f, "ms_per_launch": kt[dom]},
+        "roofline": None if dom is None else {
+            "bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": achieved / HBM_PEAK_GBS, "traffic": None,
+            "algorithmic_bytes_per_launch": kb[dom] * share_f, "ms_per_launch": kt[dom]},
         "kernel_ms": kt,
         "kernel_ms_method": (f"HIP events around every launch of every {events_every}th step of the {len(repeats)} timed "
                              f"regions" if not distributed else
-                             "HIP events around every launch and collective of K further steps run in sequence"),
+                             "HIP events around every launch and collective of K further steps run in sequence" if args.full
+                             else "none: N > 1 times its launches in K further steps with --full"),
         # the K-step region run `repeats` times back to back: `value` / `ms_per_step` are the FIRST one
         "repeats": {"regions": len(rep_ms), "ms_per_step": rep_ms, "min": min(rep_ms),
                     "median": float(np.median(rep_ms)), "max": max(rep_ms)},
@@ -1012,11 +1063,12 @@ def main():
         "setup_s": {"generate": t_gen, "total": t_setup},
     }
     if distributed:
-        kernels_only = sum(v for k, v in kt.items() if k not in ("halo_all_to_all", "partial_all_reduce"))
         out["rccl_ranks"] = dist.get_world_size() if args.backend == "nccl" else 0
         out["backend"] = args.backend
         out["graph"] = graph_on
         out["graph_reason"] = graph_reason
+    if distributed and kt:
+        kernels_only = sum(v for k, v in kt.items() if k not in ("halo_all_to_all", "partial_all_reduce"))
         out["collective_ms_sequential"] = {k: kt[k] for k in ("halo_all_to_all", "partial_all_reduce") if k in kt}
         # what the production step (collectives overlapped with the phases that do not need them) takes beyond
         # this rank's kernels run back to back: collective time that did not hide + launch gaps
@@ -1051,7 +1103,8 @@ def main():
         with open(os.path.join(ROOT, "profiles", "pmc_traffic.json")) as f:
             pmc = json.load(f)
         w = pmc["workload"]
-        same_workload = (w["preset"], w["n_agents"], w["layout"]) == (args.preset, world["n_agents"], args.layout)
+        same_workload = dom is not None and (w["preset"], w["n_agents"], w["layout"]) == (args.preset, world["n_agents"],
+                                                                                          args.layout)
         if same_workload and world_size == 1 and pmc.get("csrc_sha256") == csrc_hash():
             out["roofline"]["traffic"] = pmc["per_launch_bytes"][dom]["total"]
             out["roofline"]["traffic_source"] = ("profiles/pmc_traffic.json (rocprofv3 --pmc FETCH_SIZE/WRITE_SIZE, "

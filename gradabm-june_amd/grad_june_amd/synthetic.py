@@ -186,6 +186,26 @@ def _venue_sizes(rng, dist, n_edges: int) -> np.ndarray:
     return sizes[sizes > 0]
 
 
+def _later_duplicates(key: np.ndarray) -> np.ndarray:
+    """dup[i] = key[i] also occurs at some j < i: every occurrence of a value but its first.  The same mask as a stable
+    argsort of all keys (keys >= 0), from an unstable sort (~10x faster on 15 M keys) and a stable one of the few
+    repeated keys."""
+    s = np.sort(key)
+    rep = np.unique(s[1:][s[1:] == s[:-1]])            # the values that occur more than once
+    dup = np.zeros(len(key), dtype=bool)
+    if len(rep) == 0:
+        return dup
+    bucket = np.zeros(1 << 20, dtype=bool)              # a cheap filter first (the low 20 bits), then the exact test
+    bucket[rep & 0xFFFFF] = True
+    cand = np.flatnonzero(bucket[key & 0xFFFFF])       # ascending
+    kc = key[cand]
+    cand = cand[rep[np.minimum(np.searchsorted(rep, kc), len(rep) - 1)] == kc]
+    _, first = np.unique(key[cand], return_index=True)  # (return_index: the first occurrence)
+    dup[cand] = True
+    dup[cand[first]] = False
+    return dup
+
+
 def _edge_set(rng, n_agents: int, n_edges: int, dist, geo=None, mix=None, members=None) -> dict:
     """``geo`` (a ``super_area_map``) + ``mix`` (the set's entry of GEOGRAPHY): the clustered form - memberships are
     dealt to the venue slots in the order of where they look for a venue, the slots lie along the curve.
@@ -213,10 +233,7 @@ def _edge_set(rng, n_agents: int, n_edges: int, dist, geo=None, mix=None, member
         agent = agent[np.argsort(_membership_keys(rng, agent, n_agents, geo, mix), kind="stable")]
     # no duplicate (agent, venue) pair: move the few collisions to the next venue
     for _ in range(4):
-        key = agent * V + venue
-        order = np.argsort(key, kind="stable")
-        dup = np.zeros(len(key), dtype=bool)
-        dup[order[1:]] = key[order[1:]] == key[order[:-1]]
+        dup = _later_duplicates(agent * V + venue)
         if not dup.any():
             break
         venue[dup] = (venue[dup] + 1) % V

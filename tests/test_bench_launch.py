@@ -10,6 +10,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -40,12 +41,54 @@ def test_more_ranks_than_gpus_is_refused_before_anything_starts():
     assert "one rank per GPU" in r.stderr and r.stdout.strip() == ""
 
 
+def test_dump_outputs_is_refused_where_no_single_gpu_step_is_timed(tmp_path):
+    """--dump-outputs writes what ONE GPU's timed step computed: asked of several ranks it says so, before anything
+    starts (runs without a GPU too)."""
+    r = _run("--gpus", "2", "--steps", "2", "--dump-outputs", str(tmp_path / "out"), timeout=120)
+    assert r.returncode == 1 and "--dump-outputs" in r.stderr and r.stdout.strip() == ""
+    assert not (tmp_path / "out").exists()
+
+
+@pytest.mark.gpu
+def test_a_plain_run_times_k_steps_and_dumps_what_the_last_one_computed(device, tmp_path):
+    """``bench.py --gpus 1 --steps K --warmup W``: one region of exactly K timed steps and none of what --full adds;
+    --dump-outputs writes the last timed step's outputs, and two runs with the same arguments write the same arrays
+    (fixed-point sums, Philox noise: the step is bitwise reproducible)."""
+    import bench as B
+
+    dumps = []
+    for run in ("a", "b"):
+        out = tmp_path / run
+        r = _run("--gpus", "1", "--agents", "300000", "--steps", "7", "--warmup", "2", "--tune", "off",
+                 "--dump-outputs", str(out))
+        assert r.returncode == 0, r.stderr[-4000:]
+        j = _one_json_line(r.stdout)
+        assert j["steps"] == 7 and j["warmup"] == 2 and j["repeats"]["regions"] == 1
+        assert j["value"] > 0 and abs(j["value"] - 1e3 / j["ms_per_step"]) < 1e-6 * j["value"]
+        assert j["state_checksum"]["infected"] == j["state_checksum"]["infected_after_first_region"]
+        assert not {"cpu_baseline", "full_step", "high_prevalence", "quarantine_social_distancing", "sustained"} & set(j)
+        files = {p.name[:-4]: np.load(p) for p in out.glob("*.npy")}
+        assert set(files) == set(B.DUMP_OUTPUTS) | {"sums", "agent_id"}
+        assert sum(p.stat().st_size for p in out.glob("*.npy")) <= 64 << 20
+        assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+        A = j["config"]["n_agents"]
+        assert np.array_equal(files["agent_id"], np.arange(A))          # fewer than 2^20 agents: every one of them
+        for k, name in enumerate(B.DUMP_OUTPUTS):
+            assert files[name].shape == (A,)
+            assert abs(files["sums"][k] - files[name].sum(dtype=np.float64)) <= 1e-9 * max(1.0, abs(files["sums"][k]))
+        assert files["sums"][B.DUMP_OUTPUTS.index("is_infected")] == j["state_checksum"]["infected"]
+        assert 0 < files["is_infected"].sum() < A and ((files["not_infected_probs"] >= 0) & (files["not_infected_probs"] <= 1)).all()
+        dumps.append(files)
+    for name in dumps[0]:
+        assert np.array_equal(dumps[0][name], dumps[1][name]), name
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("geography", ["random", "clustered"])
 def test_bench_starts_its_own_ranks(device, geography):
     """(both kinds of world: SURVEY 8d's uniformly random one and the one with a geography, synthetic.GEOGRAPHY)"""
     r = _run("--gpus", "2", "--backend", "gloo", "--agents", "400000", "--steps", "5", "--warmup", "2",
-             "--repeats", "2", "--geography", geography)
+             "--repeats", "2", "--geography", geography, "--full")
     assert r.returncode == 0, r.stderr[-4000:]
     j = _one_json_line(r.stdout)
     assert j["n_gpus"] == 2 and j["steps"] == 5 and j["warmup"] == 2 and j["scaling"] == "strong"
@@ -61,7 +104,7 @@ def test_bench_starts_its_own_ranks(device, geography):
         assert hh["local"] >= hh["venues"] - 5 and j["exchange"]["halo_agents_rank0"] < 60_000
     # the two ranks together computed what one GPU computes: same seed, same world, Philox keyed by global agent id
     r1 = _run("--gpus", "1", "--agents", "400000", "--steps", "5", "--warmup", "2", "--repeats", "2",
-              "--no-cpu-baseline", "--tune", "off", "--geography", geography)
+              "--no-cpu-baseline", "--tune", "off", "--geography", geography, "--full")
     assert r1.returncode == 0, r1.stderr[-4000:]
     j1 = _one_json_line(r1.stdout)
     # both runs make warm-up + repeats x steps (+ the sequential bracketed pass of N > 1) steps: compare equal step counts
@@ -79,21 +122,22 @@ def test_rccl_step_is_captured_and_validated_by_default(device):
     """One rank under the nccl backend: the production step (asynchronous collectives) is captured after the warm-up,
     ONE replay is compared with the eager step from the same state, and the timed region replays the graph."""
     r = _run("--gpus", "1", "--force-distributed", "--agents", "400000", "--steps", "6", "--warmup", "3",
-             "--repeats", "2", "--graph", "on")
+             "--repeats", "2", "--graph", "on", "--full")
     assert r.returncode == 0, r.stderr[-4000:]
     j = _one_json_line(r.stdout)
     assert j["rccl_ranks"] == 1 and j["backend"] == "nccl"
     assert j["graph"] is True, j["graph_reason"]
     # the default (--graph auto) also times replays against eager steps from one state and keeps the faster form; the
     # state is restored, so the run ends where the others end
-    r0 = _run("--gpus", "1", "--force-distributed", "--agents", "400000", "--steps", "6", "--warmup", "3", "--repeats", "2")
+    r0 = _run("--gpus", "1", "--force-distributed", "--agents", "400000", "--steps", "6", "--warmup", "3", "--repeats", "2",
+              "--full")
     assert r0.returncode == 0, r0.stderr[-4000:]
     j0 = _one_json_line(r0.stdout)
     assert "steps each from one state" in j0["graph_reason"] and ("replaying" in j0["graph_reason"]) == j0["graph"]
     assert j0["state_checksum"] == j["state_checksum"]
     # the same run with the eager production step ends in the same state
     r2 = _run("--gpus", "1", "--force-distributed", "--agents", "400000", "--steps", "6", "--warmup", "3",
-              "--repeats", "2", "--graph", "off")
+              "--repeats", "2", "--graph", "off", "--full")
     assert r2.returncode == 0, r2.stderr[-4000:]
     j2 = _one_json_line(r2.stdout)
     assert j2["graph"] is False and j2["state_checksum"] == j["state_checksum"]

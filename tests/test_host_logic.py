@@ -145,6 +145,40 @@ def test_no_cpu_path():
         nets(data=data, timer=t, policies=Policies())
 
 
+def test_duplicate_memberships_are_the_ones_a_stable_sort_finds():
+    """synthetic._later_duplicates: every occurrence of a key but its first - the mask a stable argsort of all keys
+    gives, which decided the seeded worlds (the venue a colliding membership moves to)."""
+    from grad_june_amd.synthetic import _later_duplicates
+
+    rng = np.random.default_rng(3)
+    for n, hi in ((0, 1), (1, 1), (7, 2), (5000, 40), (300_000, 10**5), (300_000, 10**13), (300_000, 1 << 40)):
+        key = rng.integers(0, hi, n)
+        if n > 10:
+            key[rng.integers(0, n, 50)] = key[rng.integers(0, n, 50)]   # a few repeats of the wide ranges too
+        order = np.argsort(key, kind="stable")
+        want = np.zeros(n, dtype=bool)
+        want[order[1:]] = key[order[1:]] == key[order[:-1]]
+        assert np.array_equal(_later_duplicates(key), want), (n, hi)
+
+
+@pytest.mark.parametrize("preset,n_agents,geography,digest", [
+    ("c3", 200_000, "random", "8f78b9ff9acf63ec"), ("c3", 200_000, "clustered", "e5bc1e024de4f1be"),
+    ("c2", 100_000, "random", "f7d6f00562139d0b")])
+def test_seeded_worlds_are_the_ones_every_figure_was_measured_on(preset, n_agents, geography, digest):
+    """The seeded generator is pinned bit for bit: the edge sets of these worlds (seed 7; leisure venues of this size
+    hold many colliding memberships) hash to fixed values, so that a faster generator still draws the same worlds."""
+    import hashlib
+
+    from grad_june_amd.synthetic import make_world
+
+    w = make_world(preset, n_agents=n_agents, seed=7, geography=geography)
+    h = hashlib.sha256()
+    for es in w["edge_sets"].values():
+        for k in ("agent", "venue", "people"):
+            h.update(np.ascontiguousarray(es[k], dtype=np.int64).tobytes())
+    assert h.hexdigest()[:16] == digest
+
+
 def test_roofline_accounting_matches_survey_8d():
     """bench.py's algorithmic bytes: B_step = 8*sum_sets E_s + 8*sum_n E_n + 12*sum_n V_n + (8N + 64)*A (SURVEY 8d);
     C3's sizes give the 3.05 GB quoted there, and the per-launch shares add up to it."""

@@ -54,7 +54,8 @@ def main():
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--build-only", action="store_true")
-    ap.add_argument("--common", default="--device-compile --no-cpu-baseline", help="bench.py arguments of every variant")
+    ap.add_argument("--common", default="--device-compile --no-cpu-baseline --full",
+                    help="bench.py arguments of every variant")
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "ab.jsonl"))
     a = ap.parse_args()
     vs = [parse_variant(v) for v in a.variants]

@@ -16,7 +16,7 @@ T="timeout -k 10"
 W="--world-cache /tmp/gj_worlds"
 
 echo "== default bench (the driver's command)" | tee -a "$out/log.txt"
-$T 600 python3 "$root/bench.py" > "$out/bench.json" 2> "$out/bench.log"
+$T 600 python3 "$root/bench.py" --full > "$out/bench.json" 2> "$out/bench.log"
 tail -c 600 "$out/bench.json" >> "$out/log.txt"
 
 echo "== kernel stats" | tee -a "$out/log.txt"
@@ -37,5 +37,5 @@ $T 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/backward_st
   python3 "$root/bench.py" --backward --backward-steps 4 --repeats 5 $W > "$out/backward_stats.log" 2>&1
 
 echo "== C2" | tee -a "$out/log.txt"
-$T 300 python3 "$root/bench.py" --preset c2 --no-cpu-baseline > "$out/c2.json" 2> "$out/c2.log"
+$T 300 python3 "$root/bench.py" --full --preset c2 --no-cpu-baseline > "$out/c2.json" 2> "$out/c2.log"
 echo "== done" | tee -a "$out/log.txt"
