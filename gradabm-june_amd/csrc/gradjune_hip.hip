@@ -663,6 +663,83 @@ __global__ __launch_bounds__(kThreads) void k_adjoint_transmission(
   grad_time[a] = grad_time[a] - tb * dtdt;                   // d t / d infection_time = -1
 }
 
+// psi(x) = d lgamma / dx (torch.digamma, the derivative torch's autograd gives lgamma), for the adjoint of the profile's
+// 1 / Gamma(shape).  x < 0: reflection psi(x) = psi(1 - x) - pi / tan(pi x), NaN at the poles; x == 0: -inf (torch:
+// copysign(inf, -x)).  x > 0: the recurrence psi(x) = psi(x + 1) - 1/x up to x >= 6, then the asymptotic series to
+// x^-6 (truncation: next term 1/(240 x^8) < 2.6e-9 there).  The error is that of fp32 rounding of the sum: a few ulp
+// of the largest term, i.e. ~1e-6 absolute for x >= 0.25 and a few ulp of 1/x below (x = 0.02: psi ~ -50, ~1e-5) -
+// over inv_gamma's fast range (0.25, 16) and its libm fallback range alike.  NaN in, NaN out.  No libm: v_log_f32
+// and (x < 0 only) v_sin/v_cos.
+__device__ __forceinline__ float digamma(float x) {
+  if (x == 0.0f) return copysignf(__builtin_inff(), -x);
+  float refl = 0.0f;
+  if (x < 0.0f) {
+    const float r = x - truncf(x);                     // (-1, 0]; tan(pi x) = tan(pi r)
+    if (r == 0.0f) return __builtin_nanf("");          // negative integer: a pole
+    // v_sin_f32 / v_cos_f32 take revolutions: sin(pi r) = sin(2 pi * r / 2)
+    refl = 3.14159265358979f * __builtin_amdgcn_cosf(0.5f * r) / __builtin_amdgcn_sinf(0.5f * r);
+    x = 1.0f - x;
+  }
+  float acc = 0.0f;
+  while (x < 6.0f) {                                   // (false for NaN)
+    acc += 1.0f / x;
+    x += 1.0f;
+  }
+  const float ix = 1.0f / x, ix2 = ix * ix;
+  float s = ix2 * (1.0f / 252.0f);
+  s = ix2 * (1.0f / 120.0f - s);
+  s = ix2 * (1.0f / 12.0f - s);
+  const float lnx = __builtin_amdgcn_logf(x) * 0.693147180559945309f;
+  return lnx - 0.5f * ix - s - acc - refl;
+}
+
+// The profile's adjoint w.r.t. its own per-agent parameters, on top of what k_adjoint_transmission computes (the same
+// grad_inf / grad_time, bit for bit).  With T the profile, d = t - shift, u = d * rate:
+//   dT/d max_inf = sign * aux * aux2 * is_infected   (not T / max_inf: max_inf == 0 is allowed)
+//   dT/d shape   = T * (ln u - psi(shape))           (torch: pow'(exponent) = pow * ln(base), masked to 0 at base == 0
+//                                                     with exponent >= 0; lgamma' = digamma)
+//   dT/d rate    = T * (shape / rate - d)
+//   dT/d shift   = T * (rate - (shape - 1) / d)      (= -dT/dt: the infection_time term shares it)
+// Each NULL output is neither computed nor written: a launch moves bytes only for the parameters that need a gradient.
+// is_infected == 0 gives 0 in every output.  (25 VGPRs, 0 scratch, occupancy 8: hipcc --offload-arch=gfx950
+// -O3 -ffp-contract=off -Rpass-analysis=kernel-resource-usage, the `resources` target of csrc/Makefile.)
+__global__ __launch_bounds__(kThreads) void k_adjoint_transmission_params(
+    int64_t n, const float* __restrict__ mx, const float* __restrict__ shp, const float* __restrict__ rt,
+    const float* __restrict__ sh, const float* __restrict__ time0, const float* __restrict__ inf0, float now,
+    const float* __restrict__ trans_bar, const float* __restrict__ g_inf, float* __restrict__ grad_inf,
+    float* __restrict__ grad_time, float* __restrict__ grad_mx, float* __restrict__ grad_shp,
+    float* __restrict__ grad_rt, float* __restrict__ grad_sh) {
+  const int64_t a = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (a >= n) return;
+  const float tb = trans_bar[a];
+  const float s = shp[a], r = rt[a];
+  const float t = now - time0[a];
+  const float d = t - sh[a];
+  const float sign = (sgnf(d + 1e-10f) + 1.0f) / 2.0f;
+  const float aux = inv_gamma(s) * fast_pow(d * r, s - 1.0f);
+  const float aux2 = fast_exp((sh[a] - t) * r) * r;
+  const float base = mx[a] * sign * aux * aux2;              // d trans / d is_infected
+  const float inf = inf0[a];
+  float p_mx = 0.0f, p_shp = 0.0f, p_rt = 0.0f, dtdt = 0.0f;  // d trans / d parameter; d trans / d t = -dT/d shift
+  if (inf != 0.0f) {
+    const float T = base * inf;
+    dtdt = T * ((s - 1.0f) / d - r);                         // (k_adjoint_transmission's op sequence)
+    if (grad_mx) p_mx = sign * aux * aux2 * inf;
+    if (grad_shp) {
+      const float u = d * r;
+      const float lnu = (u == 0.0f && s >= 1.0f) ? 0.0f : __builtin_amdgcn_logf(u) * 0.693147180559945309f;
+      p_shp = T * lnu - T * digamma(s);
+    }
+    if (grad_rt) p_rt = T * (s / r - d);
+  }
+  grad_inf[a] = (g_inf ? g_inf[a] : 0.0f) + tb * base;
+  grad_time[a] = grad_time[a] - tb * dtdt;                   // d t / d infection_time = -1
+  if (grad_mx) grad_mx[a] = tb * p_mx;
+  if (grad_shp) grad_shp[a] = tb * p_shp;
+  if (grad_rt) grad_rt[a] = tb * p_rt;
+  if (grad_sh) grad_sh[a] = 0.0f - tb * dtdt;               // (0 - x: no -0 for the uninfected)
+}
+
 // f3: d loss / d log_beta of the networks on one edge set (include/gradjune_hip.h, gj_adjoint_beta_*)
 struct AdjBetaArgs {
   int64_t n_venues;
@@ -1669,6 +1746,22 @@ int gj_adjoint_transmission(int64_t n, const gj_agent_state* st, float now, cons
                      dim3(gj::kThreads), 0, (hipStream_t)stream, n, st->max_infectiousness, st->shape, st->rate,
                      st->shift, st->infection_time, st->is_infected, now, trans_bar, g_inf, grad_inf_out,
                      grad_time_inout);
+  return gj::launch_status();
+}
+
+int gj_adjoint_transmission_params(int64_t n, const gj_agent_state* st, float now, const float* trans_bar,
+                                   const float* g_inf, float* grad_inf_out, float* grad_time_inout,
+                                   float* grad_max_infectiousness_out, float* grad_shape_out, float* grad_rate_out,
+                                   float* grad_shift_out, void* stream) {
+  if (n < 0) return GJ_E_RANGE;
+  if (n == 0) return GJ_OK;
+  if (!st || !trans_bar || !grad_inf_out || !grad_time_inout) return GJ_E_NULL;
+  if (!st->max_infectiousness || !st->shape || !st->rate || !st->shift || !st->infection_time || !st->is_infected)
+    return GJ_E_NULL;
+  hipLaunchKernelGGL(gj::k_adjoint_transmission_params, dim3((unsigned)((n + gj::kThreads - 1) / gj::kThreads)),
+                     dim3(gj::kThreads), 0, (hipStream_t)stream, n, st->max_infectiousness, st->shape, st->rate,
+                     st->shift, st->infection_time, st->is_infected, now, trans_bar, g_inf, grad_inf_out,
+                     grad_time_inout, grad_max_infectiousness_out, grad_shape_out, grad_rate_out, grad_shift_out);
   return gj::launch_status();
 }
 

@@ -10,7 +10,7 @@ import ctypes as C
 import os
 from typing import Optional
 
-GJ_ABI_VERSION = 6
+GJ_ABI_VERSION = 7
 GJ_MAX_SETS = 12
 GJ_MAX_NETS = 16
 GJ_MAX_NETS_PER_SET = 8
@@ -203,6 +203,8 @@ SYMBOLS = {
          _vp, _vp, _vp, _vp],
     ),
     "gj_adjoint_transmission": (C.c_int, [C.c_int64, C.POINTER(AgentState), C.c_float, _vp, _vp, _vp, _vp, _vp]),
+    "gj_adjoint_transmission_params": (
+        C.c_int, [C.c_int64, C.POINTER(AgentState), C.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gj_adjoint_beta_partial": (
         C.c_int,
         [C.c_int64, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, C.POINTER(C.c_float), C.POINTER(C.c_int32), _vp, _vp],

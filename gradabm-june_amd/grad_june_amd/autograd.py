@@ -35,6 +35,7 @@ import os
 from . import _native as N
 from .engine import AgentBuffers
 from .plan import SPLIT_SUFFIX
+from .transmission import PROFILE
 
 KEEP_FORWARD_SUMS = os.environ.get("GJ_BACKWARD_RECOMPUTE", "0") in ("", "0")
 
@@ -161,14 +162,46 @@ def _param_grads(nets, grads):
     return out
 
 
+def _adjoint_profile(n, st0, now, tbar, g_inf, grad_inf, grad_time, want, dev):
+    """Through the transmission profile: grad_inf = g_inf + tbar * dT/d is_infected, grad_time += tbar * dT/dt, and -
+    for each of the four profile parameters ``want`` flags - tbar * dT/d parameter (None for the others).  With no flag
+    set this is the launch the step has always made (gj_adjoint_transmission); otherwise gj_adjoint_transmission_params,
+    whose grad_inf / grad_time are the same bit for bit and which writes only the requested parameter gradients."""
+    lib = N.load()
+    if not any(want):
+        N.check(lib.gj_adjoint_transmission(n, C.byref(st0.c), float(now), N.ptr(tbar), N.ptr(g_inf), N.ptr(grad_inf),
+                                            N.ptr(grad_time), N.current_stream()), "gj_adjoint_transmission")
+        return [None] * len(PROFILE)
+    outs = [torch.empty(n, dtype=torch.float32, device=dev) if w else None for w in want]
+    N.check(lib.gj_adjoint_transmission_params(n, C.byref(st0.c), float(now), N.ptr(tbar), N.ptr(g_inf),
+                                               N.ptr(grad_inf), N.ptr(grad_time), *[N.ptr(o) for o in outs],
+                                               N.current_stream()), "gj_adjoint_transmission_params")
+    return outs
+
+
+def _profile_wanted(ctx, n_nets):
+    """Which of the four profile tensors (the inputs after the log_betas, when the caller passed them) need a gradient."""
+    flags = tuple(ctx.needs_input_grad[4 + n_nets:])
+    return flags if flags else (False,) * len(PROFILE)
+
+
+def _profile_grads(ctx, n_nets, grads):
+    """The profile gradients in the order of the node's inputs (nothing when the caller passed no profile tensors)."""
+    if len(ctx.needs_input_grad) <= 4 + n_nets:
+        return []
+    return [None if g is None else g.to(dev) for g, dev in zip(grads, ctx.profile_devices)]
+
+
 class HotPathStep(torch.autograd.Function):
-    """(susceptibility, is_infected, infection_time, *log_betas) -> (susceptibility', is_infected',
-    infection_time', new_infected)."""
+    """(susceptibility, is_infected, infection_time, *log_betas[, max_infectiousness, shape, rate, shift]) ->
+    (susceptibility', is_infected', infection_time', new_infected).  The four profile tensors are optional inputs
+    (the step reads ``env["fixed"]``, their detached values): passed, they receive d loss / d parameter per agent."""
 
     @staticmethod
-    def forward(ctx, env, susc, inf, time, *log_betas):
+    def forward(ctx, env, susc, inf, time, *log_betas_and_profile):
         engine, params, fixed, stage, exp_noise, nets = (env[k] for k in ("engine", "params", "fixed", "stage",
                                                                            "exp_noise", "nets"))
+        ctx.profile_devices = [t.device for t in log_betas_and_profile[len(nets):]]
         plan = engine.plan
         n = plan.host.n_agents
         out_s, out_i, out_t = (t.detach().to(torch.float32).clone().contiguous() for t in (susc, inf, time))
@@ -227,10 +260,8 @@ class HotPathStep(torch.autograd.Function):
         grad_inf = torch.empty(n, dtype=torch.float32, device=dev)
         st0 = AgentBuffers(plan, **fixed, infection_time=time0, is_infected=inf0, susceptibility=ones,
                            transmission=scratch)
-        N.check(lib.gj_adjoint_transmission(n, C.byref(st0.c), float(p.now), N.ptr(tbar), N.ptr(g_inf),
-                                            N.ptr(grad_inf), N.ptr(grad_time), N.current_stream()),
-                "gj_adjoint_transmission")
-        return (None, grad_susc, grad_inf, grad_time, *_param_grads(nets, grads))
+        pg = _adjoint_profile(n, st0, p.now, tbar, g_inf, grad_inf, grad_time, _profile_wanted(ctx, len(nets)), dev)
+        return (None, grad_susc, grad_inf, grad_time, *_param_grads(nets, grads), *_profile_grads(ctx, len(nets), pg))
 
 
 class DistributedHotPathStep(torch.autograd.Function):
@@ -243,8 +274,9 @@ class DistributedHotPathStep(torch.autograd.Function):
     result series: ``distributed_api.DistributedRunner``)."""
 
     @staticmethod
-    def forward(ctx, env, susc, inf, time, *log_betas):
+    def forward(ctx, env, susc, inf, time, *log_betas_and_profile):
         hp, params_of, fixed, stage, exp_noise = (env[k] for k in ("hp", "params_of", "fixed", "stage", "exp_noise"))
+        ctx.profile_devices = [t.device for t in log_betas_and_profile[len(env["nets"]):]]
         plan = hp.engine.plan
         n = plan.host.n_agents
         out_s, out_i, out_t = (t.detach().to(torch.float32).clone().contiguous() for t in (susc, inf, time))
@@ -322,13 +354,53 @@ class DistributedHotPathStep(torch.autograd.Function):
         total = hp.all_reduce_sum(torch.stack(grads)) if grads else None        # fp64: the world's gradient
         grads32 = [total[i].to(torch.float32) for i in range(len(grads))]
         # ---- through the transmission profile (owned agents) --------------------------------------------------------
+        # (tbar is complete for the owned agents after the transposed passes: their profile gradients need no collective)
         grad_inf = torch.empty(n, dtype=torch.float32, device=dev)
         st0 = AgentBuffers(plan, **fixed, infection_time=time0, is_infected=inf0, susceptibility=ones,
                            transmission=scratch)
-        N.check(lib.gj_adjoint_transmission(n, C.byref(st0.c), float(p.now), N.ptr(tbar), N.ptr(g_inf),
-                                            N.ptr(grad_inf), N.ptr(grad_time), N.current_stream()),
-                "gj_adjoint_transmission")
-        return (None, grad_susc, grad_inf, grad_time, *_param_grads(nets, grads32))
+        pg = _adjoint_profile(n, st0, p.now, tbar, g_inf, grad_inf, grad_time, _profile_wanted(ctx, len(nets)), dev)
+        return (None, grad_susc, grad_inf, grad_time, *_param_grads(nets, grads32), *_profile_grads(ctx, len(nets), pg))
+
+
+class TransmissionProfile(torch.autograd.Function):
+    """The stand-alone ``TransmissionUpdater.forward`` (transmission.py:39-51) as an autograd node:
+    (max_infectiousness, shape, rate, shift, infection_time, is_infected) -> transmission, differentiable w.r.t. all
+    six like the reference's plain torch ops.  Forward = ``gj_transmission_update``; backward = one
+    ``gj_adjoint_transmission_params`` launch that writes only the gradients autograd asks for."""
+
+    @staticmethod
+    def forward(ctx, env, mx, shape, rate, shift, time, inf):
+        engine, p = env["engine"], env["params"]
+        plan = engine.plan
+        n, dev = plan.host.n_agents, plan.device
+        f = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
+        vals = [f(t) for t in (mx, shape, rate, shift, time, inf)]
+        out = torch.empty(n, dtype=torch.float32, device=dev)
+        bufs = AgentBuffers(plan, **dict(zip(PROFILE, vals[:4])), infection_time=vals[4], is_infected=vals[5],
+                            susceptibility=_ones(plan, n), transmission=out)
+        engine.transmission_update(bufs, p)
+        ctx.engine, ctx.now = engine, float(p.now)
+        ctx.devices = [t.device for t in (mx, shape, rate, shift, time, inf)]
+        ctx.save_for_backward(*vals)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        plan = ctx.engine.plan
+        n, dev = plan.host.n_agents, plan.device
+        vals = ctx.saved_tensors
+        tbar = g.detach().to(device=dev, dtype=torch.float32).contiguous()
+        st0 = AgentBuffers(plan, **dict(zip(PROFILE, vals[:4])), infection_time=vals[4], is_infected=vals[5],
+                           susceptibility=_ones(plan, n), transmission=tbar)
+        grad_inf = torch.empty(n, dtype=torch.float32, device=dev)
+        grad_time = torch.zeros(n, dtype=torch.float32, device=dev)
+        want = ctx.needs_input_grad[1:5]
+        outs = [torch.empty(n, dtype=torch.float32, device=dev) if w else None for w in want]
+        N.check(N.load().gj_adjoint_transmission_params(n, C.byref(st0.c), ctx.now, N.ptr(tbar), None, N.ptr(grad_inf),
+                                                        N.ptr(grad_time), *[N.ptr(o) for o in outs],
+                                                        N.current_stream()), "gj_adjoint_transmission_params")
+        grads = outs + [grad_time if ctx.needs_input_grad[5] else None, grad_inf if ctx.needs_input_grad[6] else None]
+        return (None, *[None if gr is None else gr.to(d) for gr, d in zip(grads, ctx.devices)])
 
 
 class AllReduceSum(torch.autograd.Function):

@@ -32,6 +32,7 @@ from .model import GradJune
 from .plan import SPLIT_SUFFIX
 from .runner import Runner
 from .timer import Timer
+from .transmission import profile_inputs, profile_requires_grad
 from .world import require_hip
 
 
@@ -91,7 +92,8 @@ class DistributedGradJune(GradJune):
         active = nets.active_networks(timer, self.policies)
         differentiable = torch.is_grad_enabled() and (
             any(isinstance(n.log_beta, torch.Tensor) and n.log_beta.requires_grad for n in active)
-            or any(data["agent"][k].requires_grad for k in ("susceptibility", "is_infected", "infection_time")))
+            or any(data["agent"][k].requires_grad for k in ("susceptibility", "is_infected", "infection_time"))
+            or profile_requires_grad(data))
         self.policies.apply(timer=timer, data=data)
         engine, dev, n = hp.engine, hp.device, hp.rw.n_local
         for net in active:
@@ -172,7 +174,8 @@ class DistributedGradJune(GradJune):
                "nets": list(active), "betas": dict(betas)}
         state = [ag[k] if ag[k].dtype == torch.float32 else ag[k].to(torch.float32) for k in
                  ("susceptibility", "is_infected", "infection_time")]
-        susc, inf, time, new_infected = DistributedHotPathStep.apply(env, *state, *[n_.log_beta for n_ in active])
+        susc, inf, time, new_infected = DistributedHotPathStep.apply(env, *state, *[n_.log_beta for n_ in active],
+                                                                     *profile_inputs(ip))
         ag.susceptibility, ag.is_infected, ag.infection_time = susc, inf, time
         ag.transmission = hp.state["transmission"][:n]
         return new_infected, None

@@ -75,6 +75,10 @@ def infect_people(data, timer, new_infected):
 def infect_fraction_of_people(data, timer, symptoms_updater, fraction, device, exp_noise=None, agent_offset=0):
     """Seed: every agent infected independently with probability ``fraction`` (a8+a9 fused launch).
     ``agent_offset``: global id of local agent 0 when ``data`` is one rank's part of a partitioned world."""
+    if torch.is_grad_enabled() and isinstance(fraction, torch.Tensor) and fraction.requires_grad:
+        # float(fraction) below would cut the gradient without a word: say so instead
+        raise NotImplementedError("gradients w.r.t. the initial-case fraction (log_fraction_initial_cases) are not "
+                                  "implemented (pass a plain number or tensor, or run under torch.no_grad())")
     device = require_hip(device)
     ag = data["agent"]
     n = ag.id.shape[0]

@@ -63,6 +63,10 @@ class InfectionNetwork(torch.nn.Module):
         ip = getattr(policies, "interaction_policies", None)
         if ip:
             beta = ip.apply(beta=beta, name=self.name, timer=timer)
+        if torch.is_grad_enabled() and isinstance(beta, torch.Tensor) and beta.requires_grad:
+            # a factor that requires a gradient would be cut here without a word: say so instead
+            raise NotImplementedError(f"network '{self.name}': gradients w.r.t. SocialDistancing beta factors are not "
+                                      "implemented (make the factor a plain tensor, or run under torch.no_grad())")
         return float(beta)
 
     # introspection helpers with the reference's names --------------------------------------------

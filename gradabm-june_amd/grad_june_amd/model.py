@@ -15,7 +15,7 @@ from .infection import IsInfectedSampler
 from .infection_networks import InfectionNetworks
 from .policies import Policies
 from .symptoms import SymptomsUpdater
-from .transmission import TransmissionUpdater
+from .transmission import TransmissionUpdater, profile_inputs, profile_requires_grad
 from .world import agent_buffers, engine_for, require_hip
 
 
@@ -63,7 +63,8 @@ class GradJune(torch.nn.Module):
         active = nets.active_networks(timer, self.policies)
         differentiable = torch.is_grad_enabled() and (
             any(isinstance(n.log_beta, torch.Tensor) and n.log_beta.requires_grad for n in active)
-            or any(data["agent"][k].requires_grad for k in ("susceptibility", "is_infected", "infection_time")))
+            or any(data["agent"][k].requires_grad for k in ("susceptibility", "is_infected", "infection_time"))
+            or profile_requires_grad(data))
         self.policies.apply(timer=timer, data=data)
         engine = engine_for(data, [n.spec() for n in nets.networks.values()], device)
         for n in active:
@@ -109,7 +110,8 @@ class GradJune(torch.nn.Module):
                "nets": list(active), "betas": {n_.name: float(params.nets[i].beta) for i, n_ in enumerate(active)}}
         state = [ag[k] if ag[k].dtype == torch.float32 else ag[k].to(torch.float32) for k in
                  ("susceptibility", "is_infected", "infection_time")]
-        susc, inf, time, new_infected = HotPathStep.apply(env, *state, *[n_.log_beta for n_ in active])
+        susc, inf, time, new_infected = HotPathStep.apply(env, *state, *[n_.log_beta for n_ in active],
+                                                          *profile_inputs(ip))
         ag.susceptibility, ag.is_infected, ag.infection_time = susc, inf, time
         return new_infected, None
 

@@ -18,7 +18,7 @@ from .graph import HeteroData, ToUndirected, load_world
 from .infection import infect_fraction_of_people
 from .model import GradJune
 from .timer import Timer
-from .transmission import TransmissionSampler
+from .transmission import TransmissionSampler, profile_requires_grad
 from .utils import read_path
 from .world import require_hip
 
@@ -187,11 +187,12 @@ class Runner(torch.nn.Module):
         else:
             n_rows = 4096
         self._series = torch.zeros(n_rows, 2 + n_bins, dtype=torch.float64, device=require_hip(self.device))
-        # differentiable run (a log_beta is an nn.Parameter, grad mode on): the case series must stay on
-        # the autograd graph, so they are formed with tensor ops instead of the fused reduction kernel
-        differentiable = torch.is_grad_enabled() and any(
+        # differentiable run (a log_beta is an nn.Parameter or a profile tensor requires a gradient, grad mode on):
+        # the case series must stay on the autograd graph, so they are formed with tensor ops instead of the fused
+        # reduction kernel
+        differentiable = torch.is_grad_enabled() and (any(
             isinstance(n.log_beta, torch.Tensor) and n.log_beta.requires_grad
-            for n in model.infection_networks.networks.values())
+            for n in model.infection_networks.networks.values()) or profile_requires_grad(data))
         diff_rows = []
 
         def record(row, done=False):

@@ -14,6 +14,23 @@ from .utils import parse_distribution
 from .world import agent_buffers, engine_for, require_hip
 
 
+PROFILE = ("max_infectiousness", "shape", "rate", "shift")
+
+
+def profile_requires_grad(data) -> bool:
+    """True when one of the four per-agent profile tensors requires a gradient (e.g. drawn with ``rsample`` from
+    distributions whose parameters are ``nn.Parameter``s, transmission.py:15-20 of the reference)."""
+    ip = data["agent"]["infection_parameters"]
+    return any(isinstance(ip[k], torch.Tensor) and ip[k].requires_grad for k in PROFILE)
+
+
+def profile_inputs(ip):
+    """The profile tensors as extra inputs of a step node when one of them requires a gradient, else none (the node
+    then runs exactly as without them)."""
+    ts = [ip[k] for k in PROFILE]
+    return ts if any(isinstance(t, torch.Tensor) and t.requires_grad for t in ts) else []
+
+
 class TransmissionSampler:
     def __init__(self, max_infectiousness, shape, rate, shift):
         self.max_infectiousness = max_infectiousness
@@ -47,6 +64,15 @@ class TransmissionUpdater(torch.nn.Module):
         ag = data["agent"]
         device = require_hip(ag["is_infected"].device)
         engine = engine_for(data, [], device)      # the transmission kernel needs no edge set
+        ip = ag["infection_parameters"]
+        inputs = [ip[k] for k in PROFILE] + [ag["infection_time"], ag["is_infected"]]
+        if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in inputs):
+            # differentiable w.r.t. the four parameters and the state, like the reference's torch ops
+            from .autograd import TransmissionProfile
+
+            p = engine.params(now=timer.now, delta_time=timer.duration, day_type=0, active=[], betas={},
+                              has_quarantine=False, q_threshold=math.inf)
+            return TransmissionProfile.apply({"engine": engine, "params": p}, *inputs)
         out = torch.empty(engine.plan.host.n_agents, dtype=torch.float32, device=device)
         bufs = agent_buffers(engine, data, need_params=True, need_stage=False)
         bufs.tensors["transmission"] = out

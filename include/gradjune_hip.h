@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define GJ_ABI_VERSION 6
+#define GJ_ABI_VERSION 7
 
 #define GJ_MAX_SETS 12        /* distinct agent<->venue edge sets in a world (reference: 6)   */
 #define GJ_MAX_NETS 16        /* infection networks active in one step (reference: <= 11)      */
@@ -404,7 +404,14 @@ int gj_symptoms_step_stats(int64_t n, const uint8_t* agent_class, const float* n
  *   grad_time_out = g_time * (1 - new_infected).
  * gj_adjoint_transmission: through the transmission profile (transmission.py:39-51):
  *   grad_inf_out = g_inf + trans_bar * d trans/d is_infected;
- *   grad_time_inout += trans_bar * d trans/d infection_time.                                        */
+ *   grad_time_inout += trans_bar * d trans/d infection_time.
+ * gj_adjoint_transmission_params (ABI 7): the same two outputs, bit for bit, plus the gradients w.r.t. the profile's
+ *   own per-agent parameters (the reference draws them with rsample, transmission.py:15-20, so a calibration can
+ *   differentiate the distributions' loc / scale through them):  grad_<p>_out[a] = trans_bar[a] * d trans[a] / d p[a]
+ *   with d = t - shift, u = d * rate:  d/d max_infectiousness = sign * aux * aux2 * is_infected,
+ *   d/d shape = trans * (ln u - digamma(shape)), d/d rate = trans * (shape / rate - d),
+ *   d/d shift = trans * (rate - (shape - 1) / d); 0 where is_infected == 0.  Each of the four outputs may be NULL:
+ *   a NULL output is neither computed nor written.                                                    */
 int gj_adjoint_sample(int64_t n, const float* susceptibility0, const float* infection_time0, const float* acc,
                       const float* exp_noise, uint64_t seed, uint64_t step, int64_t agent_offset, float now,
                       float delta_time, const float* g_susc, const float* g_inf, const float* g_time,
@@ -412,6 +419,10 @@ int gj_adjoint_sample(int64_t n, const float* susceptibility0, const float* infe
                       void* stream);
 int gj_adjoint_transmission(int64_t n, const gj_agent_state* state0, float now, const float* trans_bar,
                             const float* g_inf, float* grad_inf_out, float* grad_time_inout, void* stream);
+int gj_adjoint_transmission_params(int64_t n, const gj_agent_state* state0, float now, const float* trans_bar,
+                                   const float* g_inf, float* grad_inf_out, float* grad_time_inout,
+                                   float* grad_max_infectiousness_out, float* grad_shape_out, float* grad_rate_out,
+                                   float* grad_shift_out, void* stream);
 
 /* d loss / d log_beta of the networks on ONE edge set, from the forward's and the transposed passes' per-venue sums:
  *   col0 + k :  ln(10) * scale * sum_v [p_contact[v] > 0]  cum_fwd[v][k] * cum_bwd[v][k] / (beta[k] * p_contact[v]) * weight[v]
