@@ -952,6 +952,190 @@ __global__ __launch_bounds__(kThreads) void k_symptoms_stats(const SymptomsArgs 
   }
 }
 
+// f2 by agent group (gj_group_stats): segmented sums of is_infected and of the deaths indicator over an int32 label.
+// Summed as 64-bit integers (is_infected in 32.32 fixed point, deaths as a count), so every order of the additions
+// gives the same bits.  Each lane carries ONE open run (label, two sums) across its agents; a run is closed when the
+// lane meets another label.  Closing is done by the whole wave: the lanes that close the same label fold their sums
+// with shuffles and one of them adds (two rounds, which is what a wave that straddles a boundary of sorted labels
+// needs; lanes still open after them add on their own).  LDS = true: the adds go to this workgroup's histogram in LDS,
+// which is added to the workspace at the end, one global atomic per non-zero accumulator.  LDS = false: the adds are
+// global atomics on the workspace.  A workgroup owns a CONTIGUOUS share of the agents, so that sorted labels give it
+// few groups.
+constexpr int kGroupFxBits = 32;
+constexpr int kGroupLdsMax = 4096;       // 2 * 8 B * 4096 = 64 KiB of LDS per workgroup: two workgroups per CU
+constexpr int kGroupLdsThreads = 1024, kGroupLdsBlocks = 512;
+constexpr int kGroupAdjLdsMax = 2048;    // gj_adjoint_group_stats stages 2 * 4 B * 2048 = 16 KiB per workgroup (above
+                                         // that, filling the copy costs more than the gathers it saves)
+constexpr uint32_t kGroupBadLabel = 1u, kGroupBadValue = 2u;    // GJ_GROUP_ERR_LABEL / GJ_GROUP_ERR_VALUE
+
+struct GroupArgs {
+  int64_t n;
+  const int32_t* group;
+  const float* inf;
+  const float* stage;
+  int32_t n_groups;
+  int32_t dead;
+  int32_t vec4;     // all three arrays 16-byte aligned
+  fx_t* ws;         // [2 * n_groups] sums, then the error word
+};
+
+__device__ __forceinline__ fx_t wave_sum_u64(fx_t v) {
+#pragma unroll
+  for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
+  return v;
+}
+
+template <bool LDS>
+__global__ __launch_bounds__(LDS ? kGroupLdsThreads : kThreads) void k_group_stats(const GroupArgs S) {
+  extern __shared__ fx_t hist[];     // LDS: [2 * n_groups]
+  const int G = S.n_groups;
+  if (LDS) {
+    for (int i = threadIdx.x; i < 2 * G; i += blockDim.x) hist[i] = 0;
+    __syncthreads();
+  }
+  const int lane = threadIdx.x % kWave;
+  int run = -1;            // label of this lane's open run
+  fx_t rc = 0, rd = 0;     // its sums: cases (fixed point), deaths (count)
+  uint32_t err = 0;
+  auto add = [&](int g, fx_t c, fx_t d) {
+    fx_t* dst = LDS ? hist : S.ws;
+    if (c) atomicAdd(&dst[g], c);
+    if (d) atomicAdd(&dst[G + g], d);
+  };
+  // wave-convergent: closes the run of every lane with `closing` set
+  auto close_runs = [&](bool closing) {
+    closing = closing && run >= 0;
+#pragma unroll 1
+    for (int round = 0; round < 2; ++round) {
+      const unsigned long long m = __ballot(closing);
+      if (m == 0) return;
+      const int leader = __ffsll((long long)m) - 1;
+      const int label = __shfl(run, leader, kWave);
+      const bool mine = closing && run == label;
+      const fx_t c = wave_sum_u64(mine ? rc : 0), d = wave_sum_u64(mine ? rd : 0);
+      if (lane == leader) add(label, c, d);
+      if (mine) closing = false, run = -1, rc = 0, rd = 0;
+    }
+    if (closing) add(run, rc, rd), run = -1, rc = 0, rd = 0;
+  };
+  // wave-convergent: one agent per lane (`on` = this lane has one)
+  auto take = [&](bool on, int g, float inf, float stage) {
+    if (on && (uint32_t)g >= (uint32_t)G) err |= kGroupBadLabel, on = false;   // never an index: the agent is skipped
+    const bool differs = on && g != run;
+    if (__any(differs && run >= 0)) close_runs(differs);
+    if (!on) return;
+    run = g;
+    const bool ok = fabsf(inf) <= fx_max<kGroupFxBits>();      // false for NaN too
+    if (!ok) err |= kGroupBadValue;
+    rc += to_fx<kGroupFxBits>(ok ? inf : 0.0f);
+    rd += (stage == (float)S.dead) ? 1u : 0u;
+  };
+  // this workgroup's share, in units of four agents (vec4) or of one
+  const int64_t units = S.vec4 ? (S.n >> 2) : S.n;
+  const int64_t per = (units + gridDim.x - 1) / gridDim.x;
+  const int64_t u0 = (int64_t)blockIdx.x * per, u1 = (u0 + per < units) ? u0 + per : units;
+  for (int64_t base = u0; base < u1; base += blockDim.x) {     // (the same trip count for every lane of a wave)
+    const int64_t i = base + threadIdx.x;
+    const bool on = i < u1;
+    if (S.vec4) {
+      int4 g = make_int4(0, 0, 0, 0);
+      float4 f = make_float4(0.f, 0.f, 0.f, 0.f), s = f;
+      if (on) {
+        g = reinterpret_cast<const int4*>(S.group)[i];
+        f = reinterpret_cast<const float4*>(S.inf)[i];
+        s = reinterpret_cast<const float4*>(S.stage)[i];
+      }
+      take(on, g.x, f.x, s.x);
+      take(on, g.y, f.y, s.y);
+      take(on, g.z, f.z, s.z);
+      take(on, g.w, f.w, s.w);
+    } else {
+      take(on, on ? S.group[i] : 0, on ? S.inf[i] : 0.f, on ? S.stage[i] : 0.f);
+    }
+  }
+  if (S.vec4 && blockIdx.x == gridDim.x - 1 && threadIdx.x < kWave) {     // the n % 4 agents behind the last float4
+    const int64_t a = (units << 2) + threadIdx.x;
+    const bool on = a < S.n;
+    take(on, on ? S.group[a] : 0, on ? S.inf[a] : 0.f, on ? S.stage[a] : 0.f);
+  }
+  close_runs(true);
+  if (err) atomicOr(reinterpret_cast<uint32_t*>(S.ws + 2 * (int64_t)G), err);
+  if (LDS) {
+    __syncthreads();
+    for (int i = threadIdx.x; i < 2 * G; i += blockDim.x) {
+      const fx_t v = hist[i];
+      if (v) atomicAdd(&S.ws[i], v);
+    }
+  }
+}
+
+// out += the sums as doubles (once, so the rounding does not depend on any order); the sums are zeroed for the next call
+__global__ __launch_bounds__(kThreads) void k_group_finish(int32_t n_groups, fx_t* ws, double* out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= 2 * (int64_t)n_groups) return;
+  const fx_t v = ws[i];
+  if (v == 0) return;
+  ws[i] = 0;
+  out[i] += (i < n_groups) ? (double)(long long)v * (1.0 / (double)(1ull << kGroupFxBits)) : (double)v;
+}
+
+// adjoint of gj_group_stats: a gather through the labels
+struct GroupAdjArgs {
+  int64_t n;
+  const int32_t* group;
+  const float* stage;
+  const float* g_cases;
+  const float* g_deaths;
+  float* grad_inf;
+  float* grad_stage;
+  int32_t n_groups;
+  int32_t dead;
+  int32_t vec4;
+};
+
+template <bool LDS>
+__global__ __launch_bounds__(kThreads) void k_adjoint_group_stats(const GroupAdjArgs S) {
+  extern __shared__ float staged[];     // LDS: g_cases [n_groups], g_deaths [n_groups]
+  const int G = S.n_groups;
+  const float* gc = S.g_cases;
+  const float* gd = S.g_deaths;
+  if (LDS) {
+    for (int i = threadIdx.x; i < G; i += blockDim.x) {
+      staged[i] = gc ? gc[i] : 0.0f;
+      staged[G + i] = gd ? gd[i] : 0.0f;
+    }
+    __syncthreads();
+    gc = staged;
+    gd = staged + G;
+  }
+  const float dead = (float)S.dead;
+  auto cases = [&](int g) { return ((uint32_t)g < (uint32_t)G && gc) ? gc[g] : 0.0f; };
+  auto deaths = [&](int g, float st) {      // autograd of (stage == dead) * stage / dead: (g / dead) * mask
+    const float v = ((uint32_t)g < (uint32_t)G && gd) ? gd[g] : 0.0f;
+    return v / dead * (st == dead ? 1.0f : 0.0f);
+  };
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  int64_t first_scalar = 0;
+  if (S.vec4) {
+    const int64_t n4 = S.n >> 2;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+      const int4 g = reinterpret_cast<const int4*>(S.group)[i];
+      if (S.grad_inf) reinterpret_cast<float4*>(S.grad_inf)[i] = make_float4(cases(g.x), cases(g.y), cases(g.z), cases(g.w));
+      if (S.grad_stage) {
+        const float4 s = reinterpret_cast<const float4*>(S.stage)[i];
+        reinterpret_cast<float4*>(S.grad_stage)[i] =
+            make_float4(deaths(g.x, s.x), deaths(g.y, s.y), deaths(g.z, s.z), deaths(g.w, s.w));
+      }
+    }
+    first_scalar = n4 << 2;
+  }
+  for (int64_t a = first_scalar + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; a < S.n; a += stride) {
+    const int g = S.group[a];
+    if (S.grad_inf) S.grad_inf[a] = cases(g);
+    if (S.grad_stage) S.grad_stage[a] = deaths(g, S.stage[a]);
+  }
+}
+
 // a2 alone: q*transmission for a caller-supplied transmission vector
 __global__ __launch_bounds__(kThreads) void k_quarantine_transmission(int64_t n, const float* __restrict__ stage,
                                                                       const float* __restrict__ trans,
@@ -1919,6 +2103,71 @@ int gj_symptoms_step_stats(int64_t n, const uint8_t* agent_class, const float* n
   if (blocks > 4096) blocks = 4096;
   if (blocks < 1) blocks = 1;
   hipLaunchKernelGGL(gj::k_symptoms_stats, dim3((unsigned)blocks), dim3(gj::kThreads), 0, (hipStream_t)stream, S, R);
+  return gj::launch_status();
+}
+
+int gj_group_stats(int64_t n, const int32_t* group, int32_t n_groups, const float* is_infected,
+                   const float* current_stage, int32_t dead_stage, double* out, void* workspace, void* stream) {
+  if (n < 0 || n_groups < 1 || n_groups > GJ_MAX_GROUPS) return GJ_E_RANGE;
+  if (!out || !workspace) return GJ_E_NULL;
+  if (n == 0) return GJ_OK;
+  if (!group || !is_infected || !current_stage) return GJ_E_NULL;
+  gj::GroupArgs S;
+  S.n = n;
+  S.group = group;
+  S.inf = is_infected;
+  S.stage = current_stage;
+  S.n_groups = n_groups;
+  S.dead = dead_stage;
+  S.vec4 = (((uintptr_t)group | (uintptr_t)is_infected | (uintptr_t)current_stage) % 16 == 0) ? 1 : 0;
+  S.ws = (gj::fx_t*)workspace;
+  const int64_t units = S.vec4 ? (n >> 2) + 1 : n;
+  if (n_groups <= gj::kGroupLdsMax) {       // regimes (i) and (iii): a histogram in LDS per workgroup
+    int64_t blocks = (units + gj::kGroupLdsThreads - 1) / gj::kGroupLdsThreads;
+    if (blocks > gj::kGroupLdsBlocks) blocks = gj::kGroupLdsBlocks;
+    hipLaunchKernelGGL(gj::k_group_stats<true>, dim3((unsigned)blocks), dim3(gj::kGroupLdsThreads),
+                       (size_t)n_groups * 2 * sizeof(gj::fx_t), (hipStream_t)stream, S);
+  } else {                                  // regime (ii): one global atomic per run of equal labels in a wave
+    int64_t blocks = (units + gj::kThreads - 1) / gj::kThreads;
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(gj::k_group_stats<false>, dim3((unsigned)blocks), dim3(gj::kThreads), 0, (hipStream_t)stream, S);
+  }
+  int rc = gj::launch_status();
+  if (rc) return rc;
+  hipLaunchKernelGGL(gj::k_group_finish, dim3((unsigned)((2 * (int64_t)n_groups + gj::kThreads - 1) / gj::kThreads)),
+                     dim3(gj::kThreads), 0, (hipStream_t)stream, n_groups, S.ws, out);
+  return gj::launch_status();
+}
+
+int gj_adjoint_group_stats(int64_t n, const int32_t* group, int32_t n_groups, const float* current_stage,
+                           int32_t dead_stage, const float* g_cases, const float* g_deaths, float* grad_is_infected,
+                           float* grad_stage, void* stream) {
+  if (n < 0 || n_groups < 1 || n_groups > GJ_MAX_GROUPS) return GJ_E_RANGE;
+  if (grad_stage && dead_stage == 0) return GJ_E_RANGE;      // (stage == dead) * stage / dead
+  if (n == 0 || (!grad_is_infected && !grad_stage)) return GJ_OK;
+  if (!group || (grad_stage && !current_stage)) return GJ_E_NULL;
+  gj::GroupAdjArgs S;
+  S.n = n;
+  S.group = group;
+  S.stage = current_stage;
+  S.g_cases = g_cases;
+  S.g_deaths = g_deaths;
+  S.grad_inf = grad_is_infected;
+  S.grad_stage = grad_stage;
+  S.n_groups = n_groups;
+  S.dead = dead_stage;
+  const uintptr_t bits = (uintptr_t)group | (uintptr_t)grad_is_infected | (uintptr_t)grad_stage |
+                         (grad_stage ? (uintptr_t)current_stage : 0);
+  S.vec4 = (bits % 16 == 0) ? 1 : 0;
+  int64_t blocks = ((S.vec4 ? (n >> 2) + 3 : n) + gj::kThreads - 1) / gj::kThreads;
+  if (blocks > 2048) blocks = 2048;
+  if (blocks < 1) blocks = 1;
+  if (n_groups <= gj::kGroupAdjLdsMax)
+    hipLaunchKernelGGL(gj::k_adjoint_group_stats<true>, dim3((unsigned)blocks), dim3(gj::kThreads),
+                       (size_t)n_groups * 2 * sizeof(float), (hipStream_t)stream, S);
+  else
+    hipLaunchKernelGGL(gj::k_adjoint_group_stats<false>, dim3((unsigned)blocks), dim3(gj::kThreads), 0,
+                       (hipStream_t)stream, S);
   return gj::launch_status();
 }
 

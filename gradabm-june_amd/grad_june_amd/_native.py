@@ -17,6 +17,8 @@ GJ_MAX_NETS_PER_SET = 8
 GJ_TABLE_SIZE = 400
 GJ_ADJ_BETA_BLOCKS = 256
 GJ_STREAM_EDGES = 2048
+GJ_MAX_GROUPS = 1 << 28
+GJ_GROUP_ERR_LABEL, GJ_GROUP_ERR_VALUE = 1, 2
 
 MASK_RAW, MASK_Q, MASK_QL, MASK_QL_AGE75 = 0, 1, 2, 3
 
@@ -219,6 +221,8 @@ SYMBOLS = {
         [C.c_int64, _vp, _vp, _vp, _vp, _vp, C.POINTER(SymptomsParams)] + [_vp] * 10,
     ),
     "gj_step_stats": (C.c_int, [C.c_int64, _vp, _vp, _vp, C.c_int32, C.POINTER(C.c_int32), C.c_int32, _vp, _vp]),
+    "gj_group_stats": (C.c_int, [C.c_int64, _vp, C.c_int32, _vp, _vp, C.c_int32, _vp, _vp, _vp]),
+    "gj_adjoint_group_stats": (C.c_int, [C.c_int64, _vp, C.c_int32, _vp, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
     "gj_step": (C.c_int, [C.POINTER(Plan), C.POINTER(AgentState), C.POINTER(StepParams), C.POINTER(StepIO), _vp]),
     "gj_step_phase": (
         C.c_int,

@@ -518,3 +518,40 @@ class SymptomsStep(torch.autograd.Function):
                                              N.ptr(g_nxt_in), N.ptr(g_ttn_in), N.ptr(g_new), N.current_stream()),
                 "gj_adjoint_symptoms")
         return None, g_new, g_cur_in, g_nxt_in, g_ttn_in
+
+
+class GroupSeriesRow(torch.autograd.Function):
+    """One row of the per-group result series as an autograd node: (is_infected, current_stage) -> (cases [G],
+    deaths [G]), the float32 values of the fp64 sums ``sum_{group[a] == g} is_infected[a]`` and
+    ``sum (stage == dead) * stage / dead`` (runner.py:198-215, 235-242 of the reference, for every group at once).
+    ``env``: ``{"stats": groups.GroupStats, "dead": id of the dead stage}``.  Forward = ``gj_group_stats`` on a zeroed
+    row; backward = ``gj_adjoint_group_stats``, a gather through the labels that writes only the gradients autograd
+    asks for."""
+
+    @staticmethod
+    def forward(ctx, env, is_infected, current_stage):
+        stats, dead = env["stats"], int(env["dead"])
+        dev = stats.labels.device
+        inf = is_infected.detach().to(device=dev, dtype=torch.float32).contiguous()
+        stage = current_stage.detach().to(device=dev, dtype=torch.float32).contiguous()
+        row = torch.zeros(2 * stats.n_groups, dtype=torch.float64, device=dev)
+        stats.add(inf, stage, dead, row)
+        ctx.stats, ctx.dead = stats, dead
+        ctx.devices = (is_infected.device, current_stage.device)
+        ctx.save_for_backward(stage)
+        row = row.to(torch.float32)
+        return row[: stats.n_groups].clone(), row[stats.n_groups:].clone()
+
+    @staticmethod
+    def backward(ctx, g_cases, g_deaths):
+        stats = ctx.stats
+        (stage,) = ctx.saved_tensors
+        dev = stats.labels.device
+
+        def f32(g):
+            return None if g is None else g.detach().to(device=dev, dtype=torch.float32).contiguous()
+
+        want_inf, want_stage = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        grad_inf, grad_stage = stats.gather(stage, ctx.dead, f32(g_cases), f32(g_deaths), want_inf, want_stage)
+        return (None, None if grad_inf is None else grad_inf.to(ctx.devices[0]),
+                None if grad_stage is None else grad_stage.to(ctx.devices[1]))

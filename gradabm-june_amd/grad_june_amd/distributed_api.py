@@ -214,9 +214,12 @@ class DistributedRunner(Runner):
 
         if not self.collectives or not dist.is_initialized() or dist.get_world_size(self.group) == 1:
             return
-        if dist.get_backend(self.group) == "gloo":                # tests: staged through the host
-            host = self._series[:n_rows].cpu()
-            dist.all_reduce(host, group=self.group)
-            self._series[:n_rows].copy_(host)
-        else:
-            dist.all_reduce(self._series[:n_rows], group=self.group)
+        # (the series by agent group too: the labels were encoded on the whole world before the partition cut it, so the
+        # columns are the same on every rank)
+        for series in [self._series, *getattr(self, "_group_series", {}).values()]:
+            if dist.get_backend(self.group) == "gloo":            # tests: staged through the host
+                host = series[:n_rows].cpu()
+                dist.all_reduce(host, group=self.group)
+                series[:n_rows].copy_(host)
+            else:
+                dist.all_reduce(series[:n_rows], group=self.group)

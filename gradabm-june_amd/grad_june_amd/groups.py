@@ -1,0 +1,144 @@
+"""Result series by agent group (area, super area, ethnicity, sex, any integer label).
+
+Host side: the label encoding (:func:`encode_groups`) and :class:`GroupStats`, the binding of ``gj_group_stats`` /
+``gj_adjoint_group_stats`` (include/gradjune_hip.h, "row f2 by agent group") for one labelling of the agents.  The
+reference has one such reduction, ``get_cases_by_ethnicity`` (grad_june/runner.py:235-242), which its time loop never
+calls; here the Runner records ``cases_by_<name>`` / ``deaths_by_<name>`` at every step when asked to.
+"""
+from __future__ import annotations
+
+import re
+from typing import Dict, List, Tuple
+
+import numpy as np
+import torch
+
+from . import _native as N
+
+#: result keys of Runner.forward() that a group name must not shadow
+_RESERVED = re.compile(r"age(_\d+)?")
+
+
+class GroupLabelError(RuntimeError):
+    """gj_group_stats met a label outside [0, n_groups) or a value it cannot sum (see the header)."""
+
+
+def check_group_name(name) -> str:
+    if not isinstance(name, str) or not re.fullmatch(r"[A-Za-z_][A-Za-z0-9_]*", name):
+        raise ValueError(f"group name {name!r}: expected an identifier-like string")
+    if _RESERVED.fullmatch(name):
+        raise ValueError(f"group name '{name}' collides with the result keys cases_by_age_XX; "
+                         "pass the age bins as a label dict under another name")
+    return name
+
+
+def _as_numpy(v) -> np.ndarray:
+    return v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+
+
+def encode_groups(agent, spec) -> Tuple[Dict[str, torch.Tensor], Dict[str, list]]:
+    """``spec``: a list of attribute names of ``agent`` (``data["agent"]``), or a dict ``name -> integer labels``
+    (one per agent, in the order of ``agent``), or a list mixing names and such dicts.
+
+    An attribute - strings or numbers - is encoded with ``np.unique(..., return_inverse=True)``: the columns are the
+    sorted distinct values of the WHOLE world it is called on.  Integer labels of a dict are used as they are: they must
+    lie in ``[0, G)`` with ``G = max + 1``, and a group without agents keeps its (zero) column.
+    Returns ``({name: int32 labels [n_agents]}, {name: list of column keys})``."""
+    n = len(agent["id"])
+    items: List[Tuple[str, object]] = []
+    if isinstance(spec, dict):
+        items = [(k, v) for k, v in spec.items()]
+    elif isinstance(spec, (list, tuple)):
+        for s in spec:
+            if isinstance(s, dict):
+                items.extend(s.items())
+            else:
+                items.append((s, None))
+    elif isinstance(spec, str):
+        items = [(spec, None)]
+    else:
+        raise TypeError(f"groups: expected a list of attribute names or a dict name -> labels, not {type(spec).__name__}")
+    labels, keys = {}, {}
+    for name, given in items:
+        check_group_name(name)
+        if name in labels:
+            raise ValueError(f"group '{name}' is given twice")
+        if given is None:
+            if name not in agent:
+                raise KeyError(f"groups: the world's agents have no attribute '{name}' "
+                               f"(present: {sorted(k for k in agent.keys())})")
+            values = _as_numpy(agent[name])
+            if values.ndim != 1 or values.shape[0] != n:
+                raise ValueError(f"group '{name}': attribute of shape {values.shape}, expected ({n},)")
+            uniq, inverse = np.unique(values, return_inverse=True)
+            lab, key = inverse.reshape(-1), uniq.tolist()
+        else:
+            lab = _as_numpy(given)
+            if lab.ndim != 1 or lab.shape[0] != n:
+                raise ValueError(f"group '{name}': {lab.shape} labels for {n} agents")
+            if lab.dtype.kind not in "iu":
+                raise TypeError(f"group '{name}': integer labels expected, not {lab.dtype}")
+            if n and (int(lab.min()) < 0 or int(lab.max()) >= N.GJ_MAX_GROUPS):
+                raise ValueError(f"group '{name}': labels must lie in [0, {N.GJ_MAX_GROUPS})")
+            key = list(range(int(lab.max()) + 1 if n else 1))
+        labels[name] = torch.from_numpy(np.ascontiguousarray(lab, dtype=np.int32))
+        keys[name] = key
+    return labels, keys
+
+
+def attach_groups(agent, spec) -> None:
+    """Encode ``spec`` on ``agent`` and keep the result on it: ``group_labels`` (a dict of per-agent tensors, so that
+    whatever renumbers or cuts the agents - graph.locality_order, the multi-GPU partition - carries the labels along)
+    and ``group_keys`` (lists: not per-agent data)."""
+    labels, keys = encode_groups(agent, spec)
+    old_l, old_k = dict(agent.get("group_labels", None) or {}), dict(agent.get("group_keys", None) or {})
+    old_l.update(labels)
+    old_k.update(keys)
+    agent.group_labels, agent.group_keys = old_l, old_k
+
+
+class GroupStats:
+    """One labelling on the device: labels, group count and the workspace of ``gj_group_stats``."""
+
+    def __init__(self, labels: torch.Tensor, n_groups: int, device=None):
+        if n_groups < 1 or n_groups > N.GJ_MAX_GROUPS:
+            raise ValueError(f"n_groups = {n_groups}: expected 1 .. {N.GJ_MAX_GROUPS}")
+        dev = torch.device(device) if device is not None else labels.device
+        self.labels = labels.detach().to(device=dev, dtype=torch.int32).contiguous()
+        self.n_groups = int(n_groups)
+        self.n = self.labels.numel()
+        # GJ_GROUP_WORKSPACE_BYTES: 2 G sums of 8 bytes, then the error word
+        self.workspace = torch.zeros(2 * self.n_groups + 1, dtype=torch.int64, device=dev)
+
+    def add(self, is_infected: torch.Tensor, current_stage: torch.Tensor, dead: int, out: torch.Tensor) -> None:
+        """out[0:G] += cases by group, out[G:2G] += deaths by group (fp64, device)."""
+        if is_infected.numel() != self.n or current_stage.numel() != self.n:
+            raise ValueError(f"{is_infected.numel()} / {current_stage.numel()} values for {self.n} labels")
+        if out.dtype != torch.float64 or out.numel() != 2 * self.n_groups or not out.is_contiguous():
+            raise ValueError("out: a contiguous float64 tensor of 2 * n_groups elements")
+        N.check(N.load().gj_group_stats(self.n, N.ptr(self.labels), self.n_groups, N.ptr(is_infected),
+                                        N.ptr(current_stage), int(dead), N.ptr(out), N.ptr(self.workspace),
+                                        N.current_stream()), "gj_group_stats")
+
+    def gather(self, current_stage, dead: int, g_cases, g_deaths, want_inf: bool = True, want_stage: bool = True):
+        """The adjoint: (grad_is_infected or None, grad_stage or None)."""
+        dev = self.labels.device
+        grad_inf = torch.empty(self.n, dtype=torch.float32, device=dev) if want_inf else None
+        grad_stage = torch.empty(self.n, dtype=torch.float32, device=dev) if want_stage else None
+        N.check(N.load().gj_adjoint_group_stats(self.n, N.ptr(self.labels), self.n_groups, N.ptr(current_stage),
+                                                int(dead), N.ptr(g_cases), N.ptr(g_deaths), N.ptr(grad_inf),
+                                                N.ptr(grad_stage), N.current_stream()), "gj_adjoint_group_stats")
+        return grad_inf, grad_stage
+
+    def check(self, what: str = "gj_group_stats") -> None:
+        """Raise if a launch since the last check met a bad label or value (one device read)."""
+        word = self.workspace[2 * self.n_groups:]
+        err = int(word.item()) & 0xFFFFFFFF
+        if err:
+            word.zero_()
+            why = []
+            if err & N.GJ_GROUP_ERR_LABEL:
+                why.append(f"a label outside [0, {self.n_groups}) (its agent was skipped)")
+            if err & N.GJ_GROUP_ERR_VALUE:
+                why.append("an is_infected that is not finite or beyond 2^18 (it was counted as 0)")
+            raise GroupLabelError(f"{what}: " + " and ".join(why))

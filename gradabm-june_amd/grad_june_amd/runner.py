@@ -50,7 +50,7 @@ def world_from_npz(path) -> HeteroData:
 
 class Runner(torch.nn.Module):
     def __init__(self, model, data, timer, log_fraction_initial_cases, save_path, parameters,
-                 age_bins=(0, 18, 65, 100)):
+                 age_bins=(0, 18, 65, 100), groups=None):
         super().__init__()
         self.model = model
         self.data = data
@@ -65,6 +65,14 @@ class Runner(torch.nn.Module):
         self.population_by_age = self.get_people_by_age()
         self.save_path = Path(save_path)
         self.input_parameters = parameters
+        # result series by agent group (not in the reference): ``groups`` = attribute names of data["agent"] or a dict
+        # name -> integer labels in the order of data["agent"]; the YAML key ``groups_to_save`` is encoded by get_data
+        if groups is not None:
+            from .groups import attach_groups
+
+            attach_groups(data["agent"], groups)
+        self.group_keys = {k: np.asarray(v) for k, v in (data["agent"].get("group_keys", None) or {}).items()}
+        self._group_stats = None
         self.restore_initial_data()
 
     @classmethod
@@ -96,6 +104,12 @@ class Runner(torch.nn.Module):
         # optional (not a reference key): ``system.locality_order: household`` renumbers the agents venue-major
         # at load time (graph.locality_order); the per-agent result of ``runner()`` is reported in the
         # file's original order
+        # optional (not a reference key): ``groups_to_save: [area, ethnicity]`` asks for result series by agent group
+        # (groups.py).  Encoded on the whole world in the file's order, before anything renumbers or cuts the agents
+        if params.get("groups_to_save"):
+            from .groups import attach_groups
+
+            attach_groups(data["agent"], params["groups_to_save"])
         by = params["system"].get("locality_order")
         if by:
             from .graph import locality_order
@@ -171,6 +185,33 @@ class Runner(torch.nn.Module):
                                        len(self.age_bins) - 1, edges, dead, N.ptr(self._series[row]),
                                        N.current_stream()), "gj_step_stats")
 
+    # per-step result reductions by agent group: one gj_group_stats pass per labelling ----------------------------
+    def _groups(self):
+        """{name: groups.GroupStats} of the labellings asked for (empty: nothing is recorded, nothing is launched)."""
+        if self._group_stats is None:
+            from .groups import GroupStats
+
+            labels = self.data["agent"].get("group_labels", None) or {}
+            dev = require_hip(self.device) if labels else None
+            self._group_stats = {name: GroupStats(labels[name], len(self.group_keys[name]), device=dev)
+                                 for name in self.group_keys}
+        return self._group_stats
+
+    def _record_groups(self, data, row, diff_rows=None):
+        ag = data["agent"]
+        dead = int(self.model.symptoms_updater.stages_ids[-1])
+        stage, inf = ag.symptoms["current_stage"], ag.is_infected
+        if diff_rows is not None:                 # differentiable run: the rows stay on the autograd graph
+            from .autograd import GroupSeriesRow
+
+            for name, stats in self._groups().items():
+                diff_rows[name].append(torch.cat(GroupSeriesRow.apply({"stats": stats, "dead": dead}, inf, stage)))
+            return
+        stage = stage.detach().to(torch.float32).contiguous()
+        inf = inf.detach().to(torch.float32).contiguous()
+        for name, stats in self._groups().items():
+            stats.add(inf, stage, dead, self._group_series[name][row])
+
     # time loop --------------------------------------------------------------------------------------
     def forward(self):
         timer, model, data = self.timer, self.model, self.data
@@ -194,10 +235,16 @@ class Runner(torch.nn.Module):
             isinstance(n.log_beta, torch.Tensor) and n.log_beta.requires_grad
             for n in model.infection_networks.networks.values()) or profile_requires_grad(data))
         diff_rows = []
+        groups = self._groups()
+        self._group_series = {name: torch.zeros(n_rows, 2 * st.n_groups, dtype=torch.float64,
+                                                device=require_hip(self.device)) for name, st in groups.items()}
+        group_diff_rows = {name: [] for name in groups} if differentiable else None
 
         def record(row, done=False):
             if not done:
                 self._record(data, row)
+            if groups:
+                self._record_groups(data, row, group_diff_rows)
             if differentiable:
                 ag = data["agent"]
                 stage = ag.symptoms["current_stage"]
@@ -238,6 +285,16 @@ class Runner(torch.nn.Module):
         }
         for i, key in enumerate(self.age_bins[1:]):
             results[f"cases_by_age_{int(key):02d}"] = series[:, 1 + i]
+        for name, st in groups.items():
+            st.check(f"result series by {name}")
+            by_group = self._group_series[name][: row + 1].to(torch.float32)
+            if differentiable:
+                by_group = self._reduce_differentiable(torch.stack(group_diff_rows[name]).to(torch.float32))
+            G = st.n_groups
+            results[f"cases_by_{name}"] = by_group[:, :G]
+            results[f"daily_cases_by_{name}"] = torch.diff(by_group[:, :G], dim=0,
+                                                           prepend=torch.zeros(1, G, device=by_group.device))
+            results[f"deaths_by_{name}"] = by_group[:, G:]
         is_infected = data["agent"].is_infected
         if "original_index" in data["agent"]:
             out = torch.empty_like(is_infected)
@@ -259,9 +316,15 @@ class Runner(torch.nn.Module):
         df = pd.DataFrame(index=results["dates"])
         df.index.name = "date"
         for key, series in results.items():
-            if key != "dates":
+            if key != "dates" and series.dim() == 1:
                 df[key] = series.detach().cpu().numpy()
         df.to_csv(self.save_path / "results.csv")
+        for name, keys in self.group_keys.items():      # [T, G] series: long format, one file per labelling
+            cols = {c: results[f"{c}_by_{name}"].detach().cpu().numpy().reshape(-1)
+                    for c in ("cases", "daily_cases", "deaths")}
+            pd.DataFrame({"date": np.repeat(np.asarray(results["dates"], dtype=object), len(keys)),
+                          name: np.tile(keys, len(results["dates"])), **cols}).to_csv(
+                self.save_path / f"results_by_{name}.csv", index=False)
         pd.DataFrame({"is_infected": is_infected.detach().cpu().numpy()}).to_csv(
             self.save_path / "results_is_infected.csv")
 

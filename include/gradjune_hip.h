@@ -391,6 +391,45 @@ int gj_symptoms_step_stats(int64_t n, const uint8_t* agent_class, const float* n
                            const float* is_infected, int32_t n_bins, const int32_t* bin_edges /* host [n_bins+1] */,
                            int32_t dead_stage, double* out, void* stream);
 
+/* ---- row f2 by agent group: result series per area / super area / ethnicity / any integer label ------------------
+ * restates, for every label at once, the masked sums of get_cases_by_ethnicity (grad_june/runner.py:235-242: one
+ * [n] mask per group) and the deaths form of store_differentiable_deaths (runner.py:198-215) per group:
+ *   out[g]            += sum over agents a with group[a] == g of is_infected[a]
+ *   out[n_groups + g] += number of those agents with current_stage[a] == dead_stage
+ * group: device int32 [n], labels in [0, n_groups).  out: device double [2 * n_groups]; the call ADDS to it, like
+ * gj_step_stats.  workspace: device, GJ_GROUP_WORKSPACE_BYTES(n_groups) bytes, 8-byte aligned, ZEROED by the caller
+ * before its first use; a call leaves the sums in it zero again, so it can be reused without clearing.
+ * Order independence: is_infected is summed as a 64-bit integer in 32.32 fixed point (deaths as a count) and
+ * converted to double once, so two launches - or any permutation of the agents together with their labels - give
+ * the same bits.  A value is rounded to the nearest multiple of 2^-32 (exact for the model's 0 / 1 / 2); a group's
+ * sum must stay below 2^31.  What cannot be summed that way never reaches another group: an agent whose label is
+ * outside [0, n_groups) is skipped altogether (the label is never used as an index) and sets GJ_GROUP_ERR_LABEL in
+ * the error word; an is_infected that is not finite or beyond +-2^18 adds 0 to its group and sets
+ * GJ_GROUP_ERR_VALUE.  The error word is the uint32 at byte 16 * n_groups of the workspace; it is sticky until the
+ * caller clears it, and the caller reads it when it wants to know (the Python binding raises).
+ * Three regimes, chosen from n_groups:  (i) n_groups <= 4096: every workgroup keeps the 2 * n_groups accumulators
+ * in LDS (at most 64 KiB, two workgroups per CU) and adds the non-zero ones to the workspace when it is done, one
+ * 64-bit atomic each;  (ii) above that, the lanes of a wave fold their runs of equal labels and one lane issues one
+ * global 64-bit atomic per run: labels that follow the geography cost one atomic per wave and boundary, shuffled
+ * labels one per agent;  (iii) n_groups == 1 is regime (i) with a single run that is never closed before the end:
+ * the national sums of gj_step_stats.  In every regime a workgroup reads a contiguous share of the agents.         */
+#define GJ_MAX_GROUPS (1 << 28)
+#define GJ_GROUP_WORKSPACE_BYTES(n_groups) (16 * (int64_t)(n_groups) + 8)
+#define GJ_GROUP_ERR_LABEL 1u
+#define GJ_GROUP_ERR_VALUE 2u
+int gj_group_stats(int64_t n, const int32_t* group, int32_t n_groups, const float* is_infected,
+                   const float* current_stage, int32_t dead_stage, double* out, void* workspace, void* stream);
+
+/* adjoint of gj_group_stats (what autograd gives for the reference's forms above): the gather
+ *   grad_is_infected[a] = g_cases[group[a]]
+ *   grad_stage[a]       = g_deaths[group[a]] / dead_stage * (current_stage[a] == dead_stage)
+ * g_cases / g_deaths: device fp32 [n_groups], NULL = zeros.  grad_is_infected / grad_stage: device fp32 [n], each
+ * may be NULL: a NULL output is neither computed nor written (current_stage is read for grad_stage only).  An agent
+ * whose label is outside [0, n_groups) gets 0.  Up to 2048 groups the two rows are staged in LDS once per workgroup. */
+int gj_adjoint_group_stats(int64_t n, const int32_t* group, int32_t n_groups, const float* current_stage,
+                           int32_t dead_stage, const float* g_cases, const float* g_deaths, float* grad_is_infected,
+                           float* grad_stage, void* stream);
+
 /* ---- row f3: adjoint (backward) of one hot-path step, forward-only kernels reused ---------------
  * The aggregation ts = susc * sum_n w_n * (M_n^T diag(beta_n p_contact) M_n)(m_n * transmission) is
  * self-adjoint up to the exchange of the masks m_n <-> w_n, so its backward is the same four tiled
