@@ -84,10 +84,13 @@ def network_specs(world, tables: Optional[dict] = None):
     return specs
 
 
-def make_engine(world, tables, device, layout="csr", split_epilogue=False, direct_table_floats=0, **plan_kw):
+def make_engine(world, tables, device, layout="csr", split_epilogue=False, direct_table_floats=0, device_compile=False,
+                **plan_kw):
     from grad_june_amd.engine import InfectionEngine
     from grad_june_amd.plan import DevicePlan, compile_plan
 
+    if device_compile:           # the tiled arrays built by the library's compile kernels instead of numpy
+        plan_kw["device"] = device
     es = {k: {kk: vv.numpy() for kk, vv in v.items()} for k, v in world["edge_sets"].items()}
     host = compile_plan(world["n_agents"], es, age=world["age"].numpy(), sex=world["sex"].numpy(), layout=layout,
                         **plan_kw)
@@ -100,3 +103,128 @@ def device_state(state: Dict[str, torch.Tensor], device):
     d = {k: v.to(torch.float32).to(device).contiguous() for k, v in state.items()}
     d["transmission"] = torch.zeros_like(d["is_infected"])
     return d
+
+
+# ---- the sparse passes restated in float64 from the edge lists (forward and transposed) ------------------------------
+U32 = 2.0 ** -24          # unit roundoff of float32 (round to nearest)
+FX_VENUE_HALF = 2.0 ** -37    # half a unit of the per-venue fixed point (2^-36, csrc/gj_tiled.h)
+FX_AGENT_HALF = 2.0 ** -33    # half a unit of the per-agent fixed point (2^-32)
+SLACK = 1.0 + 2.0 ** -20      # the second-order terms (products of two roundings) of the first-order bounds below
+
+
+def edge_set_name(network: str) -> str:
+    return "leisure" if network in LEISURE or network == "care_visit" else network
+
+
+def network_weights(name, world, tables, day_type, qmask):
+    """(transmitting-side, receiving-side) per-agent weights of one network in float64, as
+    ``oracle/gj_oracle.py:infection_network`` applies them in the forward: household 1 / 1; school ... care_home q / q;
+    leisure q * table / q * table; care_visit q * table / q * table * (age > 75)."""
+    A = world["n_agents"]
+    q = np.ones(A) if qmask is None else np.asarray(qmask, dtype=np.float64)
+    if name == "household":
+        one = np.ones(A)
+        return one, one
+    if name in LEISURE or name == "care_visit":
+        age, sex = world["age"].numpy(), world["sex"].numpy()
+        lp = tables[name].numpy()[day_type, sex, age].astype(np.float64)
+        m = q * lp
+        return m, (m * (age > 75) if name == "care_visit" else m)
+    return q, q
+
+
+def sparse_passes_fp64(world, active, betas, tables, day_type, qmask, x, transpose=True, pc_float32=True):
+    """The two sparse passes of a step on the per-agent vector ``x`` (signed, any magnitude), in float64 numpy straight
+    from the edge lists.  With w1 / w2 the transmitting / receiving-side weights of ``network_weights`` (EXCHANGED when
+    ``transpose``: the backward of the aggregation w.r.t. the transmissions is the same operator with the two exchanged):
+
+        cum_n[v] = float32(beta_n) * p_contact[v] * sum_{edges (a, v)} w1_n[a] * x[a]
+        out[a]   = sum_n w2_n[a] * sum_{edges (a, v)} cum_n[v]
+
+    Returns a dict: ``cum[n]`` [V], ``out`` [A] and - per element, for the error bounds - the number of terms of each
+    sum (``cum_terms[n]``, ``out_terms``), the sum of their absolute values (``cum_abs[n]``: of w1 * x, i.e. BEFORE
+    beta * p_contact; ``out_abs``: of w2 * cum), ``bp[n]`` = beta_n * p_contact and ``out_sets`` = the number of edge
+    sets that contribute to an agent.  ``pc_float32=False`` keeps p_contact in float64 (the oracle's flow when ``people``
+    is a float64 tensor)."""
+    A = world["n_agents"]
+    x = np.asarray(x, dtype=np.float64)
+    res = {"cum": {}, "cum_terms": {}, "cum_abs": {}, "bp": {}, "w2": {}, "out": np.zeros(A), "out_terms": np.zeros(A),
+           "out_abs": np.zeros(A), "out_sets": np.zeros(A)}
+    seen_sets = set()
+    for name in active:
+        es_name = edge_set_name(name)
+        es = world["edge_sets"][es_name]
+        a, v = es["agent"].numpy(), es["venue"].numpy()
+        people = es["people"].numpy().astype(np.float64)
+        V = len(people)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            pc = np.clip(1.0 / (people - 1.0), 0.0, 1.0)
+        if pc_float32:                                         # the plan keeps p_contact in float32
+            pc = pc.astype(np.float32).astype(np.float64)
+        wt, wr = network_weights(name, world, tables, day_type, qmask)
+        w1, w2 = (wr, wt) if transpose else (wt, wr)
+        term = (w1 * x)[a]
+        bp = float(np.float32(betas[name])) * pc
+        s = np.bincount(v, weights=term, minlength=V)
+        cum = bp * s
+        res["cum"][name], res["bp"][name], res["w2"][name] = cum, bp, w2
+        res["cum_terms"][name] = np.bincount(v, minlength=V).astype(np.float64)
+        res["cum_abs"][name] = np.bincount(v, weights=np.abs(term), minlength=V)
+        t2 = w2[a] * cum[v]
+        res["out"] += np.bincount(a, weights=t2, minlength=A)
+        res["out_abs"] += np.bincount(a, weights=np.abs(t2), minlength=A)
+        res["out_terms"] += np.bincount(a, minlength=A)
+        if es_name not in seen_sets:
+            seen_sets.add(es_name)
+            res["out_sets"] += np.bincount(a, minlength=A) > 0
+    return res
+
+
+def sparse_pass_bounds(world, active, ref, scale=1.0):
+    """Per-element bounds on |device - float64 restatement| for the tiled passes, from the number formats alone
+    (csrc/gj_tiled.h: "64-bit fixed point", lines 41-50).  u = 2^-24 is float32's unit roundoff.
+
+    Pass 1, ``cum_n[v]`` - the kernel forms every term w1 * x as ONE float32 product (error <= u |term|), converts it to
+    fixed point with 2^-36 resolution (round to nearest: <= 2^-37 per term), adds the integers exactly, converts the sum
+    to float32 (u |sum|) and multiplies by float32(beta * p_contact) (one rounding for that product, one for the
+    result); p_contact itself is the float32 value of a float64 quotient here and of a float32 division on the host (a
+    fourth u).  First order, with T = number of terms and S_abs = sum |term|:
+
+        E1[v] = bp[v] * (u * S_abs + T * 2^-37) + 4 u |cum[v]|
+
+    Pass 2, ``out[a]`` - every term w2 * cum_dev[v] carries pass 1's error (|w2| E1[v], summed over the agent's terms)
+    and one float32 rounding (u |term|).  The terms of one edge are added over the set's networks in float32, and in the
+    direct and run forms the edges, planes and sets of an agent are added in float32 registers too: every one of at most
+    T + sets + 1 additions rounds a partial sum that is <= S_abs in magnitude (u S_abs each).  The workspace form
+    converts each edge's value to fixed point with 2^-32 resolution instead (<= 2^-33 per term; integer adds are exact).
+    The result is rounded to float32 once more (u |out|); the quarantine factor (0 or 1) and the susceptibility of 1 are
+    exact:
+
+        E2[a] = sum |w2| E1[v]  +  u S_abs  +  (T + sets + 1) u S_abs  +  T * 2^-33  +  u |out[a]|
+
+    Both are multiplied by 1 + 2^-20 for the second-order terms.  ``ref`` is the restatement of the vector the kernels
+    saw; ``scale``: they saw x / scale (a power of two: exact) and the results were multiplied by it afterwards - the
+    bounds are then ``scale`` times those of the scaled problem (the fixed-point terms are absolute in ITS units).
+    Returns ``({network: E1}, E2)`` in the units of ``scale * ref``."""
+    A = world["n_agents"]
+    e1, carried = {}, np.zeros(A)
+    for n in active:
+        cum = ref["cum"][n]
+        e1[n] = SLACK * (ref["bp"][n] * (U32 * ref["cum_abs"][n] + ref["cum_terms"][n] * FX_VENUE_HALF)
+                         + 4 * U32 * np.abs(cum))
+        es = world["edge_sets"][edge_set_name(n)]
+        a, v = es["agent"].numpy(), es["venue"].numpy()
+        carried += np.bincount(a, weights=np.abs(ref["w2"][n])[a] * e1[n][v], minlength=A)
+    e2 = SLACK * (carried + (ref["out_terms"] + ref["out_sets"] + 2) * U32 * ref["out_abs"]
+                  + ref["out_terms"] * FX_AGENT_HALF + U32 * np.abs(ref["out"]))
+    return {n: scale * e for n, e in e1.items()}, scale * e2
+
+
+def sparse_passes_with_bounds(world, active, betas, tables, day_type, qmask, x, transpose=True, scale=1.0):
+    """``sparse_passes_fp64`` of x / scale with the bounds of ``sparse_pass_bounds``: ``cum[n]``, ``out`` (multiplied
+    back by ``scale``), ``cum_bound[n]``, ``out_bound`` (same units) and ``bp[n]`` = beta_n * p_contact."""
+    ref = sparse_passes_fp64(world, active, betas, tables, day_type, qmask, np.asarray(x, dtype=np.float64) / scale,
+                             transpose)
+    e1, e2 = sparse_pass_bounds(world, active, ref, scale)
+    return {"cum": {n: scale * c for n, c in ref["cum"].items()}, "out": scale * ref["out"], "cum_bound": e1,
+            "out_bound": e2, "bp": ref["bp"]}
