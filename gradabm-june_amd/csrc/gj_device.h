@@ -86,14 +86,27 @@ __device__ __forceinline__ float infection_uniform(uint64_t seed, uint64_t step,
 }
 __device__ __forceinline__ float own_new_infected(float p, float theta) { return (p < theta) ? 1.0f : 0.0f; }
 // (e0, e1) with e0 / (e0 + e1) == theta up to rounding: what k_adjoint_sample feeds the softmax derivative
-__device__ __forceinline__ void exp_pair(uint64_t seed, uint64_t step, int64_t agent, float& e0, float& e1) {
-  const float theta = infection_uniform(seed, step, agent);
+__device__ __forceinline__ void exp_pair_parts(uint64_t seed, uint64_t step, int64_t agent, float& theta, float& s) {
+  theta = infection_uniform(seed, step, agent);
   uint32_t r[4];
   philox4x32_10((uint64_t)agent >> 1, step | (1ull << 62), seed, r);
   const float u1 = u01((agent & 1) ? r[2] : r[0]), u2 = u01((agent & 1) ? r[3] : r[1]);
-  const float s = -logf(u1) - logf(u2);
+  s = -logf(u1) - logf(u2);
+}
+__device__ __forceinline__ void exp_pair(uint64_t seed, uint64_t step, int64_t agent, float& e0, float& e1) {
+  float theta, s;
+  exp_pair_parts(seed, step, agent, theta, s);
   e0 = theta * s;
   e1 = (1.0f - theta) * s;
+}
+// The same pair with the two products formed in fp64, where they are exact (24 x 24 bits; 1 - theta is exact in fp32):
+// e0 / e1 == theta / (1 - theta) to fp64 rounding, so the softmax terms - which see the draws through log e0 - log e1
+// only - do not depend on the last bit of logf in s.
+__device__ __forceinline__ void exp_pair(uint64_t seed, uint64_t step, int64_t agent, double& e0, double& e1) {
+  float theta, s;
+  exp_pair_parts(seed, step, agent, theta, s);
+  e0 = (double)theta * (double)s;
+  e1 = (double)(1.0f - theta) * (double)s;
 }
 
 // a8: IsInfectedSampler.forward = F.gumbel_softmax(vstack(p, 1-p).log(), tau=0.1, hard=True, dim=0)
@@ -120,6 +133,71 @@ __device__ __forceinline__ void infect(float nw, float now, float& susc, float& 
   susc = fmaxf(0.0f, susc - nw);
   inf = inf + nw;
   t_inf = t_inf + nw * (now - t_inf);
+}
+
+// Adjoint of a8 + a9 for one agent, shared by k_adjoint_sample (a hot-path step, T = float) and k_adjoint_seed_agents
+// (the seed, T = double): four pieces.
+//  sampler_draws:    agent a's columns of `noise` ([2, n]) or, without it, exp_pair(seed, step, agent_offset + a)
+//  sampler_decision: the decision nu the FORWARD took - in its arithmetic (fp32), by its rule: the argmax of the
+//                    tau = 0.1 softmax for injected draws, p < theta for the library's own
+//  sampler_softmax:  y0, y1 of the straight-through sampler's forward, in T
+//  sample_adjoint:   given p (the probability of NOT being infected), the pre-state, y0, y1, nu and the gradients w.r.t.
+//                    the outputs: h, the subgradient of max(0, susceptibility - nu) (a tie splits the gradient),
+//                    nu_bar = d loss / d new_infected = g_inf + g_time * (now - time0) - g_susc * h + g_new
+//                    and the straight-through derivative d nu / d p of the softmax
+__device__ __forceinline__ float gj_log(float x) { return logf(x); }
+__device__ __forceinline__ double gj_log(double x) { return log(x); }
+__device__ __forceinline__ float gj_exp(float x) { return expf(x); }
+__device__ __forceinline__ double gj_exp(double x) { return exp(x); }
+__device__ __forceinline__ float gj_max(float a, float b) { return fmaxf(a, b); }
+__device__ __forceinline__ double gj_max(double a, double b) { return fmax(a, b); }
+__device__ __forceinline__ float gj_abs(float x) { return fabsf(x); }
+__device__ __forceinline__ double gj_abs(double x) { return fabs(x); }
+
+template <typename T>
+__device__ __forceinline__ void sampler_draws(const float* __restrict__ noise, int64_t n, int64_t a, uint64_t seed,
+                                              uint64_t step, int64_t agent_offset, T& e0, T& e1) {
+  if (noise) {
+    e0 = noise[a];
+    e1 = noise[n + a];
+  } else {
+    exp_pair(seed, step, agent_offset + a, e0, e1);
+  }
+}
+
+// y0, y1 of the straight-through sampler's forward (same op sequence as gumbel_new_infected)
+template <typename T>
+__device__ __forceinline__ void sampler_softmax(T p, T e0, T e1, T& y0, T& y1) {
+  const T tau = (T)0.1;
+  const T z0 = (gj_log(p) + (-gj_log(e0))) / tau;
+  const T z1 = (gj_log((T)1 - p) + (-gj_log(e1))) / tau;
+  const T m = gj_max(z0, z1);
+  const T x0 = gj_exp(z0 - m), x1 = gj_exp(z1 - m);
+  y0 = x0 / (x0 + x1);
+  y1 = x1 / (x0 + x1);
+}
+
+// (y0, y1: the FLOAT softmax terms; read for injected draws only)
+__device__ __forceinline__ float sampler_decision(float p, bool injected, float y0, float y1, uint64_t seed,
+                                                  uint64_t step, int64_t agent) {
+  return injected ? ((y1 > y0) ? 1.0f : 0.0f)                                          // the forward's rule
+                  : own_new_infected(p, infection_uniform(seed, step, agent));
+}
+
+template <typename T>
+struct SampleAdjoint {
+  T h, nu_bar, dnu_dp;
+};
+template <typename T>
+__device__ __forceinline__ SampleAdjoint<T> sample_adjoint(T p, T s0, T t0, T y0, T y1, T nu, T now, T gs, T gi, T gt,
+                                                           T gn) {
+  SampleAdjoint<T> r;
+  const T x = s0 - nu;                                       // torch.maximum(0, x): tie splits the gradient
+  r.h = (x > (T)0) ? (T)1 : ((x == (T)0) ? (T)0.5 : (T)0);
+  r.nu_bar = gi + gt * (now - t0) - gs * r.h + gn;
+  r.dnu_dp = -(y0 * y1 / (T)0.1) * ((T)1 / p + (T)1 / ((T)1 - p));
+  if (!(gj_abs(r.dnu_dp) < (T)3.0e38f)) r.dnu_dp = (T)0;     // p == 0 or 1: y0*y1 == 0 there
+  return r;
 }
 
 // a7 (reference base.py:136-140): p = clamp(exp(-clamp(ts, 1e-6, 100) * dt), 0, 1).  torch.clamp passes a NaN

@@ -614,32 +614,127 @@ __global__ __launch_bounds__(kThreads) void k_adjoint_sample(
   const float ts = s0 * ac;
   const bool inside = (ts >= 1e-6f) && (ts <= 100.0f);
   const float p = not_infected_prob(ts, dt);
-  float e0, e1;
-  if (noise) {
-    e0 = noise[a];
-    e1 = noise[n + a];
-  } else {
-    exp_pair(seed, step, agent_offset + a, e0, e1);
-  }
-  // forward of the straight-through sampler (same op sequence as gumbel_new_infected)
-  const float z0 = (logf(p) + (-logf(e0))) / 0.1f;
-  const float z1 = (logf(1.0f - p) + (-logf(e1))) / 0.1f;
-  const float m = fmaxf(z0, z1);
-  const float x0 = expf(z0 - m), x1 = expf(z1 - m);
-  const float y0 = x0 / (x0 + x1), y1 = x1 / (x0 + x1);
-  const float nu = noise ? ((y1 > y0) ? 1.0f : 0.0f)                                   // the forward's rule
-                         : own_new_infected(p, infection_uniform(seed, step, agent_offset + a));
   const float gs = g_susc ? g_susc[a] : 0.0f, gi = g_inf ? g_inf[a] : 0.0f, gt = g_time ? g_time[a] : 0.0f;
   const float gn = g_new ? g_new[a] : 0.0f;
-  const float x = s0 - nu;                                   // torch.maximum(0, x): tie splits the gradient
-  const float h = (x > 0.0f) ? 1.0f : ((x == 0.0f) ? 0.5f : 0.0f);
-  const float nu_bar = gi + gt * (now - time0[a]) - gs * h + gn;
-  float dnu_dp = -(y0 * y1 / 0.1f) * (1.0f / p + 1.0f / (1.0f - p));
-  if (!(fabsf(dnu_dp) < 3.0e38f)) dnu_dp = 0.0f;             // p == 0 or 1: y0*y1 == 0 there
-  const float ts_bar = inside ? nu_bar * dnu_dp * (-dt * p) : 0.0f;
+  float e0, e1;
+  sampler_draws(noise, n, a, seed, step, agent_offset, e0, e1);
+  float y0, y1;
+  sampler_softmax<float>(p, e0, e1, y0, y1);
+  const float nu = sampler_decision(p, noise != nullptr, y0, y1, seed, step, agent_offset + a);
+  const SampleAdjoint<float> r = sample_adjoint<float>(p, s0, time0[a], y0, y1, nu, now, gs, gi, gt, gn);
+  const float ts_bar = inside ? r.nu_bar * r.dnu_dp * (-dt * p) : 0.0f;
   x_out[a] = s0 * ts_bar;
-  grad_susc[a] = gs * h + ts_bar * ac;
+  grad_susc[a] = gs * r.h + ts_bar * ac;
   grad_time[a] = gt * (1.0f - nu);
+}
+
+// f3, the seed: adjoint of sampling with one probability per agent group followed by infect_people (include/gradjune_hip.h,
+// gj_adjoint_seed).  Three launches.  (1) one lane per agent: the per-agent term c_a = -nu_bar * d nu / d p of
+// d loss / d fraction[group[a]] (in fp64 from the fp32 inputs, into a workspace) and the elementwise outputs.
+struct SeedAdjArgs {
+  int64_t n;
+  const float* p_not;       // [n_groups]
+  const int32_t* group;     // [n] or NULL (every agent in group 0)
+  int32_t n_groups;
+  const float* susc0;
+  const float* time0;
+  const float* noise;
+  uint64_t seed, step;
+  int64_t agent_offset;
+  float now;
+  const float* g_susc;
+  const float* g_inf;
+  const float* g_time;
+  const float* g_new;
+  double* contrib;          // [n]
+  float* grad_susc;         // [n] or NULL
+  float* grad_time;         // [n] or NULL
+};
+
+__global__ __launch_bounds__(kThreads) void k_adjoint_seed_agents(const SeedAdjArgs S) {
+  const int64_t a = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (a >= S.n) return;
+  const int32_t g = S.group ? S.group[a] : 0;
+  const float s0 = S.susc0[a];
+  const float gs = S.g_susc ? S.g_susc[a] : 0.0f, gt = S.g_time ? S.g_time[a] : 0.0f;
+  if ((uint32_t)g >= (uint32_t)S.n_groups) {   // no group: not seeded (nu = 0), no term; the label is not an index
+    S.contrib[a] = 0.0;
+    if (S.grad_susc) S.grad_susc[a] = gs * ((s0 > 0.0f) ? 1.0f : ((s0 == 0.0f) ? 0.5f : 0.0f));
+    if (S.grad_time) S.grad_time[a] = gt;
+    return;
+  }
+  const float gi = S.g_inf ? S.g_inf[a] : 0.0f, gn = S.g_new ? S.g_new[a] : 0.0f;
+  const float p = S.p_not[g];
+  double e0, e1;                                                // (injected draws: the fp32 values; the library's own:
+  sampler_draws(S.noise, S.n, a, S.seed, S.step, S.agent_offset, e0, e1);   //  exp_pair's products taken in fp64)
+  float y0f = 0.0f, y1f = 0.0f;                                 // the decision is the forward's: taken in its arithmetic
+  if (S.noise) sampler_softmax<float>(p, (float)e0, (float)e1, y0f, y1f);
+  const float nu = sampler_decision(p, S.noise != nullptr, y0f, y1f, S.seed, S.step, S.agent_offset + a);
+  double y0, y1;
+  sampler_softmax<double>(p, e0, e1, y0, y1);
+  const SampleAdjoint<double> r = sample_adjoint<double>(p, s0, S.time0[a], y0, y1, nu, S.now, gs, gi, gt, gn);
+  S.contrib[a] = -(r.nu_bar * r.dnu_dp);       // d fraction = -d p
+  if (S.grad_susc) S.grad_susc[a] = gs * (float)r.h;
+  if (S.grad_time) S.grad_time[a] = gt * (1.0f - nu);
+}
+
+// (2) one WAVE per (group, chunk): the chunk's <= GJ_SEED_CHUNK terms, read through the label-sorted agent list, are
+// added in fp64 - every lane its terms in list order, then the lanes by a butterfly - and written as partial[chunk].
+// (3) one wave per group adds its chunks' partials the same way.  No atomics: the order of every sum is a function of
+// the labels alone, so two launches give the same bits.  Every index read from the tables is checked before use.
+struct SeedSumArgs {
+  int64_t n, n_sorted, n_chunks;
+  int32_t n_groups;
+  const double* contrib;
+  const int64_t* order;        // [n_sorted] or NULL (identity)
+  const int64_t* seg_offsets;  // [n_groups + 1] or NULL ({0, n})
+  const int64_t* chunk_first;  // [n_groups + 1] or NULL ({0, n_chunks})
+  const int32_t* chunk_group;  // [n_chunks] or NULL (0)
+  double* partial;             // [n_chunks]
+  double* out;                 // [n_groups]
+};
+
+__device__ __forceinline__ double wave_sum_f64(double x) {
+#pragma unroll
+  for (int off = kWave / 2; off > 0; off >>= 1) x += __shfl_xor(x, off, kWave);
+  return x;
+}
+
+__global__ __launch_bounds__(kThreads) void k_adjoint_seed_chunks(const SeedSumArgs S) {
+  const int64_t c = (int64_t)blockIdx.x * (kThreads / kWave) + threadIdx.x / kWave;
+  const int lane = threadIdx.x % kWave;
+  if (c >= S.n_chunks) return;                 // (whole waves leave: the shuffles below see full waves)
+  const int32_t g = S.chunk_group ? S.chunk_group[c] : 0;
+  double acc = 0.0;
+  if ((uint32_t)g < (uint32_t)S.n_groups) {
+    const int64_t k = c - (S.chunk_first ? S.chunk_first[g] : 0);
+    const int64_t s0 = S.seg_offsets ? S.seg_offsets[g] : 0, s1 = S.seg_offsets ? S.seg_offsets[g + 1] : S.n;
+    if (k >= 0 && s0 >= 0 && k <= (S.n_sorted - s0) / GJ_SEED_CHUNK) {
+      const int64_t begin = s0 + k * GJ_SEED_CHUNK;
+      int64_t end = begin + GJ_SEED_CHUNK;
+      if (end > s1) end = s1;
+      if (end > S.n_sorted) end = S.n_sorted;
+      for (int64_t j = begin + lane; j < end; j += kWave) {
+        const int64_t a = S.order ? S.order[j] : j;
+        if ((uint64_t)a < (uint64_t)S.n) acc += S.contrib[a];
+      }
+    }
+  }
+  acc = wave_sum_f64(acc);
+  if (lane == 0) S.partial[c] = acc;
+}
+
+__global__ __launch_bounds__(kThreads) void k_adjoint_seed_finish(const SeedSumArgs S) {
+  const int64_t g = (int64_t)blockIdx.x * (kThreads / kWave) + threadIdx.x / kWave;
+  const int lane = threadIdx.x % kWave;
+  if (g >= S.n_groups) return;
+  int64_t c0 = S.chunk_first ? S.chunk_first[g] : 0, c1 = S.chunk_first ? S.chunk_first[g + 1] : S.n_chunks;
+  if (c0 < 0) c0 = 0;
+  if (c1 > S.n_chunks) c1 = S.n_chunks;
+  double acc = 0.0;
+  for (int64_t c = c0 + lane; c < c1; c += kWave) acc += S.partial[c];
+  acc = wave_sum_f64(acc);
+  if (lane == 0) S.out[g] = acc;
 }
 
 __global__ __launch_bounds__(kThreads) void k_adjoint_transmission(
@@ -1916,6 +2011,85 @@ int gj_adjoint_sample(int64_t n, const float* susceptibility0, const float* infe
   hipLaunchKernelGGL(gj::k_adjoint_sample, dim3((unsigned)((n + gj::kThreads - 1) / gj::kThreads)), dim3(gj::kThreads),
                      0, (hipStream_t)stream, n, susceptibility0, infection_time0, acc, exp_noise, seed, step,
                      agent_offset, now, delta_time, g_susc, g_inf, g_time, g_new, x_out, grad_susc_out, grad_time_out);
+  return gj::launch_status();
+}
+
+int gj_adjoint_seed(int64_t n, const float* p_not_by_group, const int32_t* group, int32_t n_groups,
+                    const gj_seed_plan* plan, const float* susceptibility0, const float* infection_time0,
+                    const float* exp_noise, uint64_t seed, uint64_t step, int64_t agent_offset, float now,
+                    const float* g_susc, const float* g_inf, const float* g_time, const float* g_new,
+                    double* contrib_workspace, double* partial_workspace, double* grad_fraction, float* grad_susc_out,
+                    float* grad_time_out, void* stream) {
+  if (n < 0 || n_groups < 1 || n_groups > GJ_MAX_GROUPS) return GJ_E_RANGE;
+  if (!group && n_groups != 1) return GJ_E_RANGE;
+  if (!grad_fraction) return GJ_E_NULL;
+  gj::SeedSumArgs R;
+  R.n = n;
+  R.n_groups = n_groups;
+  R.contrib = contrib_workspace;
+  R.partial = partial_workspace;
+  R.out = grad_fraction;
+  if (group) {
+    if (!plan) return GJ_E_NULL;
+    if (plan->n_sorted < 0 || plan->n_sorted > n || plan->n_chunks < 0 ||
+        plan->n_chunks > plan->n_sorted / GJ_SEED_CHUNK + n_groups)
+      return GJ_E_RANGE;
+    if (!plan->seg_offsets || !plan->chunk_first) return GJ_E_NULL;
+    if (plan->n_chunks > 0 && (!plan->order || !plan->chunk_group)) return GJ_E_NULL;
+    R.n_sorted = plan->n_sorted;
+    R.n_chunks = plan->n_chunks;
+    R.order = plan->order;
+    R.seg_offsets = plan->seg_offsets;
+    R.chunk_first = plan->chunk_first;
+    R.chunk_group = plan->chunk_group;
+  } else {
+    R.n_sorted = n;
+    R.n_chunks = (n + GJ_SEED_CHUNK - 1) / GJ_SEED_CHUNK;
+    R.order = nullptr;
+    R.seg_offsets = nullptr;
+    R.chunk_first = nullptr;
+    R.chunk_group = nullptr;
+  }
+  constexpr int kWaves = gj::kThreads / gj::kWave;
+  const int64_t agent_blocks = (n + gj::kThreads - 1) / gj::kThreads;
+  const int64_t chunk_blocks = (R.n_chunks + kWaves - 1) / kWaves;
+  const int64_t group_blocks = ((int64_t)n_groups + kWaves - 1) / kWaves;
+  if (agent_blocks > 0x7fffffff || chunk_blocks > 0x7fffffff) return GJ_E_RANGE;
+  if (n > 0 && (!p_not_by_group || !susceptibility0 || !infection_time0 || !contrib_workspace)) return GJ_E_NULL;
+  if (R.n_chunks > 0 && !partial_workspace) return GJ_E_NULL;
+  if (n > 0) {
+    gj::SeedAdjArgs A;
+    A.n = n;
+    A.p_not = p_not_by_group;
+    A.group = group;
+    A.n_groups = n_groups;
+    A.susc0 = susceptibility0;
+    A.time0 = infection_time0;
+    A.noise = exp_noise;
+    A.seed = seed;
+    A.step = step;
+    A.agent_offset = agent_offset;
+    A.now = now;
+    A.g_susc = g_susc;
+    A.g_inf = g_inf;
+    A.g_time = g_time;
+    A.g_new = g_new;
+    A.contrib = contrib_workspace;
+    A.grad_susc = grad_susc_out;
+    A.grad_time = grad_time_out;
+    hipLaunchKernelGGL(gj::k_adjoint_seed_agents, dim3((unsigned)agent_blocks), dim3(gj::kThreads), 0,
+                       (hipStream_t)stream, A);
+    int rc = gj::launch_status();
+    if (rc) return rc;
+  }
+  if (R.n_chunks > 0) {
+    hipLaunchKernelGGL(gj::k_adjoint_seed_chunks, dim3((unsigned)chunk_blocks), dim3(gj::kThreads), 0,
+                       (hipStream_t)stream, R);
+    int rc = gj::launch_status();
+    if (rc) return rc;
+  }
+  hipLaunchKernelGGL(gj::k_adjoint_seed_finish, dim3((unsigned)group_blocks), dim3(gj::kThreads), 0, (hipStream_t)stream,
+                     R);
   return gj::launch_status();
 }
 

@@ -19,6 +19,7 @@ GJ_ADJ_BETA_BLOCKS = 256
 GJ_STREAM_EDGES = 2048
 GJ_MAX_GROUPS = 1 << 28
 GJ_GROUP_ERR_LABEL, GJ_GROUP_ERR_VALUE = 1, 2
+GJ_SEED_CHUNK = 1024
 
 MASK_RAW, MASK_Q, MASK_QL, MASK_QL_AGE75 = 0, 1, 2, 3
 
@@ -183,6 +184,17 @@ class SymptomsParams(C.Structure):
     ]
 
 
+class SeedPlan(C.Structure):
+    _fields_ = [
+        ("n_sorted", C.c_int64),
+        ("n_chunks", C.c_int64),
+        ("order", _vp),
+        ("seg_offsets", _vp),
+        ("chunk_first", _vp),
+        ("chunk_group", _vp),
+    ]
+
+
 #: every symbol include/gradjune_hip.h declares: (restype, argtypes)
 SYMBOLS = {
     "gj_version": (C.c_int, []),
@@ -207,6 +219,11 @@ SYMBOLS = {
     "gj_adjoint_transmission": (C.c_int, [C.c_int64, C.POINTER(AgentState), C.c_float, _vp, _vp, _vp, _vp, _vp]),
     "gj_adjoint_transmission_params": (
         C.c_int, [C.c_int64, C.POINTER(AgentState), C.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gj_adjoint_seed": (
+        C.c_int,
+        [C.c_int64, _vp, _vp, C.c_int32, C.POINTER(SeedPlan), _vp, _vp, _vp, C.c_uint64, C.c_uint64, C.c_int64,
+         C.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    ),
     "gj_adjoint_beta_partial": (
         C.c_int,
         [C.c_int64, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, C.POINTER(C.c_float), C.POINTER(C.c_int32), _vp, _vp],

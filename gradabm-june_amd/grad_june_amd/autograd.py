@@ -476,6 +476,68 @@ class NetworksForward(torch.autograd.Function):
         return (None, tbar, grad_susc, *_param_grads(nets, grads))
 
 
+class SeedByGroup(torch.autograd.Function):
+    """The seed as an autograd node (``infection.infect_fraction_by_group``): (fractions [G], susceptibility,
+    is_infected, infection_time) -> (new_infected, susceptibility', is_infected', infection_time').  Forward =
+    ``gj_sample_infect`` on ``p_not[labels]`` and fresh state tensors; backward = ``gj_adjoint_seed``, which sums the
+    per-agent terms of d loss / d fraction per group in fp64 in a fixed order.  ``env``: labels (None: one group), the
+    labelling's ``groups.SeedPlan``, ``p_not`` (float32 [G], 1 - fraction), the noise or the (seed, step, agent_offset)
+    of the Philox draws, ``now``, and - on a rank of a partitioned world - ``all_reduce``, the sum over the ranks that
+    makes every rank's gradient the whole world's (as ``DistributedHotPathStep`` does for log_beta)."""
+
+    @staticmethod
+    def forward(ctx, env, fractions, susc, inf, time):
+        from .infection import _launch_sample
+
+        labels, p_not = env["labels"], env["p_not"]
+        dev = p_not.device
+        pre = [t.detach().to(device=dev, dtype=torch.float32).contiguous() for t in (susc, inf, time)]
+        n = pre[0].numel()
+        out_s, out_i, out_t = (t.clone() for t in pre)
+        probs = p_not.expand(n).contiguous() if labels is None else p_not[labels.long()]
+        new_inf = torch.empty(n, dtype=torch.float32, device=dev)
+        _launch_sample(probs, env["exp_noise"], new_inf, now=env["now"], state=(out_s, out_i, out_t), seed=env["seed"],
+                       step=env["step"], agent_offset=env["agent_offset"])
+        ctx.env = env
+        ctx.like = (fractions.device, fractions.dtype, fractions.shape)
+        ctx.devices = [t.device for t in (susc, inf, time)]
+        ctx.save_for_backward(pre[0], pre[2])
+        return new_inf, out_s, out_i, out_t
+
+    @staticmethod
+    def backward(ctx, g_new, g_susc, g_inf, g_time):
+        env = ctx.env
+        susc0, time0 = ctx.saved_tensors
+        labels, plan, p_not = env["labels"], env["plan"], env["p_not"]
+        dev, n, G = p_not.device, susc0.numel(), p_not.numel()
+
+        def f32(g):
+            return None if g is None else g.detach().to(device=dev, dtype=torch.float32).contiguous()
+
+        g_new, g_susc, g_inf, g_time = f32(g_new), f32(g_susc), f32(g_inf), f32(g_time)
+        want_s, want_i, want_t = ctx.needs_input_grad[2:5]
+        n_chunks = plan.n_chunks if labels is not None else (n + N.GJ_SEED_CHUNK - 1) // N.GJ_SEED_CHUNK
+        contrib = torch.empty(max(1, n), dtype=torch.float64, device=dev)
+        partial = torch.empty(max(1, n_chunks), dtype=torch.float64, device=dev)
+        grad = torch.empty(G, dtype=torch.float64, device=dev)
+        grad_s = torch.empty(n, dtype=torch.float32, device=dev) if want_s else None
+        grad_t = torch.empty(n, dtype=torch.float32, device=dev) if want_t else None
+        N.check(N.load().gj_adjoint_seed(n, N.ptr(p_not), N.ptr(labels), G, C.byref(plan.c) if labels is not None else None,
+                                         N.ptr(susc0), N.ptr(time0), N.ptr(env["exp_noise"]), int(env["seed"]),
+                                         int(env["step"]), int(env["agent_offset"]), float(env["now"]), N.ptr(g_susc),
+                                         N.ptr(g_inf), N.ptr(g_time), N.ptr(g_new), N.ptr(contrib), N.ptr(partial),
+                                         N.ptr(grad), N.ptr(grad_s), N.ptr(grad_t), N.current_stream()),
+                "gj_adjoint_seed")
+        if env.get("all_reduce") is not None:
+            grad = env["all_reduce"](grad)                     # fp64: the world's gradient on every rank
+        like_dev, like_dtype, like_shape = ctx.like
+        grad_i = None
+        if want_i:
+            grad_i = g_inf if g_inf is not None else torch.zeros(n, dtype=torch.float32, device=dev)
+        outs = [None if g is None else g.to(d) for g, d in zip((grad_s, grad_i, grad_t), ctx.devices)]
+        return (None, grad.to(device=like_dev, dtype=like_dtype).reshape(like_shape), *outs)
+
+
 class SymptomsStep(torch.autograd.Function):
     """(new_infected, current_stage, next_stage, time_to_next_stage) -> the three updated arrays, with the
     reference's gradient paths (symptoms.py:98,105-124,231-236): a loss on the stages - the deaths series of

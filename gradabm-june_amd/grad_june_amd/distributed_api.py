@@ -190,17 +190,23 @@ class DistributedRunner(Runner):
         model = DistributedGradJune.from_parameters(params)
         full = Runner.get_data(params)                # the whole world, identical on every rank (same torch seed)
         n_total = len(full["agent"]["id"])
+        seed_group, log_fraction = Runner.seed_parameters(params, full)      # (keys of the whole world's labelling)
         local = model.partition(full, group=group, rank=rank, world_size=world_size, collectives=collectives)
         del full
         torch.cuda.empty_cache()
         runner = cls(model=model, data=local, timer=Timer.from_parameters(params),
-                     log_fraction_initial_cases=params["infection_seed"]["log_fraction_initial_cases"],
+                     log_fraction_initial_cases=log_fraction,
                      save_path=params["save_path"], parameters=params,
-                     age_bins=params.get("age_bins_to_save", (0, 18, 65, 100)))
+                     age_bins=params.get("age_bins_to_save", (0, 18, 65, 100)), seed_group=seed_group)
         runner.agent_offset = model.agent_range[0]
         runner.n_agents_total = n_total
         runner.group, runner.collectives = group, collectives
         return runner
+
+    def _seed_all_reduce(self):
+        """The seed's d loss / d fraction is a sum over agents: every rank adds its own, the ranks' [G] partial sums
+        are added over the forward's process group, and every rank holds the whole world's gradient."""
+        return self.model._hp.all_reduce_sum if self.collectives else None
 
     def _reduce_differentiable(self, series: torch.Tensor) -> torch.Tensor:
         from .autograd import AllReduceSum

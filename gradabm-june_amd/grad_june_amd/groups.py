@@ -1,5 +1,8 @@
 """Result series by agent group (area, super area, ethnicity, sex, any integer label).
 
+Also the host side of seeding by group: :class:`SeedPlan`, the tables ``gj_adjoint_seed`` reduces through, and
+:func:`seed_log_fractions`, the ``infection_seed`` keys ``by`` / ``log_fraction_by_group`` of the YAML schema.
+
 Host side: the label encoding (:func:`encode_groups`) and :class:`GroupStats`, the binding of ``gj_group_stats`` /
 ``gj_adjoint_group_stats`` (include/gradjune_hip.h, "row f2 by agent group") for one labelling of the agents.  The
 reference has one such reduction, ``get_cases_by_ethnicity`` (grad_june/runner.py:235-242), which its time loop never
@@ -142,3 +145,60 @@ class GroupStats:
             if err & N.GJ_GROUP_ERR_VALUE:
                 why.append("an is_infected that is not finite or beyond 2^18 (it was counted as 0)")
             raise GroupLabelError(f"{what}: " + " and ".join(why))
+
+
+class SeedPlan:
+    """One labelling as ``gj_adjoint_seed`` wants it (include/gradjune_hip.h, gj_seed_plan): the agents with a label in
+    [0, n_groups) sorted by label (stable), every group's segment cut into chunks of GJ_SEED_CHUNK agents.  Built once per
+    labelling with torch ops on the labels' device (one host read: the number of chunks)."""
+
+    def __init__(self, labels: torch.Tensor, n_groups: int, device=None):
+        if n_groups < 1 or n_groups > N.GJ_MAX_GROUPS:
+            raise ValueError(f"n_groups = {n_groups}: expected 1 .. {N.GJ_MAX_GROUPS}")
+        dev = torch.device(device) if device is not None else labels.device
+        self.labels = labels.detach().to(device=dev, dtype=torch.int32).contiguous()
+        self.n_groups, self.n = int(n_groups), self.labels.numel()
+        G = self.n_groups
+        lab = self.labels.long()
+        key = torch.where((lab >= 0) & (lab < G), lab, torch.full_like(lab, G))     # no group: sorted behind the last
+        counts = torch.bincount(key, minlength=G + 1)[:G]
+        zero = torch.zeros(1, dtype=torch.int64, device=dev)
+        chunks = (counts + (N.GJ_SEED_CHUNK - 1)) // N.GJ_SEED_CHUNK
+        self.seg_offsets = torch.cat((zero, torch.cumsum(counts, 0))).contiguous()
+        self.chunk_first = torch.cat((zero, torch.cumsum(chunks, 0))).contiguous()
+        self.n_sorted, self.n_chunks = (int(v) for v in torch.stack((counts.sum(), chunks.sum())).tolist())
+        self.order = torch.argsort(key, stable=True)[: self.n_sorted].contiguous()
+        self.chunk_group = torch.repeat_interleave(torch.arange(G, device=dev), chunks).to(torch.int32).contiguous()
+        self.c = N.SeedPlan(self.n_sorted, self.n_chunks, N.ptr(self.order), N.ptr(self.seg_offsets),
+                            N.ptr(self.chunk_first), N.ptr(self.chunk_group))
+
+    @property
+    def all_valid(self) -> bool:
+        return self.n_sorted == self.n
+
+
+def seed_log_fractions(seed_params: dict, keys=None):
+    """The ``infection_seed`` section of the YAML schema -> (attribute to seed by or None, log fractions).
+
+    ``log_fraction_initial_cases`` alone (the reference's schema): (None, that scalar, as it is).  With ``by: <agent
+    attribute>`` every group of that labelling gets its own log fraction: ``log_fraction_by_group: {key: value}`` for
+    the groups listed, the scalar for the others.  ``keys``: the labelling's column keys (``group_keys[by]``), needed
+    then; the result is a float64 tensor in their order (the YAML's doubles as they are, so that a group's fraction is
+    formed from the same number as the scalar seed's).  A key that is no group of the labelling is an error."""
+    scalar = seed_params["log_fraction_initial_cases"]
+    by, listed = seed_params.get("by"), seed_params.get("log_fraction_by_group")
+    if by is None:
+        if listed:
+            raise ValueError("infection_seed.log_fraction_by_group needs infection_seed.by (the agent attribute to group by)")
+        return None, scalar
+    check_group_name(by)
+    if keys is None:
+        raise ValueError(f"infection_seed.by = '{by}': no such labelling")
+    index = {str(k): i for i, k in enumerate(keys)}
+    out = torch.full((len(index),), float(scalar), dtype=torch.float64)
+    for k, v in (listed or {}).items():
+        if str(k) not in index:
+            raise ValueError(f"infection_seed.log_fraction_by_group: '{k}' is no value of the agents' '{by}' "
+                             f"({len(index)} groups, e.g. {list(index)[:5]})")
+        out[index[str(k)]] = float(v)
+    return by, out

@@ -93,6 +93,73 @@ def infect_fraction_of_people(data, timer, symptoms_updater, fraction, device, e
     return new_inf
 
 
+def infect_fraction_by_group(data, timer, symptoms_updater, fractions, labels, device, exp_noise=None, agent_offset=0,
+                             plan=None, all_reduce=None):
+    """Seed by agent group: agent ``a`` infected independently with probability ``fractions[labels[a]]``.
+
+    ``fractions``: tensor [G] of probabilities; ``labels``: int32 [n] in [0, G), or None with G == 1 (everybody in the
+    one group: the national seed).  Same launch, Philox key and offset conventions as ``infect_fraction_of_people``,
+    and the same bits when all groups hold one value: 1 - fraction is formed per group on the host in double and
+    rounded to fp32 once.  With ``fractions.requires_grad`` in grad mode the call is the autograd node
+    ``autograd.SeedByGroup``: ``new_infected`` and the three updated state arrays stay on the graph, and a loss on
+    anything downstream reaches every group's fraction (``gj_adjoint_seed``).
+    ``plan``: the labelling's ``groups.SeedPlan`` when the caller keeps one (built here otherwise); ``all_reduce``: for
+    a rank of a partitioned world, the sum over the ranks applied to the [G] gradient in the backward."""
+    device = require_hip(device)
+    ag = data["agent"]
+    n = ag.id.shape[0]
+    fr = fractions if isinstance(fractions, torch.Tensor) else torch.as_tensor(fractions, dtype=torch.float32)
+    if fr.dim() != 1 or fr.numel() < 1:
+        raise ValueError(f"fractions: expected a tensor [G], got shape {tuple(fr.shape)}")
+    G = fr.numel()
+    if labels is None:
+        if G != 1:
+            raise ValueError(f"{G} fractions need labels")
+    else:
+        labels = labels if isinstance(labels, torch.Tensor) else torch.as_tensor(labels)
+        if labels.numel() != n or labels.is_floating_point():
+            raise ValueError(f"labels: expected {n} integers, got {labels.numel()} of {labels.dtype}")
+        labels = labels.detach().to(device=device, dtype=torch.int32).contiguous()
+        if plan is not None:                  # the plan sorted the labels when it was built: nothing to read back
+            if plan.n != n or plan.n_groups != G:
+                raise ValueError(f"plan: {plan.n} agents in {plan.n_groups} groups, expected {n} in {G}")
+            if not plan.all_valid:
+                raise ValueError(f"labels must lie in [0, {G}): {n - plan.n_sorted} agents have no group")
+        else:
+            lo, hi = (int(v) for v in torch.aminmax(labels)) if n else (0, 0)
+            if lo < 0 or hi >= G:
+                raise ValueError(f"labels must lie in [0, {G}): found {lo} .. {hi}")
+    p_not = (1.0 - fr.detach().to(device="cpu", dtype=torch.float64)).to(torch.float32).to(device)
+    for k in ("susceptibility", "is_infected", "infection_time"):
+        if ag[k].dtype != torch.float32 or ag[k].device != device or not ag[k].is_contiguous():
+            ag[k] = ag[k].to(device=device, dtype=torch.float32).contiguous()
+    if exp_noise is not None:
+        exp_noise = exp_noise.to(device=device, dtype=torch.float32).contiguous()
+        if exp_noise.numel() != 2 * n:
+            raise ValueError("exp_noise must be [2, A]")
+    seed, step = torch.initial_seed() & 0xFFFFFFFFFFFFFFFF, next(_philox_step)
+    if torch.is_grad_enabled() and fr.requires_grad:
+        from .autograd import SeedByGroup
+
+        if labels is not None and plan is None:
+            from .groups import SeedPlan
+
+            plan = SeedPlan(labels, G, device=device)
+        env = {"labels": labels, "plan": plan, "p_not": p_not, "exp_noise": exp_noise, "seed": seed, "step": step,
+               "agent_offset": int(agent_offset), "now": float(timer.now), "all_reduce": all_reduce}
+        new_inf, ag.susceptibility, ag.is_infected, ag.infection_time = SeedByGroup.apply(
+            env, fr, ag.susceptibility, ag.is_infected, ag.infection_time)
+        return new_inf
+    probs = p_not.expand(n).contiguous() if labels is None else p_not[labels.long()]
+    for k in ("susceptibility", "is_infected", "infection_time"):
+        ag[k] = ag[k].detach()
+    new_inf = torch.empty(n, dtype=torch.float32, device=device)
+    _launch_sample(probs, exp_noise, new_inf, now=timer.now,
+                   state=(ag.susceptibility, ag.is_infected, ag.infection_time), seed=seed, step=step,
+                   agent_offset=agent_offset)
+    return new_inf
+
+
 def infect_people_at_indices(data, indices, device="cuda:0"):
     ag = data["agent"]
     idx = torch.as_tensor(list(indices), dtype=torch.long, device=ag["susceptibility"].device)

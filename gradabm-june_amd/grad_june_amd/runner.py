@@ -50,7 +50,7 @@ def world_from_npz(path) -> HeteroData:
 
 class Runner(torch.nn.Module):
     def __init__(self, model, data, timer, log_fraction_initial_cases, save_path, parameters,
-                 age_bins=(0, 18, 65, 100), groups=None):
+                 age_bins=(0, 18, 65, 100), groups=None, seed_group=None):
         super().__init__()
         self.model = model
         self.data = data
@@ -73,6 +73,12 @@ class Runner(torch.nn.Module):
             attach_groups(data["agent"], groups)
         self.group_keys = {k: np.asarray(v) for k, v in (data["agent"].get("group_keys", None) or {}).items()}
         self._group_stats = None
+        # seeding by agent group (not in the reference): ``seed_group`` names a labelling of ``group_keys``;
+        # ``log_fraction_initial_cases`` is then a tensor [G] in the order of ``group_keys[seed_group]``
+        if seed_group is not None and seed_group not in self.group_keys:
+            raise ValueError(f"seed_group '{seed_group}': no such labelling (present: {sorted(self.group_keys)})")
+        self.seed_group = seed_group
+        self._seed_plan = None
         self.restore_initial_data()
 
     @classmethod
@@ -86,15 +92,28 @@ class Runner(torch.nn.Module):
 
     @classmethod
     def from_parameters(cls, params):
+        data = cls.get_data(params)
+        seed_group, log_fraction = cls.seed_parameters(params, data)
         return cls(
             model=GradJune.from_parameters(params),
-            data=cls.get_data(params),
+            data=data,
             timer=Timer.from_parameters(params),
-            log_fraction_initial_cases=params["infection_seed"]["log_fraction_initial_cases"],
+            log_fraction_initial_cases=log_fraction,
             save_path=params["save_path"],
             parameters=params,
             age_bins=params.get("age_bins_to_save", (0, 18, 65, 100)),
+            seed_group=seed_group,
         )
+
+    @staticmethod
+    def seed_parameters(params, data):
+        """(labelling to seed by or None, log fraction(s)) from ``infection_seed`` (groups.seed_log_fractions): the
+        reference's scalar as it is, or - with ``by`` - a float32 tensor with one value per group."""
+        from .groups import seed_log_fractions
+
+        by = params["infection_seed"].get("by")
+        keys = (data["agent"].get("group_keys", None) or {}).get(by) if by is not None else None
+        return seed_log_fractions(params["infection_seed"], keys)
 
     @staticmethod
     def get_data(params):
@@ -110,6 +129,16 @@ class Runner(torch.nn.Module):
             from .groups import attach_groups
 
             attach_groups(data["agent"], params["groups_to_save"])
+        # optional (not a reference key): ``infection_seed.by: area`` seeds every group of that attribute with its own
+        # fraction.  The same encoding, at the same place; a labelling that is only seeded by gets no result series
+        seed_by = (params.get("infection_seed") or {}).get("by")
+        if seed_by is not None and seed_by not in (data["agent"].get("group_keys", None) or {}):
+            from .groups import attach_groups
+
+            if not isinstance(seed_by, str) or seed_by not in data["agent"]:
+                raise ValueError(f"infection_seed.by: the world's agents have no attribute '{seed_by}'")
+            attach_groups(data["agent"], [seed_by])
+            data["agent"].groups_without_series = [seed_by]
         by = params["system"].get("locality_order")
         if by:
             from .graph import locality_order
@@ -149,11 +178,46 @@ class Runner(torch.nn.Module):
             ag.symptoms[k] = self.data_backup["symptoms"][k].detach().clone()
         self.data["results"] = {"deaths_per_timestep": None}
 
+    def _seed_requires_grad(self) -> bool:
+        lf = self.log_fraction_initial_cases
+        return torch.is_grad_enabled() and isinstance(lf, torch.Tensor) and lf.requires_grad
+
+    def _seed_labels(self):
+        """(int32 labels on the device, groups.SeedPlan) of the labelling the seed goes by; built once."""
+        if self._seed_plan is None:
+            from .groups import SeedPlan
+
+            labels = self.data["agent"]["group_labels"][self.seed_group]
+            self._seed_plan = SeedPlan(labels, len(self.group_keys[self.seed_group]), device=require_hip(self.device))
+        return self._seed_plan.labels, self._seed_plan
+
+    def _seed_all_reduce(self):
+        """Hook: a partitioned run sums the seed's [G] gradient over the ranks (distributed_api.DistributedRunner)."""
+        return None
+
     def set_initial_cases(self):
-        new_infected = infect_fraction_of_people(
-            data=self.data, timer=self.timer, symptoms_updater=self.model.symptoms_updater,
-            device=self.device, fraction=10.0 ** self.log_fraction_initial_cases,
-            agent_offset=getattr(self, "agent_offset", 0))
+        lf = self.log_fraction_initial_cases
+        if self.seed_group is None and not self._seed_requires_grad():      # the reference's path: one national value
+            new_infected = infect_fraction_of_people(
+                data=self.data, timer=self.timer, symptoms_updater=self.model.symptoms_updater,
+                device=self.device, fraction=10.0 ** lf, agent_offset=getattr(self, "agent_offset", 0))
+        else:
+            from .infection import infect_fraction_by_group
+
+            lf = lf if isinstance(lf, torch.Tensor) else torch.as_tensor(lf, dtype=torch.float64)
+            labels, plan = (None, None) if self.seed_group is None else self._seed_labels()
+            n_groups = 1 if self.seed_group is None else plan.n_groups
+            if lf.numel() != n_groups or lf.dim() > 1:
+                raise ValueError(f"log_fraction_initial_cases: shape {tuple(lf.shape)}, expected "
+                                 + ("a scalar" if self.seed_group is None else f"[{n_groups}] (group_keys['{self.seed_group}'])"))
+            if self._seed_requires_grad():
+                fractions = (10.0 ** lf).reshape(n_groups)           # in torch: the chain rule to the log is autograd's
+            else:      # as the scalar path forms it: 10.0 ** x in Python doubles, whatever the tensor's precision
+                fractions = torch.tensor([10.0 ** v for v in lf.detach().reshape(-1).tolist()], dtype=torch.float64)
+            new_infected = infect_fraction_by_group(
+                data=self.data, timer=self.timer, symptoms_updater=self.model.symptoms_updater,
+                fractions=fractions, labels=labels, device=self.device,
+                agent_offset=getattr(self, "agent_offset", 0), plan=plan, all_reduce=self._seed_all_reduce())
         self.model.symptoms_updater(data=self.data, timer=self.timer, new_infected=new_infected)
 
     # per-step result reductions: one fused pass (gj_step_stats) into a preallocated series ------------
@@ -193,8 +257,9 @@ class Runner(torch.nn.Module):
 
             labels = self.data["agent"].get("group_labels", None) or {}
             dev = require_hip(self.device) if labels else None
+            skip = self.data["agent"].get("groups_without_series", None) or []
             self._group_stats = {name: GroupStats(labels[name], len(self.group_keys[name]), device=dev)
-                                 for name in self.group_keys}
+                                 for name in self.group_keys if name not in skip}
         return self._group_stats
 
     def _record_groups(self, data, row, diff_rows=None):
@@ -228,12 +293,13 @@ class Runner(torch.nn.Module):
         else:
             n_rows = 4096
         self._series = torch.zeros(n_rows, 2 + n_bins, dtype=torch.float64, device=require_hip(self.device))
-        # differentiable run (a log_beta is an nn.Parameter or a profile tensor requires a gradient, grad mode on):
+        # differentiable run (a log_beta is an nn.Parameter, a profile tensor or the seed requires a gradient, grad mode on):
         # the case series must stay on the autograd graph, so they are formed with tensor ops instead of the fused
         # reduction kernel
         differentiable = torch.is_grad_enabled() and (any(
             isinstance(n.log_beta, torch.Tensor) and n.log_beta.requires_grad
-            for n in model.infection_networks.networks.values()) or profile_requires_grad(data))
+            for n in model.infection_networks.networks.values()) or profile_requires_grad(data)
+            or self._seed_requires_grad())
         diff_rows = []
         groups = self._groups()
         self._group_series = {name: torch.zeros(n_rows, 2 * st.n_groups, dtype=torch.float64,
@@ -320,6 +386,8 @@ class Runner(torch.nn.Module):
                 df[key] = series.detach().cpu().numpy()
         df.to_csv(self.save_path / "results.csv")
         for name, keys in self.group_keys.items():      # [T, G] series: long format, one file per labelling
+            if f"cases_by_{name}" not in results:       # a labelling that is only seeded by has no series
+                continue
             cols = {c: results[f"{c}_by_{name}"].detach().cpu().numpy().reshape(-1)
                     for c in ("cases", "daily_cases", "deaths")}
             pd.DataFrame({"date": np.repeat(np.asarray(results["dates"], dtype=object), len(keys)),

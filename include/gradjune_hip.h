@@ -463,6 +463,47 @@ int gj_adjoint_transmission_params(int64_t n, const gj_agent_state* state0, floa
                                    float* grad_max_infectiousness_out, float* grad_shape_out, float* grad_rate_out,
                                    float* grad_shift_out, void* stream);
 
+/* gj_adjoint_seed: adjoint of the seed - gj_sample_infect on p_not[a] = p_not_by_group[group[a]] (the per-group
+ * probability of NOT being an initial case, 1 - fraction) - w.r.t. each group's fraction.  A pure addition to ABI 7.
+ * Per agent, with the rules of gj_adjoint_sample (one shared device function): the draws (e0, e1) from exp_noise or
+ * exp_pair(seed, step, agent_offset + a); y0, y1 the tau = 0.1 softmax terms; nu the forward's decision; h the
+ * subgradient of max(0, susceptibility0 - nu) (0.5 at the tie);
+ *   nu_bar = g_inf + g_time * (now - infection_time0) - g_susc * h + g_new
+ *   d nu / d p = -(y0 * y1 / 0.1) * (1/p + 1/(1-p)), 0 where that is not finite
+ *   c_a = -nu_bar * d nu / d p                       (d fraction = -d p)
+ *   grad_fraction[g] = sum over agents with group[a] == g of c_a                   (device double [n_groups])
+ *   grad_susc_out[a] = g_susc * h,  grad_time_out[a] = g_time * (1 - nu)            (each may be NULL: not written)
+ * g_* : device fp32 [n], NULL = zeros.  group: device int32 [n]; NULL = every agent in group 0 (n_groups must be 1,
+ * `plan` is not read).  An agent whose label is outside [0, n_groups) was not seeded: it contributes nothing, its
+ * nu is 0, and the label is never used as an index.
+ * The sums are taken in fp64 without atomics, in an order fixed by the labels alone, so the same inputs give the same
+ * bits from launch to launch: `plan` lists the agents with a valid label sorted by label (stable) and cuts every
+ * group's segment into chunks of GJ_SEED_CHUNK agents; one wave adds a chunk (each lane its terms in list order,
+ * then a butterfly over the lanes) into partial_workspace[chunk], then one wave per group adds its chunks the same
+ * way.  The tables are built once per labelling (groups.SeedPlan); a kernel checks every index it reads from them.
+ * Arithmetic: nu is taken in the forward's fp32 arithmetic, so it IS the forward's decision; h, nu_bar, d nu / d p
+ * and c_a are evaluated in fp64 from the fp32 inputs.  (The logarithms' rounding errors are multiplied by 1 / tau = 10
+ * on their way into y0 * y1: in fp32 a single agent's term is good to a few 1e-6 only, and underflows where fp64 does
+ * not.)  Of the library's own draws, theta and s are fp32 as everywhere; e0 = theta * s and e1 = (1 - theta) * s are
+ * formed in fp64, where the products are exact, so the last bit of s cancels in log e0 - log e1.
+ * contrib_workspace: device double [n].  partial_workspace: device double [plan->n_chunks], or
+ * [(n + GJ_SEED_CHUNK - 1) / GJ_SEED_CHUNK] when group is NULL.                                                  */
+#define GJ_SEED_CHUNK 1024
+typedef struct gj_seed_plan {
+  int64_t n_sorted;            /* agents with a label in [0, n_groups)                                          */
+  int64_t n_chunks;            /* sum over groups of ceil(size / GJ_SEED_CHUNK)                                 */
+  const int64_t* order;        /* device [n_sorted]: agent indices, stable sort by label                        */
+  const int64_t* seg_offsets;  /* device [n_groups + 1]: group g is order[seg_offsets[g] .. seg_offsets[g+1])   */
+  const int64_t* chunk_first;  /* device [n_groups + 1]: group g owns chunks chunk_first[g] .. chunk_first[g+1] */
+  const int32_t* chunk_group;  /* device [n_chunks]: the group of every chunk                                   */
+} gj_seed_plan;
+int gj_adjoint_seed(int64_t n, const float* p_not_by_group, const int32_t* group, int32_t n_groups,
+                    const gj_seed_plan* plan, const float* susceptibility0, const float* infection_time0,
+                    const float* exp_noise, uint64_t seed, uint64_t step, int64_t agent_offset, float now,
+                    const float* g_susc, const float* g_inf, const float* g_time, const float* g_new,
+                    double* contrib_workspace, double* partial_workspace, double* grad_fraction, float* grad_susc_out,
+                    float* grad_time_out, void* stream);
+
 /* d loss / d log_beta of the networks on ONE edge set, from the forward's and the transposed passes' per-venue sums:
  *   col0 + k :  ln(10) * scale * sum_v [p_contact[v] > 0]  cum_fwd[v][k] * cum_bwd[v][k] / (beta[k] * p_contact[v]) * weight[v]
  * (reference: autograd through base.py:36-42,78-83; `weights` - fp64 [n_venues] or NULL = 1 - is a rank's share of
