@@ -2,9 +2,13 @@
 ``log_beta`` and w.r.t. the incoming state, so that a loss on the infection counts can be
 back-propagated through the timesteps like with the reference (example_scripts/run_model.py:9-11).
 
-The forward of a step is the ordinary fused HIP step on fresh output tensors.  The backward is
-hand-written (``oracle/gj_oracle.py:adjoint_step`` is its dense CPU restatement, checked against the
-reference's autograd):
+The forward of a step is the ordinary fused HIP step on fresh output tensors.  There is ONE step node, ``HotPathStep``,
+for a single GPU and for a rank of a partitioned world: it is written against the few things a backward needs from "the
+place the passes run" - ``engine``, ``run_step``, ``sparse_passes(bufs, io, p, between)``, ``venue_weights``,
+``all_reduce_max``, ``all_reduce_sum`` - which ``distributed.DistributedHotPath`` provides for a rank (halo all-to-all
+and partial-sum all-reduce inside the passes, real reductions) and ``_LocalPasses`` for one GPU (two launches, identity
+reductions).  The backward is hand-written (``oracle/gj_oracle.py:adjoint_step`` is its dense CPU restatement, checked
+against the reference's autograd):
 
 * the two sparse passes are self-adjoint up to exchanging the per-network masks, so the gradient
   w.r.t. the transmissions is the SAME four tiled phases run with ``transpose = 1`` on the vector
@@ -44,6 +48,16 @@ def _keep_sums(env) -> bool:
     return bool(env.get("keep_sums", KEEP_FORWARD_SUMS))
 
 
+def _f32(g, device=None):
+    """A tensor as the kernels read it - detached, contiguous float32, on ``device`` if given; None stays None."""
+    return None if g is None else g.detach().to(device=device, dtype=torch.float32).contiguous()
+
+
+def _to_devices(grads, devices):
+    """Gradients handed back to the devices of their inputs; None (no gradient asked for) stays None."""
+    return [None if g is None else g.to(d) for g, d in zip(grads, devices)]
+
+
 def _ones(plan, n):
     """A constant vector of ones on the plan's device (the adjoint runs the passes with susceptibility = 1; the phases
     it calls only read it) - one per plan, not a fill launch per backward step."""
@@ -65,44 +79,117 @@ def _clone_forward_cum(plan, nets):
     return cum_fwd
 
 
-def _forward_sums(engine, p, bufs, acc, nets, compute_transmission: bool):
+class _LocalPasses:
+    """One GPU seen as ``distributed.DistributedHotPath`` is seen by a differentiable step: the place the passes run.
+    No peers, so the sparse passes have nothing to exchange and the two small reductions return their argument."""
+
+    halo = None                                                    # (as on a rank without peers: nothing to reduce over)
+
+    def __init__(self, engine):
+        self.engine = engine
+
+    def transmission_buffers(self):
+        return {"transmission": _new_transmission(self.engine.plan)}
+
+    def run_step(self, bufs, io, params_of):
+        self.engine.step(bufs, params_of(None), io)
+
+    def sparse_passes(self, bufs, io, p, between=None):
+        self.engine.step_phase(bufs, p, io, 8)                     # phase A, then B + C in one launch (cum stays in place)
+        if between is not None:
+            between()
+        self.engine.step_phase(bufs, p, io, 4)
+
+    def venue_weights(self, set_name):
+        return None
+
+    def all_reduce_max(self, x):
+        return x
+
+    all_reduce_sum = all_reduce_max
+
+
+def _passes_of(where):
+    """``where``: a ``DistributedHotPath``, a ``_LocalPasses``, or a bare engine (wrapped)."""
+    return where if hasattr(where, "sparse_passes") else _LocalPasses(where)
+
+
+def _step_env(env):
+    """(where the passes run, params_of, the step's transmission buffers as a callable) of a step's ``env``: one GPU
+    gives ``engine`` and ``params``, a rank of a partitioned world ``hp`` (its ``DistributedHotPath``, which steps on its
+    own extended transmission arrays) and ``params_of``."""
+    if "hp" in env:
+        hp = env["hp"]
+        return hp, env["params_of"], lambda: {k: hp.state[k] for k in ("transmission", "q_transmission")}
+    local = _LocalPasses(env["engine"])
+    return local, lambda sets: env["params"], local.transmission_buffers
+
+
+def _new_transmission(plan):
+    """A transmission array for one call: uninitialised where the passes write all of it, zeros where it has halo or
+    pad slots."""
+    n, n_ext = plan.host.n_agents, plan.host.n_ext_agents
+    return (torch.empty if n_ext == n else torch.zeros)(n_ext, dtype=torch.float32, device=plan.device)
+
+
+def _require_tiled(plan):
+    if plan.c.tiled is None or not bool(plan.c.tiled):
+        raise NotImplementedError("the backward pass runs on the tiled layout")
+
+
+def _forward_sums(where, p, bufs, acc, nets, compute_transmission: bool):
     """Forward of the two sparse passes with susceptibility = 1 in ``bufs``: fills ``acc`` with
     sum_n w_n * (L_n (m_n trans)) and returns {edge set: clone of its per-venue sums}."""
-    plan = engine.plan
+    passes = _passes_of(where)
+    engine = passes.engine
     io = engine.io(trans_susc=acc)
     p.transpose = 0
     if compute_transmission:
         engine.step_phase(bufs, p, io, 0)                      # transmission (+ q * transmission)
     else:
         engine.quarantine_transmission(bufs, p)                # the caller supplied the transmissions
-    engine.step_phase(bufs, p, io, 8)                          # phase A, then B + C in one launch (cum stays in place)
-    cum_fwd = _clone_forward_cum(plan, nets)
-    engine.step_phase(bufs, p, io, 4)
+    cum_fwd = {}
+    passes.sparse_passes(bufs, io, p, between=lambda: cum_fwd.update(_clone_forward_cum(engine.plan, nets)))
     return cum_fwd
 
 
-def _transposed_passes(engine, p, bufs, scratch, x, nets, betas, cum_fwd):
+def _transposed_passes(where, p, bufs, scratch, x, nets, betas, cum_fwd):
     """The transposed pipeline on x = susceptibility * ts_bar: returns (d loss / d transmission,
-    [d loss / d log_beta per network of ``nets``]).  ``scratch`` is the transmission buffer of ``bufs``."""
+    [d loss / d log_beta per network of ``nets``]).  ``scratch`` is the transmission buffer of ``bufs``.  On a rank the
+    passes communicate as the forward's do (the cotangents of halo agents travel by the same all-to-all as their
+    transmissions, the transposed per-venue sums by the same all-reduce) and the beta gradients are summed over the
+    ranks at the end: every rank returns the whole world's."""
+    passes = _passes_of(where)
+    engine = passes.engine
     plan = engine.plan
     n = plan.host.n_agents
     # The tiled passes sum in fixed point (2^-36 / 2^-32 resolution, |value| <= 16384 / 262144): scales chosen for the
     # forward's transmissions.  A cotangent has whatever magnitude the user's loss gives it (an MSE on case counts:
-    # 1e5; a normalised loss: 1e-10), so x is brought to max |x| in [0.5, 1) by a power of two first and the results
-    # are scaled back - exact, the passes being linear - without a host synchronisation.
+    # 1e5; a normalised loss: 1e-10), so x is brought to max |x| in [0.5, 1) by a power of two first - one scale for
+    # the whole world - and the results are scaled back - exact, the passes being linear - without a host
+    # synchronisation.
     lo, hi = torch.aminmax(x)                                  # (one reduction launch; max |x| = max(-lo, hi))
-    scale = _power_of_two_scale(torch.maximum(-lo, hi))
+    scale = _power_of_two_scale(passes.all_reduce_max(torch.maximum(-lo, hi)))
+    if scratch.numel() != n:
+        scratch[n:].zero_()                                    # halo and pad slots (a recomputation filled the halo's)
     torch.div(x, scale, out=scratch[:n])
     tbar = torch.empty(n, dtype=torch.float32, device=plan.device)
-    io_t = engine.io(trans_susc=tbar)
+    reduce = passes.halo is not None                           # peers: the ranks' fp64 dot products are summed first
+    grads: List[torch.Tensor] = []
+
+    def beta_gradients():                                      # cum' is complete
+        gs = _beta_gradients(plan, nets, betas, cum_fwd, scale, weights_of=passes.venue_weights)
+        grads.extend(gs if reduce else [g.to(torch.float32) for g in gs])
+
     p.transpose = 1
     try:
         engine.quarantine_transmission(bufs, p)                # q * x for the masked sets
-        engine.step_phase(bufs, p, io_t, 8)                    # phase A, then B + C in one launch: cum' is complete
-        grads = [g.to(torch.float32) for g in _beta_gradients(plan, nets, betas, cum_fwd, scale)]
-        engine.step_phase(bufs, p, io_t, 4)                    # tbar = d loss / d transmission (of x / scale)
+        passes.sparse_passes(bufs, engine.io(trans_susc=tbar), p, between=beta_gradients)   # tbar: of x / scale
     finally:
         p.transpose = 0
+    if reduce and grads:
+        total = passes.all_reduce_sum(torch.stack(grads))
+        grads = [total[i].to(torch.float32) for i in range(len(grads))]
     return tbar.mul_(scale), grads
 
 
@@ -189,63 +276,64 @@ def _profile_grads(ctx, n_nets, grads):
     """The profile gradients in the order of the node's inputs (nothing when the caller passed no profile tensors)."""
     if len(ctx.needs_input_grad) <= 4 + n_nets:
         return []
-    return [None if g is None else g.to(dev) for g, dev in zip(grads, ctx.profile_devices)]
+    return _to_devices(grads, ctx.profile_devices)
 
 
 class HotPathStep(torch.autograd.Function):
     """(susceptibility, is_infected, infection_time, *log_betas[, max_infectiousness, shape, rate, shift]) ->
     (susceptibility', is_infected', infection_time', new_infected).  The four profile tensors are optional inputs
-    (the step reads ``env["fixed"]``, their detached values): passed, they receive d loss / d parameter per agent."""
+    (the step reads ``env["fixed"]``, their detached values): passed, they receive d loss / d parameter per agent.
+
+    ``env``: ``fixed``, ``stage``, ``exp_noise``, ``nets``, ``betas``, optionally ``keep_sums``, and where the step runs
+    (``_step_env``): ``engine`` and ``params`` on one GPU, or ``hp`` and ``params_of`` on one rank of a multi-GPU job
+    (``distributed.DistributedHotPath``).  There the inputs and outputs are the rank's OWNED agents, the forward is the
+    multi-rank launch sequence and the backward runs the transposed passes with the forward's communication pattern
+    and ends with one all-reduce of the step's d loss / d log_beta - so every rank's ``log_beta.grad`` is the whole
+    world's gradient, equal to the single-GPU run's.  Every rank must back-propagate the same graph (a loss built from
+    the rank-summed result series: ``distributed_api.DistributedRunner``)."""
 
     @staticmethod
     def forward(ctx, env, susc, inf, time, *log_betas_and_profile):
-        engine, params, fixed, stage, exp_noise, nets = (env[k] for k in ("engine", "params", "fixed", "stage",
-                                                                           "exp_noise", "nets"))
+        passes, params_of, transmission_buffers = _step_env(env)
+        fixed, stage, exp_noise, nets = (env[k] for k in ("fixed", "stage", "exp_noise", "nets"))
         ctx.profile_devices = [t.device for t in log_betas_and_profile[len(nets):]]
+        engine = passes.engine
         plan = engine.plan
         n = plan.host.n_agents
         out_s, out_i, out_t = (t.detach().to(torch.float32).clone().contiguous() for t in (susc, inf, time))
-        n_ext = plan.host.n_ext_agents                # (one GPU: no halo slots, the step writes every transmission)
-        trans = (torch.empty if n_ext == n else torch.zeros)(n_ext, dtype=torch.float32, device=plan.device)
         new_inf = torch.empty(n, dtype=torch.float32, device=plan.device)
         bufs = AgentBuffers(plan, **fixed, infection_time=out_t, is_infected=out_i, susceptibility=out_s,
-                            transmission=trans, current_stage=stage)
+                            current_stage=stage, **transmission_buffers())
         keep = _keep_sums(env) and plan.c.tiled is not None and bool(plan.c.tiled)
         acc = torch.empty(n, dtype=torch.float32, device=plan.device) if keep else None
-        engine.step(bufs, params, engine.io(new_infected=new_inf, exp_noise=exp_noise, agent_sums=acc))
+        passes.run_step(bufs, engine.io(new_infected=new_inf, exp_noise=exp_noise, agent_sums=acc), params_of)
         ctx.env = env
         ctx.save_for_backward(susc.detach().to(torch.float32).contiguous(), inf.detach().to(torch.float32).contiguous(),
                               time.detach().to(torch.float32).contiguous())
-        ctx.transmission = trans
-        ctx.kept = (acc, _clone_forward_cum(plan, nets)) if keep else None
+        ctx.transmission = bufs.tensors["transmission"]
+        ctx.kept = (acc, _clone_forward_cum(plan, nets)) if keep else None      # (cum: complete after the all-reduce)
         return out_s, out_i, out_t, new_inf
 
     @staticmethod
     def backward(ctx, g_susc, g_inf, g_time, g_new):
         env = ctx.env
-        engine, params, fixed, stage, exp_noise, nets = (env[k] for k in ("engine", "params", "fixed", "stage",
-                                                                           "exp_noise", "nets"))
+        passes, params_of, _ = _step_env(env)
+        fixed, stage, exp_noise, nets = (env[k] for k in ("fixed", "stage", "exp_noise", "nets"))
         susc0, inf0, time0 = ctx.saved_tensors
-        plan, lib, dev = engine.plan, N.load(), engine.plan.device
+        plan, lib, dev = passes.engine.plan, N.load(), passes.engine.plan.device
         n = plan.host.n_agents
-        if plan.c.tiled is None or not bool(plan.c.tiled):
-            raise NotImplementedError("the backward pass runs on the tiled layout")
-
-        def f32(g):
-            return None if g is None else g.detach().to(torch.float32).contiguous()
-
-        g_susc, g_inf, g_time, g_new = f32(g_susc), f32(g_inf), f32(g_time), f32(g_new)
+        _require_tiled(plan)
+        p = params_of(None)
+        g_susc, g_inf, g_time, g_new = _f32(g_susc), _f32(g_inf), _f32(g_time), _f32(g_new)
         ones = _ones(plan, n)
-        n_ext = plan.host.n_ext_agents                # (no halo slots on one GPU: the transposed pass overwrites all of it)
-        scratch = (torch.empty if n_ext == n else torch.zeros)(n_ext, dtype=torch.float32, device=dev)
+        scratch = _new_transmission(plan)
         bufs = AgentBuffers(plan, **fixed, infection_time=time0, is_infected=inf0, susceptibility=ones,
                             transmission=scratch, current_stage=stage)
-        p = params
         if ctx.kept is not None:      # the forward's per-agent and per-venue sums, kept by the step
             acc, cum_fwd = ctx.kept
         else:                         # recompute the forward of the two passes from the saved pre-state
             acc = torch.empty(n, dtype=torch.float32, device=dev)
-            cum_fwd = _forward_sums(engine, p, bufs, acc, nets, compute_transmission=True)
+            cum_fwd = _forward_sums(passes, p, bufs, acc, nets, compute_transmission=True)
         # ---- elementwise adjoint of epilogue + sampler + infect_people ------------------------------------
         x = torch.empty(n, dtype=torch.float32, device=dev)
         grad_susc = torch.empty(n, dtype=torch.float32, device=dev)
@@ -255,111 +343,14 @@ class HotPathStep(torch.autograd.Function):
                                       N.ptr(g_susc), N.ptr(g_inf), N.ptr(g_time), N.ptr(g_new), N.ptr(x),
                                       N.ptr(grad_susc), N.ptr(grad_time), N.current_stream()), "gj_adjoint_sample")
         # ---- transposed passes on x = susc0 * ts_bar --------------------------------------------------------
-        tbar, grads = _transposed_passes(engine, p, bufs, scratch, x, nets, env["betas"], cum_fwd)
+        tbar, grads = _transposed_passes(passes, p, bufs, scratch, x, nets, env["betas"], cum_fwd)
         # ---- through the transmission profile ------------------------------------------------------------------
+        # (tbar is complete for a rank's owned agents after the transposed passes: no collective here)
         grad_inf = torch.empty(n, dtype=torch.float32, device=dev)
         st0 = AgentBuffers(plan, **fixed, infection_time=time0, is_infected=inf0, susceptibility=ones,
                            transmission=scratch)
         pg = _adjoint_profile(n, st0, p.now, tbar, g_inf, grad_inf, grad_time, _profile_wanted(ctx, len(nets)), dev)
         return (None, grad_susc, grad_inf, grad_time, *_param_grads(nets, grads), *_profile_grads(ctx, len(nets), pg))
-
-
-class DistributedHotPathStep(torch.autograd.Function):
-    """``HotPathStep`` on one rank of a multi-GPU job (``distributed.DistributedHotPath``): the same inputs and
-    outputs for the rank's OWNED agents.  The forward is the multi-rank launch sequence; the backward runs the
-    transposed passes with the forward's communication pattern (the cotangents of halo agents travel by the same
-    all-to-all as their transmissions, the transposed per-venue sums by the same all-reduce), and ends with one
-    all-reduce of the step's d loss / d log_beta - so every rank's ``log_beta.grad`` is the whole world's gradient,
-    equal to the single-GPU run's.  Every rank must back-propagate the same graph (a loss built from the rank-summed
-    result series: ``distributed_api.DistributedRunner``)."""
-
-    @staticmethod
-    def forward(ctx, env, susc, inf, time, *log_betas_and_profile):
-        hp, params_of, fixed, stage, exp_noise = (env[k] for k in ("hp", "params_of", "fixed", "stage", "exp_noise"))
-        ctx.profile_devices = [t.device for t in log_betas_and_profile[len(env["nets"]):]]
-        plan = hp.engine.plan
-        n = plan.host.n_agents
-        out_s, out_i, out_t = (t.detach().to(torch.float32).clone().contiguous() for t in (susc, inf, time))
-        new_inf = torch.empty(n, dtype=torch.float32, device=plan.device)
-        bufs = AgentBuffers(plan, **fixed, infection_time=out_t, is_infected=out_i, susceptibility=out_s,
-                            transmission=hp.state["transmission"], q_transmission=hp.state["q_transmission"],
-                            current_stage=stage)
-        keep = _keep_sums(env)
-        acc = torch.empty(n, dtype=torch.float32, device=plan.device) if keep else None
-        hp.run_step(bufs, hp.engine.io(new_infected=new_inf, exp_noise=exp_noise, agent_sums=acc), params_of)
-        ctx.env = env
-        ctx.save_for_backward(susc.detach().to(torch.float32).contiguous(), inf.detach().to(torch.float32).contiguous(),
-                              time.detach().to(torch.float32).contiguous())
-        ctx.kept = (acc, _clone_forward_cum(plan, env["nets"])) if keep else None      # (cum: complete after the all-reduce)
-        return out_s, out_i, out_t, new_inf
-
-    @staticmethod
-    def backward(ctx, g_susc, g_inf, g_time, g_new):
-        env = ctx.env
-        hp, params_of, fixed, stage, exp_noise, nets = (env[k] for k in ("hp", "params_of", "fixed", "stage",
-                                                                          "exp_noise", "nets"))
-        susc0, inf0, time0 = ctx.saved_tensors
-        engine = hp.engine
-        plan, lib, dev = engine.plan, N.load(), engine.plan.device
-        n, n_ext = plan.host.n_agents, plan.host.n_ext_agents
-        p = params_of(None)
-
-        def f32(g):
-            return None if g is None else g.detach().to(torch.float32).contiguous()
-
-        g_susc, g_inf, g_time, g_new = f32(g_susc), f32(g_inf), f32(g_time), f32(g_new)
-        ones = _ones(plan, n)
-        scratch = torch.zeros(n_ext, dtype=torch.float32, device=dev)
-        scratch_q = torch.zeros(n_ext, dtype=torch.float32, device=dev) if p.has_quarantine else None
-        bufs = AgentBuffers(plan, **fixed, infection_time=time0, is_infected=inf0, susceptibility=ones,
-                            transmission=scratch, q_transmission=scratch_q, current_stage=stage)
-        if ctx.kept is not None:      # the forward's per-agent and per-venue sums, kept by the step
-            acc, cum_fwd = ctx.kept
-        else:
-            acc = torch.empty(n, dtype=torch.float32, device=dev)
-            cum_fwd = {}
-
-            def keep_forward_sums():
-                cum_fwd.update(_clone_forward_cum(plan, nets))
-
-            # ---- recompute the forward of the two passes from the saved pre-state, across the ranks -----------
-            p.transpose = 0
-            engine.step_phase(bufs, p, engine.io(trans_susc=acc), 0)          # transmission (+ q * transmission)
-            hp.sparse_passes(bufs, engine.io(trans_susc=acc), p, between=keep_forward_sums)
-        # ---- elementwise adjoint of epilogue + sampler + infect_people (owned agents) ----------------------------
-        x = torch.empty(n, dtype=torch.float32, device=dev)
-        grad_susc = torch.empty(n, dtype=torch.float32, device=dev)
-        grad_time = torch.empty(n, dtype=torch.float32, device=dev)
-        N.check(lib.gj_adjoint_sample(n, N.ptr(susc0), N.ptr(time0), N.ptr(acc), N.ptr(exp_noise), int(p.seed),
-                                      int(p.step), int(p.agent_offset), float(p.now), float(p.delta_time),
-                                      N.ptr(g_susc), N.ptr(g_inf), N.ptr(g_time), N.ptr(g_new), N.ptr(x),
-                                      N.ptr(grad_susc), N.ptr(grad_time), N.current_stream()), "gj_adjoint_sample")
-        # ---- transposed passes on x = susc0 * ts_bar: one scale for the whole world -------------------------------
-        scale = _power_of_two_scale(hp.all_reduce_max(x.abs().max().reshape(1)).reshape(()))
-        scratch.zero_()
-        scratch[:n].copy_(x / scale)
-        tbar = torch.empty(n, dtype=torch.float32, device=dev)
-        grads: List[torch.Tensor] = []
-
-        def beta_gradients():
-            grads.extend(_beta_gradients(plan, nets, env["betas"], cum_fwd, scale, weights_of=hp.venue_weights))
-
-        p.transpose = 1
-        try:
-            engine.quarantine_transmission(bufs, p)                            # q * x for the masked sets
-            hp.sparse_passes(bufs, engine.io(trans_susc=tbar), p, between=beta_gradients)
-        finally:
-            p.transpose = 0
-        tbar = tbar * scale
-        total = hp.all_reduce_sum(torch.stack(grads)) if grads else None        # fp64: the world's gradient
-        grads32 = [total[i].to(torch.float32) for i in range(len(grads))]
-        # ---- through the transmission profile (owned agents) --------------------------------------------------------
-        # (tbar is complete for the owned agents after the transposed passes: their profile gradients need no collective)
-        grad_inf = torch.empty(n, dtype=torch.float32, device=dev)
-        st0 = AgentBuffers(plan, **fixed, infection_time=time0, is_infected=inf0, susceptibility=ones,
-                           transmission=scratch)
-        pg = _adjoint_profile(n, st0, p.now, tbar, g_inf, grad_inf, grad_time, _profile_wanted(ctx, len(nets)), dev)
-        return (None, grad_susc, grad_inf, grad_time, *_param_grads(nets, grads32), *_profile_grads(ctx, len(nets), pg))
 
 
 class TransmissionProfile(torch.autograd.Function):
@@ -373,8 +364,7 @@ class TransmissionProfile(torch.autograd.Function):
         engine, p = env["engine"], env["params"]
         plan = engine.plan
         n, dev = plan.host.n_agents, plan.device
-        f = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
-        vals = [f(t) for t in (mx, shape, rate, shift, time, inf)]
+        vals = [_f32(t, dev) for t in (mx, shape, rate, shift, time, inf)]
         out = torch.empty(n, dtype=torch.float32, device=dev)
         bufs = AgentBuffers(plan, **dict(zip(PROFILE, vals[:4])), infection_time=vals[4], is_infected=vals[5],
                             susceptibility=_ones(plan, n), transmission=out)
@@ -389,7 +379,7 @@ class TransmissionProfile(torch.autograd.Function):
         plan = ctx.engine.plan
         n, dev = plan.host.n_agents, plan.device
         vals = ctx.saved_tensors
-        tbar = g.detach().to(device=dev, dtype=torch.float32).contiguous()
+        tbar = _f32(g, dev)
         st0 = AgentBuffers(plan, **dict(zip(PROFILE, vals[:4])), infection_time=vals[4], is_infected=vals[5],
                            susceptibility=_ones(plan, n), transmission=tbar)
         grad_inf = torch.empty(n, dtype=torch.float32, device=dev)
@@ -400,7 +390,7 @@ class TransmissionProfile(torch.autograd.Function):
                                                         N.ptr(grad_time), *[N.ptr(o) for o in outs],
                                                         N.current_stream()), "gj_adjoint_transmission_params")
         grads = outs + [grad_time if ctx.needs_input_grad[5] else None, grad_inf if ctx.needs_input_grad[6] else None]
-        return (None, *[None if gr is None else gr.to(d) for gr, d in zip(grads, ctx.devices)])
+        return (None, *_to_devices(grads, ctx.devices))
 
 
 class AllReduceSum(torch.autograd.Function):
@@ -429,7 +419,7 @@ class NetworksForward(torch.autograd.Function):
         dev = plan.device
         trans = torch.zeros(plan.host.n_ext_agents, dtype=torch.float32, device=dev)
         trans[:n].copy_(transmission.detach())
-        susc = susceptibility.detach().to(device=dev, dtype=torch.float32).contiguous()
+        susc = _f32(susceptibility, dev)
         bufs = AgentBuffers(plan, susceptibility=susc, transmission=trans, current_stage=env["stage"])
         out = torch.empty(n, dtype=torch.float32, device=dev)
         keep = _keep_sums(env) and plan.c.tiled is not None and bool(plan.c.tiled)
@@ -452,9 +442,8 @@ class NetworksForward(torch.autograd.Function):
         trans, susc = ctx.saved_tensors
         plan, dev = engine.plan, engine.plan.device
         n = plan.host.n_agents
-        if plan.c.tiled is None or not bool(plan.c.tiled):
-            raise NotImplementedError("the backward pass runs on the tiled layout")
-        g = g_out.detach().to(torch.float32).contiguous()
+        _require_tiled(plan)
+        g = _f32(g_out)
         ones = _ones(plan, n)
         scratch = trans.clone()
         bufs = AgentBuffers(plan, susceptibility=ones, transmission=scratch, current_stage=env["stage"])
@@ -483,7 +472,7 @@ class SeedByGroup(torch.autograd.Function):
     per-agent terms of d loss / d fraction per group in fp64 in a fixed order.  ``env``: labels (None: one group), the
     labelling's ``groups.SeedPlan``, ``p_not`` (float32 [G], 1 - fraction), the noise or the (seed, step, agent_offset)
     of the Philox draws, ``now``, and - on a rank of a partitioned world - ``all_reduce``, the sum over the ranks that
-    makes every rank's gradient the whole world's (as ``DistributedHotPathStep`` does for log_beta)."""
+    makes every rank's gradient the whole world's (as ``HotPathStep`` does for log_beta)."""
 
     @staticmethod
     def forward(ctx, env, fractions, susc, inf, time):
@@ -491,7 +480,7 @@ class SeedByGroup(torch.autograd.Function):
 
         labels, p_not = env["labels"], env["p_not"]
         dev = p_not.device
-        pre = [t.detach().to(device=dev, dtype=torch.float32).contiguous() for t in (susc, inf, time)]
+        pre = [_f32(t, dev) for t in (susc, inf, time)]
         n = pre[0].numel()
         out_s, out_i, out_t = (t.clone() for t in pre)
         probs = p_not.expand(n).contiguous() if labels is None else p_not[labels.long()]
@@ -510,11 +499,7 @@ class SeedByGroup(torch.autograd.Function):
         susc0, time0 = ctx.saved_tensors
         labels, plan, p_not = env["labels"], env["plan"], env["p_not"]
         dev, n, G = p_not.device, susc0.numel(), p_not.numel()
-
-        def f32(g):
-            return None if g is None else g.detach().to(device=dev, dtype=torch.float32).contiguous()
-
-        g_new, g_susc, g_inf, g_time = f32(g_new), f32(g_susc), f32(g_inf), f32(g_time)
+        g_new, g_susc, g_inf, g_time = (_f32(g, dev) for g in (g_new, g_susc, g_inf, g_time))
         want_s, want_i, want_t = ctx.needs_input_grad[2:5]
         n_chunks = plan.n_chunks if labels is not None else (n + N.GJ_SEED_CHUNK - 1) // N.GJ_SEED_CHUNK
         contrib = torch.empty(max(1, n), dtype=torch.float64, device=dev)
@@ -534,8 +519,8 @@ class SeedByGroup(torch.autograd.Function):
         grad_i = None
         if want_i:
             grad_i = g_inf if g_inf is not None else torch.zeros(n, dtype=torch.float32, device=dev)
-        outs = [None if g is None else g.to(d) for g, d in zip((grad_s, grad_i, grad_t), ctx.devices)]
-        return (None, grad.to(device=like_dev, dtype=like_dtype).reshape(like_shape), *outs)
+        return (None, grad.to(device=like_dev, dtype=like_dtype).reshape(like_shape),
+                *_to_devices((grad_s, grad_i, grad_t), ctx.devices))
 
 
 class SymptomsStep(torch.autograd.Function):
@@ -549,8 +534,7 @@ class SymptomsStep(torch.autograd.Function):
     def forward(ctx, env, new_infected, cur, nxt, ttn):
         lib = N.load()
         n = new_infected.numel()
-        nw = new_infected.detach().to(torch.float32).contiguous()
-        cur0, nxt0, ttn0 = (t.detach().to(torch.float32).contiguous() for t in (cur, nxt, ttn))
+        nw, cur0, nxt0, ttn0 = (_f32(t) for t in (new_infected, cur, nxt, ttn))
         out_c, out_x, out_t = cur0.clone(), nxt0.clone(), ttn0.clone()
         p = env["params"]
         N.check(lib.gj_symptoms_update(n, N.ptr(env["cls"]), N.ptr(nw), N.ptr(out_c), N.ptr(out_x), N.ptr(out_t),
@@ -568,11 +552,7 @@ class SymptomsStep(torch.autograd.Function):
         nw, cur0, nxt0, ttn0 = ctx.saved_tensors
         env = ctx.env
         n = nw.numel()
-
-        def f32(g):
-            return None if g is None else g.detach().to(torch.float32).contiguous()
-
-        g_cur, g_nxt, g_ttn = f32(g_cur), f32(g_nxt), f32(g_ttn)
+        g_cur, g_nxt, g_ttn = _f32(g_cur), _f32(g_nxt), _f32(g_ttn)
         g_cur_in, g_nxt_in, g_ttn_in, g_new = (torch.empty_like(nw) for _ in range(4))
         N.check(N.load().gj_adjoint_symptoms(n, N.ptr(env["cls"]), N.ptr(nw), N.ptr(cur0), N.ptr(nxt0), N.ptr(ttn0),
                                              C.byref(env["params"]), N.ptr(env["progresses"]), N.ptr(env["dwell"]),
@@ -594,8 +574,7 @@ class GroupSeriesRow(torch.autograd.Function):
     def forward(ctx, env, is_infected, current_stage):
         stats, dead = env["stats"], int(env["dead"])
         dev = stats.labels.device
-        inf = is_infected.detach().to(device=dev, dtype=torch.float32).contiguous()
-        stage = current_stage.detach().to(device=dev, dtype=torch.float32).contiguous()
+        inf, stage = _f32(is_infected, dev), _f32(current_stage, dev)
         row = torch.zeros(2 * stats.n_groups, dtype=torch.float64, device=dev)
         stats.add(inf, stage, dead, row)
         ctx.stats, ctx.dead = stats, dead
@@ -609,11 +588,6 @@ class GroupSeriesRow(torch.autograd.Function):
         stats = ctx.stats
         (stage,) = ctx.saved_tensors
         dev = stats.labels.device
-
-        def f32(g):
-            return None if g is None else g.detach().to(device=dev, dtype=torch.float32).contiguous()
-
         want_inf, want_stage = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
-        grad_inf, grad_stage = stats.gather(stage, ctx.dead, f32(g_cases), f32(g_deaths), want_inf, want_stage)
-        return (None, None if grad_inf is None else grad_inf.to(ctx.devices[0]),
-                None if grad_stage is None else grad_stage.to(ctx.devices[1]))
+        grads = stats.gather(stage, ctx.dead, _f32(g_cases, dev), _f32(g_deaths, dev), want_inf, want_stage)
+        return (None, *_to_devices(grads, ctx.devices))

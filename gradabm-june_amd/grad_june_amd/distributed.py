@@ -951,7 +951,7 @@ class DistributedHotPath:
             e.step_phase(bufs, p_g, io, 6)                                # C of the group
         e.step_phase(bufs, p_all, io, 3)                                  # D + epilogue: all sets
 
-    # ---- what the differentiable step (autograd.DistributedHotPathStep) needs -------------------------------
+    # ---- what the differentiable step needs (autograd.HotPathStep; autograd._LocalPasses is the same for one GPU) ----
     def sparse_passes(self, bufs, io, p, between=None) -> None:
         """The two sparse passes of one step on ``bufs``' extended transmission arrays, in sequence and WITHOUT the
         decision: halo all-to-all, phases A + B, all-reduce of the partial sums, ``between()`` (every set's complete

@@ -10,8 +10,11 @@ work (symptoms, state updates) is local; the per-step result series are summed o
 loop.  Sampling noise is Philox keyed by the GLOBAL agent id and sums are fixed-point, so the series equal the
 single-GPU run's for the same seed (tests/test_gpu_distributed_virtual.py).  Differentiable like the single-GPU
 ``Runner`` (example_scripts/run_model.py:9-11): with a ``log_beta`` that requires grad the step is the autograd node
-``autograd.DistributedHotPathStep`` and the result series are summed over the ranks on the graph, so a loss on
-``results`` back-propagated on EVERY rank leaves the whole world's gradient in every rank's ``log_beta.grad``.
+``autograd.HotPathStep`` - the single-GPU run's, handed this rank's ``DistributedHotPath`` as the place its passes run -
+and the result series are summed over the ranks on the graph, so a loss on ``results`` back-propagated on EVERY rank
+leaves the whole world's gradient in every rank's ``log_beta.grad``.  ``DistributedGradJune`` is ``GradJune`` with the
+few steps of ``hot_path`` overridden that a rank does differently: the engine is the partition's, the launch parameters
+come per group of edge sets (``params_of``, with the twins of split sets), injected noise is cut to the rank's agents.
 
     torch.manual_seed(seed)                    # the same seed on every rank
     runner = DistributedRunner.from_parameters(params)          # params["system"]["device"] = this rank's GPU
@@ -32,7 +35,6 @@ from .model import GradJune
 from .plan import SPLIT_SUFFIX
 from .runner import Runner
 from .timer import Timer
-from .transmission import profile_inputs, profile_requires_grad
 from .world import require_hip
 
 
@@ -88,29 +90,24 @@ class DistributedGradJune(GradJune):
         hp = getattr(self, "_hp", None)
         if hp is None:
             raise RuntimeError("call partition(data) first")
-        nets = self.infection_networks
-        active = nets.active_networks(timer, self.policies)
-        differentiable = torch.is_grad_enabled() and (
-            any(isinstance(n.log_beta, torch.Tensor) and n.log_beta.requires_grad for n in active)
-            or any(data["agent"][k].requires_grad for k in ("susceptibility", "is_infected", "infection_time"))
-            or profile_requires_grad(data))
-        self.policies.apply(timer=timer, data=data)
-        engine, dev, n = hp.engine, hp.device, hp.rw.n_local
-        for net in active:
-            if net.name not in engine.plan.networks:
-                raise KeyError(f"network '{net.name}': edge set 'attends_{net.edge_set}' is not in the world")
-        qp = self.policies.quarantine_policies
-        has_q = bool(qp)
-        betas = {net.name: net.beta_value(self.policies, timer) for net in active}
-        betas.update({k + SPLIT_SUFFIX: v for k, v in list(betas.items())})
-        if self.rng_seed is None:
-            self.rng_seed = torch.initial_seed() & 0xFFFFFFFFFFFFFFFF
-        step = self.n_steps
-        self.n_steps += 1
-        day_type = 0 if timer.day_type == "weekday" else 1
+        out = super().hot_path(data, timer, exp_noise=exp_noise, want_probs=want_probs)
+        data["agent"].transmission = hp.state["transmission"][: hp.rw.n_local]
+        return out
 
+    # what GradJune.hot_path does differently on a rank -----------------------------------------------------------
+    def _engine(self, data, device):
+        return self._hp.engine
+
+    def _betas(self, engine, active, timer):
+        betas = super()._betas(engine, active, timer)
+        betas.update({k + SPLIT_SUFFIX: v for k, v in list(betas.items())})
+        return betas
+
+    def _launch_env(self, engine, timer, active, betas, has_q, step):
+        hp = self._hp
+        day_type = 0 if timer.day_type == "weekday" else 1
         now, duration, seed = timer.now, timer.duration, self.rng_seed      # (the backward pass calls params_of later)
-        q_threshold = qp.threshold if has_q else math.inf
+        q_threshold = self.policies.quarantine_policies.threshold if has_q else math.inf
 
         def params_of(sets):
             # a network on a set the partition split runs on both halves (its twin: same beta)
@@ -123,9 +120,21 @@ class DistributedGradJune(GradJune):
                                  has_quarantine=has_q, q_threshold=q_threshold, seed=seed, step=step,
                                  agent_offset=hp.a0)
 
+        return {"hp": hp, "params_of": params_of}
+
+    def _exp_noise(self, engine, exp_noise):
+        """[2, A] for the whole world or [2, n_local]: this rank's agents' columns."""
+        hp = self._hp
+        if exp_noise is None:
+            return None
+        exp_noise = super()._exp_noise(engine, exp_noise).reshape(2, -1)
+        if exp_noise.shape[1] != hp.rw.n_local:
+            exp_noise = exp_noise[:, hp.a0:hp.a0 + hp.rw.n_local]
+        return exp_noise.contiguous()
+
+    def _hot_path_in_place(self, data, engine, where, has_q, exp_noise, want_probs):
+        hp, dev, n = self._hp, self._hp.device, self._hp.rw.n_local
         ag = data["agent"]
-        if differentiable:
-            return self._hot_path_differentiable(data, hp, params_of, active, betas, has_q, exp_noise, want_probs)
 
         def f32(t):
             if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
@@ -143,42 +152,9 @@ class DistributedGradJune(GradJune):
                             current_stage=stage)
         new_infected = torch.empty(n, dtype=torch.float32, device=dev)
         probs = torch.empty(n, dtype=torch.float32, device=dev) if want_probs else None
-        if exp_noise is not None:                                 # [2, A] for the whole world or [2, n_local]
-            exp_noise = exp_noise.to(device=dev, dtype=torch.float32).reshape(2, -1)
-            if exp_noise.shape[1] != n:
-                exp_noise = exp_noise[:, hp.a0:hp.a0 + n]
-            exp_noise = exp_noise.contiguous()
-        hp.run_step(bufs, engine.io(not_infected_probs=probs, new_infected=new_infected, exp_noise=exp_noise), params_of)
-        ag.transmission = hp.state["transmission"][:n]
+        hp.run_step(bufs, engine.io(not_infected_probs=probs, new_infected=new_infected, exp_noise=exp_noise),
+                    where["params_of"])
         return new_infected, probs
-
-
-    def _hot_path_differentiable(self, data, hp, params_of, active, betas, has_q, exp_noise, want_probs):
-        """Row f3 across the ranks: the step as the autograd node ``autograd.DistributedHotPathStep``."""
-        from .autograd import DistributedHotPathStep
-
-        if want_probs:
-            raise NotImplementedError("want_probs is not available in differentiable mode")
-        dev, n = hp.device, hp.rw.n_local
-        ag = data["agent"]
-        f = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
-        ip = ag["infection_parameters"]
-        fixed = {k: f(ip[k]) for k in ("max_infectiousness", "shape", "rate", "shift")}
-        stage = f(ag["symptoms"]["current_stage"]).clone() if has_q else None
-        if exp_noise is not None:
-            exp_noise = exp_noise.to(device=dev, dtype=torch.float32).reshape(2, -1)
-            if exp_noise.shape[1] != n:
-                exp_noise = exp_noise[:, hp.a0:hp.a0 + n]
-            exp_noise = exp_noise.contiguous()
-        env = {"hp": hp, "params_of": params_of, "fixed": fixed, "stage": stage, "exp_noise": exp_noise,
-               "nets": list(active), "betas": dict(betas)}
-        state = [ag[k] if ag[k].dtype == torch.float32 else ag[k].to(torch.float32) for k in
-                 ("susceptibility", "is_infected", "infection_time")]
-        susc, inf, time, new_infected = DistributedHotPathStep.apply(env, *state, *[n_.log_beta for n_ in active],
-                                                                     *profile_inputs(ip))
-        ag.susceptibility, ag.is_infected, ag.infection_time = susc, inf, time
-        ag.transmission = hp.state["transmission"][:n]
-        return new_infected, None
 
 
 class DistributedRunner(Runner):

@@ -59,39 +59,59 @@ class GradJune(torch.nn.Module):
     def hot_path(self, data, timer, exp_noise=None, want_probs=False):
         """Rows a1-a9.  Returns (new_infected, not_infected_probs or None)."""
         device = require_hip(self.device)
-        nets = self.infection_networks
-        active = nets.active_networks(timer, self.policies)
+        active = self.infection_networks.active_networks(timer, self.policies)
         differentiable = torch.is_grad_enabled() and (
             any(isinstance(n.log_beta, torch.Tensor) and n.log_beta.requires_grad for n in active)
             or any(data["agent"][k].requires_grad for k in ("susceptibility", "is_infected", "infection_time"))
             or profile_requires_grad(data))
         self.policies.apply(timer=timer, data=data)
-        engine = engine_for(data, [n.spec() for n in nets.networks.values()], device)
+        engine = self._engine(data, device)
         for n in active:
             if n.name not in engine.plan.networks:
                 raise KeyError(f"network '{n.name}': edge set 'attends_{n.edge_set}' is not in the world")
-        qp = self.policies.quarantine_policies
-        has_q = bool(qp)
+        has_q = bool(self.policies.quarantine_policies)
         if self.rng_seed is None:
             self.rng_seed = torch.initial_seed() & 0xFFFFFFFFFFFFFFFF
-        params = engine.params(
-            now=timer.now, delta_time=timer.duration, day_type=0 if timer.day_type == "weekday" else 1,
-            active=[n.name for n in active], betas={n.name: n.beta_value(self.policies, timer) for n in active},
-            has_quarantine=has_q, q_threshold=qp.threshold if has_q else math.inf,
-            seed=self.rng_seed, step=self.n_steps)
+        step = self.n_steps
         self.n_steps += 1
+        betas = self._betas(engine, active, timer)
+        where = self._launch_env(engine, timer, active, betas, has_q, step)
+        exp_noise = self._exp_noise(engine, exp_noise)
         if differentiable:
-            return self._hot_path_differentiable(data, engine, params, active, has_q, exp_noise, want_probs)
+            return self._hot_path_differentiable(data, engine, where, active, betas, has_q, exp_noise, want_probs)
+        return self._hot_path_in_place(data, engine, where, has_q, exp_noise, want_probs)
+
+    # what a partitioned world does differently (distributed_api.DistributedGradJune), one method each ----------------
+    def _engine(self, data, device):
+        return engine_for(data, [n.spec() for n in self.infection_networks.networks.values()], device)
+
+    def _betas(self, engine, active, timer):
+        return {n.name: n.beta_value(self.policies, timer) for n in active}
+
+    def _launch_env(self, engine, timer, active, betas, has_q, step):
+        """Where the step runs and with which launch parameters, as ``autograd.HotPathStep`` takes it in its ``env``."""
+        qp = self.policies.quarantine_policies
+        return {"engine": engine, "params": engine.params(
+            now=timer.now, delta_time=timer.duration, day_type=0 if timer.day_type == "weekday" else 1,
+            active=[n.name for n in active], betas=betas, has_quarantine=has_q,
+            q_threshold=qp.threshold if has_q else math.inf, seed=self.rng_seed, step=step)}
+
+    def _exp_noise(self, engine, exp_noise):
+        if exp_noise is None:
+            return None
+        return exp_noise.to(device=engine.plan.device, dtype=torch.float32).contiguous()
+
+    def _hot_path_in_place(self, data, engine, where, has_q, exp_noise, want_probs):
+        """The step that updates ``data["agent"]``'s state tensors in place (nothing requires a gradient)."""
         bufs = agent_buffers(engine, data, need_params=True, need_stage=has_q)
-        n = engine.plan.host.n_agents
+        n, device = engine.plan.host.n_agents, engine.plan.device
         new_infected = torch.empty(n, dtype=torch.float32, device=device)
         probs = torch.empty(n, dtype=torch.float32, device=device) if want_probs else None
-        if exp_noise is not None:
-            exp_noise = exp_noise.to(device=device, dtype=torch.float32).contiguous()
-        engine.step(bufs, params, engine.io(not_infected_probs=probs, new_infected=new_infected, exp_noise=exp_noise))
+        engine.step(bufs, where["params"],
+                    engine.io(not_infected_probs=probs, new_infected=new_infected, exp_noise=exp_noise))
         return new_infected, probs
 
-    def _hot_path_differentiable(self, data, engine, params, active, has_q, exp_noise, want_probs):
+    def _hot_path_differentiable(self, data, engine, where, active, betas, has_q, exp_noise, want_probs):
         """Row f3: the step as an autograd node (grad_june_amd.autograd.HotPathStep)."""
         from .autograd import HotPathStep
 
@@ -99,15 +119,11 @@ class GradJune(torch.nn.Module):
             raise NotImplementedError("want_probs is not available in differentiable mode")
         dev = engine.plan.device
         ag = data["agent"]
-        n = engine.plan.host.n_agents
         f = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
         ip = ag["infection_parameters"]
         fixed = {k: f(ip[k]) for k in ("max_infectiousness", "shape", "rate", "shift")}
         stage = f(ag["symptoms"]["current_stage"]).clone() if has_q else None
-        if exp_noise is not None:
-            exp_noise = exp_noise.to(device=dev, dtype=torch.float32).contiguous()
-        env = {"engine": engine, "params": params, "fixed": fixed, "stage": stage, "exp_noise": exp_noise,
-               "nets": list(active), "betas": {n_.name: float(params.nets[i].beta) for i, n_ in enumerate(active)}}
+        env = dict(where, fixed=fixed, stage=stage, exp_noise=exp_noise, nets=list(active), betas=betas)
         state = [ag[k] if ag[k].dtype == torch.float32 else ag[k].to(torch.float32) for k in
                  ("susceptibility", "is_infected", "infection_time")]
         susc, inf, time, new_infected = HotPathStep.apply(env, *state, *[n_.log_beta for n_ in active],

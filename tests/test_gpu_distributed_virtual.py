@@ -452,3 +452,61 @@ def test_two_ranks_gradients_match_single_gpu(device, modes):
     out = mp.get_context("spawn").Array("i", [0])
     mp.spawn(_grad_worker, args=(R, 29400 + os.getpid() % 90, out, modes), nprocs=R, join=True)
     assert out[0] == 1
+
+
+def test_rank_backward_recomputation_equals_the_kept_sums(device, monkeypatch):
+    """The rank's memory-lean backward (``autograd.KEEP_FORWARD_SUMS = False``: the two sparse passes recomputed through
+    ``DistributedHotPath.sparse_passes`` before they run transposed) against the form that keeps the forward's sums: one
+    rank holding the whole 769-agent world (11 networks, both venue-launch forms, a quarantine window over days 2 to 4),
+    every log_beta and max_infectiousness a leaf.  Series and gradients are bit for bit the same in both forms, and the
+    log_beta gradients are the single-GPU Runner's to the tolerance of the two-rank test."""
+    import itertools
+
+    import grad_june_amd as G
+    from grad_june_amd import autograd as AG
+    from grad_june_amd import infection
+    from grad_june_amd.defaults import default_parameters
+    from grad_june_amd.distributed_api import DistributedRunner
+
+    def params():
+        p = default_parameters("cuda:0")
+        p["timer"]["total_days"] = 4
+        p["infection_seed"]["log_fraction_initial_cases"] = -1.3
+        for n in p["networks"]:
+            p["networks"][n]["log_beta"] += 0.6
+        p["policies"]["quarantine"] = {
+            "quarantine": {1: {"start_date": "2022-02-03", "end_date": "2022-02-20", "stage_threshold": 4}}}
+        return p
+
+    def run(make, keep):
+        monkeypatch.setattr(AG, "KEEP_FORWARD_SUMS", keep)
+        torch.manual_seed(33)
+        infection._philox_step = itertools.count(1 << 40)        # the seeding stream of a fresh process
+        runner = make(params())
+        nets = runner.model.infection_networks.networks
+        for n in nets.values():
+            n.log_beta = torch.nn.Parameter(n.log_beta.detach().clone())
+        mx = runner.data["agent"]["infection_parameters"]["max_infectiousness"].requires_grad_(True)
+        results, _ = runner()
+        cases = results["cases_per_timestep"]
+        w = torch.linspace(0.5, 1.5, cases.numel(), device=cases.device)
+        loss = (cases * w).sum() + 3.0 * results["deaths_per_timestep"].sum() + 0.25 * results["cases_by_age_65"].sum()
+        loss.backward()
+        series = {k: v.detach().cpu() for k, v in results.items() if isinstance(v, torch.Tensor)}
+        return series, {k: n.log_beta.grad.detach().cpu() for k, n in nets.items()}, mx.grad.detach().cpu()
+
+    rank = lambda p: DistributedRunner.from_parameters(p, rank=0, world_size=1, collectives=False)
+    kept, lean = run(rank, True), run(rank, False)
+    assert kept[0].keys() == lean[0].keys() and len(kept[0]) >= 3
+    for k in kept[0]:
+        assert torch.equal(kept[0][k], lean[0][k]), k
+    assert kept[1].keys() == lean[1].keys() and len(kept[1]) == 11
+    for k in kept[1]:
+        assert torch.equal(kept[1][k], lean[1][k]), k
+    assert torch.equal(kept[2], lean[2])
+    assert sum(bool(g != 0) for g in lean[1].values()) >= 5
+    assert kept[2].shape == (769,) and bool((kept[2] != 0).any())
+    _, single, _ = run(G.Runner.from_parameters, True)
+    for k, g in single.items():
+        # (the tolerance of test_two_ranks_gradients_match_single_gpu)
+        assert float(lean[1][k]) == pytest.approx(float(g), rel=2e-5, abs=1e-7), (k, float(lean[1][k]), float(g))
