@@ -1,0 +1,679 @@
+// The per-agent kernels beside the infection path, and their argument blocks: the symptoms update (f1), the per-step
+// statistics by age bin and by agent group (f2), and the elementwise and seed adjoints (f3).  One lane per agent (or
+// per four), no edge structure.  Included by gradjune_hip.hip, which holds their launches (C ABI: include/gradjune_hip.h).
+#pragma once
+#include "../../include/gradjune_hip.h"
+#include "gj_device.h"
+#include "gj_tiled.h"   // fx_t, to_fx, fx_max: the group statistics' fixed point
+
+namespace gj {
+
+// f1: disease-stage progression (reference grad_june/symptoms.py:204-247, 82-128), one lane per agent
+struct SymptomsArgs {
+  gj_symptoms_params P;
+  int64_t n;
+  const uint8_t* cls;
+  const float* new_inf;
+  float* cur;
+  float* nxt;
+  float* ttn;
+  const float* progresses;
+  const float* dwell;
+};
+
+__device__ __forceinline__ float dwell_sample(int kind, float loc, float scale, float z) {
+  const float v = loc + scale * z;
+  return kind == 1 ? __builtin_amdgcn_exp2f(v * 1.44269504088896341f) : v;      // LogNormal: exp on v_exp_f32
+}
+// The library's own draw for an agent at stage s that is due (no reference stream to reproduce: symptoms.py:82-128 draws
+// torch.bernoulli + rsample): progress with the table's probability, dwell time = LogNormal / Normal of one Box-Muller
+// normal.  On the hardware's transcendental units (v_log_f32, v_sqrt_f32, v_cos_f32 - whose argument is in revolutions -
+// v_exp_f32): the draws of a wave's due agents were half of the fused symptoms launch with libm's logf / cosf / expf.
+// ONE definition, shared by the update and its adjoint (which must replay the same draw).
+__device__ __forceinline__ void stage_draw(const gj_symptoms_params& P, int64_t a, int s, int age, bool& onward, float& d) {
+  uint32_t r[4];
+  philox4x32_10((uint64_t)(P.agent_offset + a), P.step | (1ull << 63), P.seed, r);
+  onward = u01(r[0]) < P.progress[s * 100 + age];
+  const float ln_u = __builtin_amdgcn_logf(u01(r[1])) * 0.693147180559945309f;        // ln(u) = log2(u) * ln(2)
+  const float z = __builtin_amdgcn_sqrtf(-2.0f * ln_u) * __builtin_amdgcn_cosf(u01(r[2]));   // cos(2 pi u)
+  d = onward ? dwell_sample(P.next_kind[s], P.next_loc[s], P.next_scale[s], z)
+             : dwell_sample(P.rec_kind[s], P.rec_loc[s], P.rec_scale[s], z);
+}
+
+// The update up to the draw, shared by the update and its adjoint (which recomputes the branch the agent took from the
+// PRE-step state): the values after a new infection (x1, t1: next stage = exposed, due now) and after the move to the
+// next stage (c1), the stage s the agent is then in and whether it is due a draw there.
+struct SymptomsMove {
+  float x1, t1, c1;
+  bool moving, due;
+  int s;
+};
+__device__ __forceinline__ SymptomsMove symptoms_move(const gj_symptoms_params& P, float nw, float c0, float x0,
+                                                      float t0) {
+  SymptomsMove M;
+  M.x1 = x0 + nw * (2.0f - x0);
+  M.t1 = t0 + nw * (P.time - t0);
+  M.moving = (P.time >= M.t1) && (c0 < (float)(P.n_stages - 1));
+  M.c1 = c0 - (c0 - M.x1) * (M.moving ? 1.0f : 0.0f);
+  M.s = min(max((int)M.c1, 0), P.n_stages - 1);
+  M.due = M.moving && M.s >= 2 && M.s <= P.n_stages - 2 && M.c1 == (float)M.s;
+  return M;
+}
+// a due agent's outcome: the injected one, or the library's own draw
+__device__ __forceinline__ void stage_outcome(const gj_symptoms_params& P, const float* progresses, const float* dwell,
+                                              int64_t a, int s, int age, bool& onward, float& d) {
+  if (progresses) {
+    onward = progresses[a] != 0.0f;
+    d = dwell[a];
+  } else {
+    stage_draw(P, a, s, age, onward, d);
+  }
+}
+
+// One agent's stage update (symptoms.py:204-247, 82-128).  Returns true when any of the three values changed.
+__device__ __forceinline__ bool symptoms_agent(const SymptomsArgs& S, int64_t a, float nw, int cls, float& cur,
+                                               float& nx, float& tt) {
+  const float cur0 = cur, nx0 = nx, tt0 = tt;
+  const SymptomsMove M = symptoms_move(S.P, nw, cur, nx, tt);
+  cur = M.c1;
+  nx = M.x1;
+  tt = M.t1;
+  if (M.due) {
+    bool onward;
+    float d;
+    stage_outcome(S.P, S.progresses, S.dwell, a, M.s, cls % 100, onward, d);
+    if (onward) {
+      nx = nx + 1.0f;
+    } else {
+      nx = nx - nx;
+    }
+    tt = tt + d;
+  }
+  // (bit comparison: a NaN that stays a NaN has not changed)
+  return __float_as_uint(cur) != __float_as_uint(cur0) || __float_as_uint(nx) != __float_as_uint(nx0) ||
+         __float_as_uint(tt) != __float_as_uint(tt0);
+}
+
+__global__ __launch_bounds__(kThreads) void k_symptoms(const SymptomsArgs S) {
+  const int64_t a = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (a >= S.n) return;
+  float cur = S.cur[a], nx = S.nxt[a], tt = S.ttn[a];
+  symptoms_agent(S, a, S.new_inf[a], (int)S.cls[a], cur, nx, tt);
+  S.cur[a] = cur;
+  S.nxt[a] = nx;
+  S.ttn[a] = tt;
+}
+
+// f3: adjoint of k_symptoms w.r.t. the stage values and new_infected (oracle/gj_oracle.py:adjoint_symptoms).
+// Recomputes the branch the agent took from the PRE-step state and the same randomness.
+struct SymptomsAdjointArgs {
+  gj_symptoms_params P;
+  int64_t n;
+  const uint8_t* cls;
+  const float* new_inf;
+  const float* cur0;
+  const float* nxt0;
+  const float* ttn0;
+  const float* progresses;
+  const float* dwell;
+  const float* g_cur;
+  const float* g_nxt;
+  const float* g_ttn;
+  float* g_cur_in;
+  float* g_nxt_in;
+  float* g_ttn_in;
+  float* g_new;
+};
+
+__global__ __launch_bounds__(kThreads) void k_adjoint_symptoms(const SymptomsAdjointArgs S) {
+  const int64_t a = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (a >= S.n) return;
+  const float time = S.P.time;
+  const float nw = S.new_inf[a];
+  const float x0 = S.nxt0[a], t0 = S.ttn0[a];
+  const SymptomsMove M = symptoms_move(S.P, nw, S.cur0[a], x0, t0);
+  const float m = M.moving ? 1.0f : 0.0f;
+  float gc1 = S.g_cur ? S.g_cur[a] : 0.0f;
+  float gx1 = S.g_nxt ? S.g_nxt[a] : 0.0f;
+  const float gt1 = S.g_ttn ? S.g_ttn[a] : 0.0f;
+  if (M.due) {
+    const int s = M.s;
+    bool onward;
+    float d;
+    stage_outcome(S.P, S.progresses, S.dwell, a, s, (int)(S.cls[a] % 100), onward, d);
+    gc1 += gt1 * d / (float)s;              // time += dwell * (current == s) * current / s  (either branch)
+    if (onward) {
+      gc1 += gx1 / (float)s;                // next += (current == s) * current / s
+    } else {
+      gc1 -= gx1 * M.x1 / (float)s;         // next -= next * (current == s) * current / s
+      gx1 = 0.0f;
+    }
+  }
+  gx1 += gc1 * m;                           // current -= (current - next) * moving
+  S.g_cur_in[a] = gc1 * (1.0f - m);
+  S.g_nxt_in[a] = gx1 * (1.0f - nw);        // next += new_infected * (2 - next)
+  if (S.g_ttn_in) S.g_ttn_in[a] = gt1 * (1.0f - nw);   // time += new_infected * (now - time)
+  S.g_new[a] = gx1 * (2.0f - x0) + gt1 * (time - t0);
+}
+
+// f3: elementwise adjoints (see include/gradjune_hip.h)
+__global__ __launch_bounds__(kThreads) void k_adjoint_sample(
+    int64_t n, const float* __restrict__ susc0, const float* __restrict__ time0, const float* __restrict__ acc,
+    const float* __restrict__ noise, uint64_t seed, uint64_t step, int64_t agent_offset, float now, float dt,
+    const float* __restrict__ g_susc, const float* __restrict__ g_inf, const float* __restrict__ g_time,
+    const float* __restrict__ g_new, float* __restrict__ x_out, float* __restrict__ grad_susc,
+    float* __restrict__ grad_time) {
+  const int64_t a = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (a >= n) return;
+  const float s0 = susc0[a];
+  const float ac = acc[a];
+  const float ts = s0 * ac;
+  const bool inside = (ts >= 1e-6f) && (ts <= 100.0f);
+  const float p = not_infected_prob(ts, dt);
+  const float gs = g_susc ? g_susc[a] : 0.0f, gi = g_inf ? g_inf[a] : 0.0f, gt = g_time ? g_time[a] : 0.0f;
+  const float gn = g_new ? g_new[a] : 0.0f;
+  float e0, e1;
+  sampler_draws(noise, n, a, seed, step, agent_offset, e0, e1);
+  float y0, y1;
+  sampler_softmax<float>(p, e0, e1, y0, y1);
+  const float nu = sampler_decision(p, noise != nullptr, y0, y1, seed, step, agent_offset + a);
+  const SampleAdjoint<float> r = sample_adjoint<float>(p, s0, time0[a], y0, y1, nu, now, gs, gi, gt, gn);
+  const float ts_bar = inside ? r.nu_bar * r.dnu_dp * (-dt * p) : 0.0f;
+  x_out[a] = s0 * ts_bar;
+  grad_susc[a] = gs * r.h + ts_bar * ac;
+  grad_time[a] = gt * (1.0f - nu);
+}
+
+// f3, the seed: adjoint of sampling with one probability per agent group followed by infect_people (include/gradjune_hip.h,
+// gj_adjoint_seed).  Three launches.  (1) one lane per agent: the per-agent term c_a = -nu_bar * d nu / d p of
+// d loss / d fraction[group[a]] (in fp64 from the fp32 inputs, into a workspace) and the elementwise outputs.
+struct SeedAdjArgs {
+  int64_t n;
+  const float* p_not;       // [n_groups]
+  const int32_t* group;     // [n] or NULL (every agent in group 0)
+  int32_t n_groups;
+  const float* susc0;
+  const float* time0;
+  const float* noise;
+  uint64_t seed, step;
+  int64_t agent_offset;
+  float now;
+  const float* g_susc;
+  const float* g_inf;
+  const float* g_time;
+  const float* g_new;
+  double* contrib;          // [n]
+  float* grad_susc;         // [n] or NULL
+  float* grad_time;         // [n] or NULL
+};
+
+__global__ __launch_bounds__(kThreads) void k_adjoint_seed_agents(const SeedAdjArgs S) {
+  const int64_t a = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (a >= S.n) return;
+  const int32_t g = S.group ? S.group[a] : 0;
+  const float s0 = S.susc0[a];
+  const float gs = S.g_susc ? S.g_susc[a] : 0.0f, gt = S.g_time ? S.g_time[a] : 0.0f;
+  if ((uint32_t)g >= (uint32_t)S.n_groups) {   // no group: not seeded (nu = 0), no term; the label is not an index
+    S.contrib[a] = 0.0;
+    if (S.grad_susc) S.grad_susc[a] = gs * ((s0 > 0.0f) ? 1.0f : ((s0 == 0.0f) ? 0.5f : 0.0f));
+    if (S.grad_time) S.grad_time[a] = gt;
+    return;
+  }
+  const float gi = S.g_inf ? S.g_inf[a] : 0.0f, gn = S.g_new ? S.g_new[a] : 0.0f;
+  const float p = S.p_not[g];
+  double e0, e1;                                                // (injected draws: the fp32 values; the library's own:
+  sampler_draws(S.noise, S.n, a, S.seed, S.step, S.agent_offset, e0, e1);   //  exp_pair's products taken in fp64)
+  float y0f = 0.0f, y1f = 0.0f;                                 // the decision is the forward's: taken in its arithmetic
+  if (S.noise) sampler_softmax<float>(p, (float)e0, (float)e1, y0f, y1f);
+  const float nu = sampler_decision(p, S.noise != nullptr, y0f, y1f, S.seed, S.step, S.agent_offset + a);
+  double y0, y1;
+  sampler_softmax<double>(p, e0, e1, y0, y1);
+  const SampleAdjoint<double> r = sample_adjoint<double>(p, s0, S.time0[a], y0, y1, nu, S.now, gs, gi, gt, gn);
+  S.contrib[a] = -(r.nu_bar * r.dnu_dp);       // d fraction = -d p
+  if (S.grad_susc) S.grad_susc[a] = gs * (float)r.h;
+  if (S.grad_time) S.grad_time[a] = gt * (1.0f - nu);
+}
+
+// (2) one WAVE per (group, chunk): the chunk's <= GJ_SEED_CHUNK terms, read through the label-sorted agent list, are
+// added in fp64 - every lane its terms in list order, then the lanes by a butterfly - and written as partial[chunk].
+// (3) one wave per group adds its chunks' partials the same way.  No atomics: the order of every sum is a function of
+// the labels alone, so two launches give the same bits.  Every index read from the tables is checked before use.
+struct SeedSumArgs {
+  int64_t n, n_sorted, n_chunks;
+  int32_t n_groups;
+  const double* contrib;
+  const int64_t* order;        // [n_sorted] or NULL (identity)
+  const int64_t* seg_offsets;  // [n_groups + 1] or NULL ({0, n})
+  const int64_t* chunk_first;  // [n_groups + 1] or NULL ({0, n_chunks})
+  const int32_t* chunk_group;  // [n_chunks] or NULL (0)
+  double* partial;             // [n_chunks]
+  double* out;                 // [n_groups]
+};
+
+__global__ __launch_bounds__(kThreads) void k_adjoint_seed_chunks(const SeedSumArgs S) {
+  const int64_t c = (int64_t)blockIdx.x * (kThreads / kWave) + threadIdx.x / kWave;
+  const int lane = threadIdx.x % kWave;
+  if (c >= S.n_chunks) return;                 // (whole waves leave: the shuffles below see full waves)
+  const int32_t g = S.chunk_group ? S.chunk_group[c] : 0;
+  double acc = 0.0;
+  if ((uint32_t)g < (uint32_t)S.n_groups) {
+    const int64_t k = c - (S.chunk_first ? S.chunk_first[g] : 0);
+    const int64_t s0 = S.seg_offsets ? S.seg_offsets[g] : 0, s1 = S.seg_offsets ? S.seg_offsets[g + 1] : S.n;
+    if (k >= 0 && s0 >= 0 && k <= (S.n_sorted - s0) / GJ_SEED_CHUNK) {
+      const int64_t begin = s0 + k * GJ_SEED_CHUNK;
+      int64_t end = begin + GJ_SEED_CHUNK;
+      if (end > s1) end = s1;
+      if (end > S.n_sorted) end = S.n_sorted;
+      for (int64_t j = begin + lane; j < end; j += kWave) {
+        const int64_t a = S.order ? S.order[j] : j;
+        if ((uint64_t)a < (uint64_t)S.n) acc += S.contrib[a];
+      }
+    }
+  }
+  acc = wave_sum(acc);
+  if (lane == 0) S.partial[c] = acc;
+}
+
+__global__ __launch_bounds__(kThreads) void k_adjoint_seed_finish(const SeedSumArgs S) {
+  const int64_t g = (int64_t)blockIdx.x * (kThreads / kWave) + threadIdx.x / kWave;
+  const int lane = threadIdx.x % kWave;
+  if (g >= S.n_groups) return;
+  int64_t c0 = S.chunk_first ? S.chunk_first[g] : 0, c1 = S.chunk_first ? S.chunk_first[g + 1] : S.n_chunks;
+  if (c0 < 0) c0 = 0;
+  if (c1 > S.n_chunks) c1 = S.n_chunks;
+  double acc = 0.0;
+  for (int64_t c = c0 + lane; c < c1; c += kWave) acc += S.partial[c];
+  acc = wave_sum(acc);
+  if (lane == 0) S.out[g] = acc;
+}
+
+// psi(x) = d lgamma / dx (torch.digamma, the derivative torch's autograd gives lgamma), for the adjoint of the profile's
+// 1 / Gamma(shape).  x < 0: reflection psi(x) = psi(1 - x) - pi / tan(pi x), NaN at the poles; x == 0: -inf (torch:
+// copysign(inf, -x)).  x > 0: the recurrence psi(x) = psi(x + 1) - 1/x up to x >= 6, then the asymptotic series to
+// x^-6 (truncation: next term 1/(240 x^8) < 2.6e-9 there).  The error is that of fp32 rounding of the sum: a few ulp
+// of the largest term, i.e. ~1e-6 absolute for x >= 0.25 and a few ulp of 1/x below (x = 0.02: psi ~ -50, ~1e-5) -
+// over inv_gamma's fast range (0.25, 16) and its libm fallback range alike.  NaN in, NaN out.  No libm: v_log_f32
+// and (x < 0 only) v_sin/v_cos.
+__device__ __forceinline__ float digamma(float x) {
+  if (x == 0.0f) return copysignf(__builtin_inff(), -x);
+  float refl = 0.0f;
+  if (x < 0.0f) {
+    const float r = x - truncf(x);                     // (-1, 0]; tan(pi x) = tan(pi r)
+    if (r == 0.0f) return __builtin_nanf("");          // negative integer: a pole
+    // v_sin_f32 / v_cos_f32 take revolutions: sin(pi r) = sin(2 pi * r / 2)
+    refl = 3.14159265358979f * __builtin_amdgcn_cosf(0.5f * r) / __builtin_amdgcn_sinf(0.5f * r);
+    x = 1.0f - x;
+  }
+  float acc = 0.0f;
+  while (x < 6.0f) {                                   // (false for NaN)
+    acc += 1.0f / x;
+    x += 1.0f;
+  }
+  const float ix = 1.0f / x, ix2 = ix * ix;
+  float s = ix2 * (1.0f / 252.0f);
+  s = ix2 * (1.0f / 120.0f - s);
+  s = ix2 * (1.0f / 12.0f - s);
+  const float lnx = __builtin_amdgcn_logf(x) * 0.693147180559945309f;
+  return lnx - 0.5f * ix - s - acc - refl;
+}
+
+// f3: the profile's adjoint, one body for two kernels.  k_adjoint_transmission (PARAMS = false): grad_inf = g_inf +
+// trans_bar * d trans / d is_infected and grad_time -= trans_bar * d trans / d t.  k_adjoint_transmission_params adds
+// the adjoint w.r.t. the profile's own per-agent parameters.  With T the profile, d = t - shift, u = d * rate:
+//   dT/d max_inf = sign * aux * aux2 * is_infected   (not T / max_inf: max_inf == 0 is allowed)
+//   dT/d shape   = T * (ln u - psi(shape))           (torch: pow'(exponent) = pow * ln(base), masked to 0 at base == 0
+//                                                     with exponent >= 0; lgamma' = digamma)
+//   dT/d rate    = T * (shape / rate - d)
+//   dT/d shift   = T * (rate - (shape - 1) / d)      (= -dT/dt: the infection_time term shares it)
+// Each NULL output is neither computed nor written: a launch moves bytes only for the parameters that need a gradient.
+// is_infected == 0 gives 0 in every output.
+template <bool PARAMS>
+__device__ __forceinline__ void adjoint_transmission_agent(
+    int64_t n, const float* __restrict__ mx, const float* __restrict__ shp, const float* __restrict__ rt,
+    const float* __restrict__ sh, const float* __restrict__ time0, const float* __restrict__ inf0, float now,
+    const float* __restrict__ trans_bar, const float* __restrict__ g_inf, float* __restrict__ grad_inf,
+    float* __restrict__ grad_time, float* __restrict__ grad_mx, float* __restrict__ grad_shp,
+    float* __restrict__ grad_rt, float* __restrict__ grad_sh) {
+  const int64_t a = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (a >= n) return;
+  const float s = shp[a], r = rt[a];
+  const ProfileHead h = profile_head(s, r, sh[a], time0[a], now);
+  const float base = mx[a] * h.sign * h.aux * h.aux2;        // d trans / d is_infected
+  const float tb = trans_bar[a];                             // (loaded here: not held in a register across the profile)
+  const float inf = inf0[a];
+  float p_mx = 0.0f, p_shp = 0.0f, p_rt = 0.0f, dtdt = 0.0f;  // d trans / d parameter; d trans / d t = -dT/d shift
+  if (inf != 0.0f) {
+    const float T = base * inf;
+    dtdt = T * ((s - 1.0f) / h.d - r);
+    if (PARAMS && grad_mx) p_mx = h.sign * h.aux * h.aux2 * inf;
+    if (PARAMS && grad_shp) {
+      const float u = h.d * r;
+      const float lnu = (u == 0.0f && s >= 1.0f) ? 0.0f : __builtin_amdgcn_logf(u) * 0.693147180559945309f;
+      p_shp = T * lnu - T * digamma(s);
+    }
+    if (PARAMS && grad_rt) p_rt = T * (s / r - h.d);
+  }
+  grad_inf[a] = (g_inf ? g_inf[a] : 0.0f) + tb * base;
+  grad_time[a] = grad_time[a] - tb * dtdt;                   // d t / d infection_time = -1
+  if (PARAMS && grad_mx) grad_mx[a] = tb * p_mx;
+  if (PARAMS && grad_shp) grad_shp[a] = tb * p_shp;
+  if (PARAMS && grad_rt) grad_rt[a] = tb * p_rt;
+  if (PARAMS && grad_sh) grad_sh[a] = 0.0f - tb * dtdt;     // (0 - x: no -0 for the uninfected)
+}
+
+__global__ __launch_bounds__(kThreads) void k_adjoint_transmission(
+    int64_t n, const float* __restrict__ mx, const float* __restrict__ shp, const float* __restrict__ rt,
+    const float* __restrict__ sh, const float* __restrict__ time0, const float* __restrict__ inf0, float now,
+    const float* __restrict__ trans_bar, const float* __restrict__ g_inf, float* __restrict__ grad_inf,
+    float* __restrict__ grad_time) {
+  adjoint_transmission_agent<false>(n, mx, shp, rt, sh, time0, inf0, now, trans_bar, g_inf, grad_inf, grad_time,
+                                    nullptr, nullptr, nullptr, nullptr);
+}
+__global__ __launch_bounds__(kThreads) void k_adjoint_transmission_params(
+    int64_t n, const float* __restrict__ mx, const float* __restrict__ shp, const float* __restrict__ rt,
+    const float* __restrict__ sh, const float* __restrict__ time0, const float* __restrict__ inf0, float now,
+    const float* __restrict__ trans_bar, const float* __restrict__ g_inf, float* __restrict__ grad_inf,
+    float* __restrict__ grad_time, float* __restrict__ grad_mx, float* __restrict__ grad_shp,
+    float* __restrict__ grad_rt, float* __restrict__ grad_sh) {
+  adjoint_transmission_agent<true>(n, mx, shp, rt, sh, time0, inf0, now, trans_bar, g_inf, grad_inf, grad_time, grad_mx,
+                                   grad_shp, grad_rt, grad_sh);
+}
+
+// f2: per-step result reductions (reference grad_june/runner.py:167,198-224), one streaming pass
+struct StatsArgs {
+  int64_t n;
+  const uint8_t* cls;
+  const float* inf;
+  const float* stage;
+  int32_t n_bins;
+  int32_t edges[GJ_MAX_AGE_BINS + 1];
+  int32_t dead;
+  int32_t vec4;     // all three arrays 16-byte (cls: 4-byte) aligned
+  double* out;
+};
+
+// A lane's sums over its agents - cases, cases per age bin, deaths - and the workgroup's reduction of them: a wave sum,
+// the waves' sums through LDS in wave order, one atomicAdd per non-zero output.  One per kernel (finish owns the LDS).
+struct AgeBins {
+  static constexpr int kOut = GJ_MAX_AGE_BINS + 2;
+  const StatsArgs& R;
+  double acc[kOut];
+  __device__ __forceinline__ explicit AgeBins(const StatsArgs& r) : R(r) {
+#pragma unroll
+    for (int k = 0; k < kOut; ++k) acc[k] = 0.0;
+  }
+  __device__ __forceinline__ void take(float inf, float stage, int cls) {
+    const int age = cls % 100;
+    acc[0] += inf;
+#pragma unroll
+    for (int b = 0; b < GJ_MAX_AGE_BINS; ++b)
+      if (b < R.n_bins && age > R.edges[b] && age < R.edges[b + 1]) acc[1 + b] += inf;
+    if (stage == (float)R.dead) acc[GJ_MAX_AGE_BINS + 1] += 1.0;
+  }
+  // four agents of one dword of classes
+  __device__ __forceinline__ void take4(const float4& inf, const float4& stage, uint32_t cls) {
+    take(inf.x, stage.x, (int)(cls & 0xFF));
+    take(inf.y, stage.y, (int)((cls >> 8) & 0xFF));
+    take(inf.z, stage.z, (int)((cls >> 16) & 0xFF));
+    take(inf.w, stage.w, (int)(cls >> 24));
+  }
+  __device__ __forceinline__ void finish(double* out) {
+    __shared__ double part[kThreads / kWave][kOut];
+    const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
+#pragma unroll
+    for (int k = 0; k < kOut; ++k) {
+      const double v = wave_sum(acc[k]);
+      if (lane == 0) part[wave][k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < kOut) {
+      double v = 0.0;
+      for (int w = 0; w < kThreads / kWave; ++w) v += part[w][threadIdx.x];
+      const int k = threadIdx.x;
+      int dst = -1;
+      if (k == 0) dst = 0;
+      else if (k <= GJ_MAX_AGE_BINS) dst = (k - 1 < R.n_bins) ? k : -1;
+      else dst = 1 + R.n_bins;
+      if (dst >= 0 && v != 0.0) atomicAdd(&out[dst], v);
+    }
+  }
+};
+
+__global__ __launch_bounds__(kThreads) void k_step_stats(const StatsArgs S) {
+  AgeBins bins(S);
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  int64_t first_scalar = 0;
+  if (S.vec4) {   // 16-byte aligned arrays: four agents per lane and load (the scalar form is latency-bound)
+    const int64_t n4 = S.n >> 2;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride)
+      bins.take4(reinterpret_cast<const float4*>(S.inf)[i], reinterpret_cast<const float4*>(S.stage)[i],
+                 reinterpret_cast<const uint32_t*>(S.cls)[i]);
+    first_scalar = n4 << 2;
+  }
+  for (int64_t a = first_scalar + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; a < S.n; a += stride)
+    bins.take(S.inf[a], S.stage[a], (int)S.cls[a]);
+  bins.finish(S.out);
+}
+
+// f1 + f2 in one pass (gj_symptoms_step_stats): the stage update of four agents per lane, written back only where a
+// value changed (early in an epidemic almost nobody moves: the three arrays are then read, not rewritten), and the
+// Runner's reductions taken from the registers that hold the updated stages.
+__global__ __launch_bounds__(kThreads) void k_symptoms_stats(const SymptomsArgs S, const StatsArgs R) {
+  AgeBins bins(R);
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  int64_t first_scalar = 0;
+  if (R.vec4) {
+    const int64_t n4 = S.n >> 2;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+      // all six loads issued before the first use
+      const float4 nw = reinterpret_cast<const float4*>(S.new_inf)[i];
+      float4 c = reinterpret_cast<const float4*>(S.cur)[i];
+      float4 x = reinterpret_cast<const float4*>(S.nxt)[i];
+      float4 t = reinterpret_cast<const float4*>(S.ttn)[i];
+      const float4 f = reinterpret_cast<const float4*>(R.inf)[i];
+      const uint32_t cl = reinterpret_cast<const uint32_t*>(S.cls)[i];
+      bool ch = symptoms_agent(S, 4 * i, nw.x, (int)(cl & 0xFF), c.x, x.x, t.x);
+      ch |= symptoms_agent(S, 4 * i + 1, nw.y, (int)((cl >> 8) & 0xFF), c.y, x.y, t.y);
+      ch |= symptoms_agent(S, 4 * i + 2, nw.z, (int)((cl >> 16) & 0xFF), c.z, x.z, t.z);
+      ch |= symptoms_agent(S, 4 * i + 3, nw.w, (int)(cl >> 24), c.w, x.w, t.w);
+      if (ch) {
+        reinterpret_cast<float4*>(S.cur)[i] = c;
+        reinterpret_cast<float4*>(S.nxt)[i] = x;
+        reinterpret_cast<float4*>(S.ttn)[i] = t;
+      }
+      bins.take4(f, c, cl);
+    }
+    first_scalar = n4 << 2;
+  }
+  for (int64_t a = first_scalar + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; a < S.n; a += stride) {
+    float cur = S.cur[a], nx = S.nxt[a], tt = S.ttn[a];
+    const int cls = (int)S.cls[a];
+    if (symptoms_agent(S, a, S.new_inf[a], cls, cur, nx, tt)) {
+      S.cur[a] = cur;
+      S.nxt[a] = nx;
+      S.ttn[a] = tt;
+    }
+    bins.take(R.inf[a], cur, cls);
+  }
+  bins.finish(R.out);
+}
+
+// f2 by agent group (gj_group_stats): segmented sums of is_infected and of the deaths indicator over an int32 label.
+// Summed as 64-bit integers (is_infected in 32.32 fixed point, deaths as a count), so every order of the additions
+// gives the same bits.  Each lane carries ONE open run (label, two sums) across its agents; a run is closed when the
+// lane meets another label.  Closing is done by the whole wave: the lanes that close the same label fold their sums
+// with shuffles and one of them adds (two rounds, which is what a wave that straddles a boundary of sorted labels
+// needs; lanes still open after them add on their own).  LDS = true: the adds go to this workgroup's histogram in LDS,
+// which is added to the workspace at the end, one global atomic per non-zero accumulator.  LDS = false: the adds are
+// global atomics on the workspace.  A workgroup owns a CONTIGUOUS share of the agents, so that sorted labels give it
+// few groups.
+constexpr int kGroupFxBits = 32;
+constexpr int kGroupLdsMax = 4096;       // 2 * 8 B * 4096 = 64 KiB of LDS per workgroup: two workgroups per CU
+constexpr int kGroupLdsThreads = 1024, kGroupLdsBlocks = 512;
+constexpr int kGroupAdjLdsMax = 2048;    // gj_adjoint_group_stats stages 2 * 4 B * 2048 = 16 KiB per workgroup (above
+                                         // that, filling the copy costs more than the gathers it saves)
+constexpr uint32_t kGroupBadLabel = 1u, kGroupBadValue = 2u;    // GJ_GROUP_ERR_LABEL / GJ_GROUP_ERR_VALUE
+
+struct GroupArgs {
+  int64_t n;
+  const int32_t* group;
+  const float* inf;
+  const float* stage;
+  int32_t n_groups;
+  int32_t dead;
+  int32_t vec4;     // all three arrays 16-byte aligned
+  fx_t* ws;         // [2 * n_groups] sums, then the error word
+};
+
+template <bool LDS>
+__global__ __launch_bounds__(LDS ? kGroupLdsThreads : kThreads) void k_group_stats(const GroupArgs S) {
+  extern __shared__ fx_t hist[];     // LDS: [2 * n_groups]
+  const int G = S.n_groups;
+  if (LDS) {
+    for (int i = threadIdx.x; i < 2 * G; i += blockDim.x) hist[i] = 0;
+    __syncthreads();
+  }
+  const int lane = threadIdx.x % kWave;
+  int run = -1;            // label of this lane's open run
+  fx_t rc = 0, rd = 0;     // its sums: cases (fixed point), deaths (count)
+  uint32_t err = 0;
+  auto add = [&](int g, fx_t c, fx_t d) {
+    fx_t* dst = LDS ? hist : S.ws;
+    if (c) atomicAdd(&dst[g], c);
+    if (d) atomicAdd(&dst[G + g], d);
+  };
+  // wave-convergent: closes the run of every lane with `closing` set
+  auto close_runs = [&](bool closing) {
+    closing = closing && run >= 0;
+#pragma unroll 1
+    for (int round = 0; round < 2; ++round) {
+      const unsigned long long m = __ballot(closing);
+      if (m == 0) return;
+      const int leader = __ffsll((long long)m) - 1;
+      const int label = __shfl(run, leader, kWave);
+      const bool mine = closing && run == label;
+      const fx_t c = wave_sum<fx_t>(mine ? rc : 0), d = wave_sum<fx_t>(mine ? rd : 0);
+      if (lane == leader) add(label, c, d);
+      if (mine) closing = false, run = -1, rc = 0, rd = 0;
+    }
+    if (closing) add(run, rc, rd), run = -1, rc = 0, rd = 0;
+  };
+  // wave-convergent: one agent per lane (`on` = this lane has one)
+  auto take = [&](bool on, int g, float inf, float stage) {
+    if (on && (uint32_t)g >= (uint32_t)G) err |= kGroupBadLabel, on = false;   // never an index: the agent is skipped
+    const bool differs = on && g != run;
+    if (__any(differs && run >= 0)) close_runs(differs);
+    if (!on) return;
+    run = g;
+    const bool ok = fabsf(inf) <= fx_max<kGroupFxBits>();      // false for NaN too
+    if (!ok) err |= kGroupBadValue;
+    rc += to_fx<kGroupFxBits>(ok ? inf : 0.0f);
+    rd += (stage == (float)S.dead) ? 1u : 0u;
+  };
+  // this workgroup's share, in units of four agents (vec4) or of one
+  const int64_t units = S.vec4 ? (S.n >> 2) : S.n;
+  const int64_t per = (units + gridDim.x - 1) / gridDim.x;
+  const int64_t u0 = (int64_t)blockIdx.x * per, u1 = (u0 + per < units) ? u0 + per : units;
+  for (int64_t base = u0; base < u1; base += blockDim.x) {     // (the same trip count for every lane of a wave)
+    const int64_t i = base + threadIdx.x;
+    const bool on = i < u1;
+    if (S.vec4) {
+      int4 g = make_int4(0, 0, 0, 0);
+      float4 f = make_float4(0.f, 0.f, 0.f, 0.f), s = f;
+      if (on) {
+        g = reinterpret_cast<const int4*>(S.group)[i];
+        f = reinterpret_cast<const float4*>(S.inf)[i];
+        s = reinterpret_cast<const float4*>(S.stage)[i];
+      }
+      take(on, g.x, f.x, s.x);
+      take(on, g.y, f.y, s.y);
+      take(on, g.z, f.z, s.z);
+      take(on, g.w, f.w, s.w);
+    } else {
+      take(on, on ? S.group[i] : 0, on ? S.inf[i] : 0.f, on ? S.stage[i] : 0.f);
+    }
+  }
+  if (S.vec4 && blockIdx.x == gridDim.x - 1 && threadIdx.x < kWave) {     // the n % 4 agents behind the last float4
+    const int64_t a = (units << 2) + threadIdx.x;
+    const bool on = a < S.n;
+    take(on, on ? S.group[a] : 0, on ? S.inf[a] : 0.f, on ? S.stage[a] : 0.f);
+  }
+  close_runs(true);
+  if (err) atomicOr(reinterpret_cast<uint32_t*>(S.ws + 2 * (int64_t)G), err);
+  if (LDS) {
+    __syncthreads();
+    for (int i = threadIdx.x; i < 2 * G; i += blockDim.x) {
+      const fx_t v = hist[i];
+      if (v) atomicAdd(&S.ws[i], v);
+    }
+  }
+}
+
+// out += the sums as doubles (once, so the rounding does not depend on any order); the sums are zeroed for the next call
+__global__ __launch_bounds__(kThreads) void k_group_finish(int32_t n_groups, fx_t* ws, double* out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= 2 * (int64_t)n_groups) return;
+  const fx_t v = ws[i];
+  if (v == 0) return;
+  ws[i] = 0;
+  out[i] += (i < n_groups) ? (double)(long long)v * (1.0 / (double)(1ull << kGroupFxBits)) : (double)v;
+}
+
+// adjoint of gj_group_stats: a gather through the labels
+struct GroupAdjArgs {
+  int64_t n;
+  const int32_t* group;
+  const float* stage;
+  const float* g_cases;
+  const float* g_deaths;
+  float* grad_inf;
+  float* grad_stage;
+  int32_t n_groups;
+  int32_t dead;
+  int32_t vec4;
+};
+
+template <bool LDS>
+__global__ __launch_bounds__(kThreads) void k_adjoint_group_stats(const GroupAdjArgs S) {
+  extern __shared__ float staged[];     // LDS: g_cases [n_groups], g_deaths [n_groups]
+  const int G = S.n_groups;
+  const float* gc = S.g_cases;
+  const float* gd = S.g_deaths;
+  if (LDS) {
+    for (int i = threadIdx.x; i < G; i += blockDim.x) {
+      staged[i] = gc ? gc[i] : 0.0f;
+      staged[G + i] = gd ? gd[i] : 0.0f;
+    }
+    __syncthreads();
+    gc = staged;
+    gd = staged + G;
+  }
+  const float dead = (float)S.dead;
+  auto cases = [&](int g) { return ((uint32_t)g < (uint32_t)G && gc) ? gc[g] : 0.0f; };
+  auto deaths = [&](int g, float st) {      // autograd of (stage == dead) * stage / dead: (g / dead) * mask
+    const float v = ((uint32_t)g < (uint32_t)G && gd) ? gd[g] : 0.0f;
+    return v / dead * (st == dead ? 1.0f : 0.0f);
+  };
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  int64_t first_scalar = 0;
+  if (S.vec4) {
+    const int64_t n4 = S.n >> 2;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+      const int4 g = reinterpret_cast<const int4*>(S.group)[i];
+      if (S.grad_inf) reinterpret_cast<float4*>(S.grad_inf)[i] = make_float4(cases(g.x), cases(g.y), cases(g.z), cases(g.w));
+      if (S.grad_stage) {
+        const float4 s = reinterpret_cast<const float4*>(S.stage)[i];
+        reinterpret_cast<float4*>(S.grad_stage)[i] =
+            make_float4(deaths(g.x, s.x), deaths(g.y, s.y), deaths(g.z, s.z), deaths(g.w, s.w));
+      }
+    }
+    first_scalar = n4 << 2;
+  }
+  for (int64_t a = first_scalar + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; a < S.n; a += stride) {
+    const int g = S.group[a];
+    if (S.grad_inf) S.grad_inf[a] = cases(g);
+    if (S.grad_stage) S.grad_stage[a] = deaths(g, S.stage[a]);
+  }
+}
+
+}  // namespace gj

@@ -1,5 +1,5 @@
 // Device-side helpers shared by the gfx950 kernels: wave64 reductions, Philox4x32-10, the
-// per-agent Gumbel-softmax decision (a8) and the infection state update (a9).
+// per-agent Gumbel-softmax decision (a8), the infection state update (a9) and the transmission profile (a1).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -11,13 +11,16 @@ constexpr int kThreads = 256;      // 4 waves per workgroup: one per SIMD of a C
 constexpr int kEdgesPerThread = 8; // STREAM block = 2048 edges = GJ_STREAM_EDGES
 
 // Sum over the lanes of an aligned group of G lanes (G = 4, 16, 64); every lane gets the total
-// of ITS group.  Butterfly order: run-to-run deterministic.
-template <int G>
-__device__ __forceinline__ float group_sum(float v) {
+// of ITS group.  Butterfly order: run-to-run deterministic.  T: float, double or uint64_t.
+template <int G, typename T>
+__device__ __forceinline__ T group_sum(T v) {
 #pragma unroll
   for (int off = G / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
   return v;
 }
+// the whole wave: THE butterfly every wave-wide sum of the library goes through
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) { return group_sum<kWave>(v); }
 
 // ---- Philox4x32-10 (Salmon et al., SC'11), counter = (pair lo, pair hi, step lo, step hi), key = seed.
 // One call yields the two Exponential(1) draws of each agent of a pair (see exp_pair).
@@ -210,5 +213,72 @@ __device__ __forceinline__ float not_infected_prob(float ts, float dt) {
 }
 
 __device__ __forceinline__ float sgnf(float x) { return (float)((0.0f < x) - (x < 0.0f)); }
+
+// ---- a1: the transmission profile (reference grad_june/transmission.py:39-51) -----------------------------------
+// The profile's transcendental part, exp(-lgamma(shape)) * pow(x, shape - 1) * exp(e), costs ~690 instructions with
+// libm's lgammaf (~420) and powf (~200) - and a wave pays them for all 64 lanes whenever one lane holds an infected
+// agent, which made k_transmission arithmetic-bound at the 5-25 % prevalence of the timed steps.  Round 3:
+//   1 / Gamma(shape)  by the recurrence to [1, 2] and Abramowitz & Stegun 6.1.36 (degree 8, |eps| <= 3e-7 there; measured
+//                     3.5e-7 relative in fp32), libm only for shapes outside (0.25, 16);
+//   pow(x, y)         = exp2(y * log2(x)) on the hardware's v_log_f32 / v_exp_f32 (1 ulp each): the error of the
+//                     exponent, |y log2 x| * 2^-23, is ~1e-6 relative in the result; 0 / inf at x == 0 as powf; x < 0: NaN for a
+//                     non-integer y and +-|x|^y for an integer one, as powf / torch.pow;
+//   exp(e)            = exp2(e * log2(e)): ~|e| * 1e-7.
+// Together ~2e-6 relative against the reference's fp32 torch ops (themselves ~1e-7); the parity tests hold the
+// transmissions to 2e-5.  ~60 instructions.
+__device__ __forceinline__ float inv_gamma(float x) {
+  if (!(x > 0.25f && x < 16.0f)) return expf(-lgammaf(x));        // (also NaN)
+  float up = 1.0f, down = 1.0f;           // Gamma(x_in) = Gamma(x) * up / down
+  while (x > 2.0f) {
+    x -= 1.0f;
+    up *= x;
+  }
+  while (x < 1.0f) {
+    down *= x;
+    x += 1.0f;
+  }
+  const float z = x - 1.0f;
+  float g = 0.035868343f;
+  g = g * z - 0.193527818f;
+  g = g * z + 0.482199394f;
+  g = g * z - 0.756704078f;
+  g = g * z + 0.918206857f;
+  g = g * z - 0.897056937f;
+  g = g * z + 0.988205891f;
+  g = g * z - 0.577191652f;
+  g = g * z + 1.0f;                       // Gamma(1 + z), 0 <= z <= 1
+  return down / (g * up);
+}
+__device__ __forceinline__ float fast_pow(float x, float y) {
+  if (y == 0.0f) return 1.0f;             // powf(x, 0) == 1 for every x
+  if (x < 0.0f) {
+    // torch.pow / powf of a negative base: finite for an INTEGER exponent (sign by its parity), NaN otherwise.  A
+    // constant integer shape with t < shift is the case that matters (transmission.py:45-49: sign == 0 there, and
+    // 0 * finite == 0 where 0 * NaN would poison the venue sums).  Rare: not worth libm's powf in the
+    // instruction stream of a launch that lives on its occupancy.
+    const float yi = truncf(y);
+    if (yi != y) return __builtin_nanf("");
+    const float r = __builtin_amdgcn_exp2f(y * __builtin_amdgcn_logf(-x));
+    const float h = 0.5f * yi;
+    return (truncf(h) != h) ? -r : r;     // odd exponent: the base's sign survives
+  }
+  return __builtin_amdgcn_exp2f(y * __builtin_amdgcn_logf(x));      // v_exp_f32(y * v_log_f32(x))
+}
+__device__ __forceinline__ float fast_exp(float e) { return __builtin_amdgcn_exp2f(e * 1.44269504088896341f); }
+
+// The head of the profile, shared by the update and its adjoints (which must give the update's bits):
+// transmission = max_infectiousness * sign * aux * aux2 * is_infected, with t the time since infection and d = t - shift.
+struct ProfileHead {
+  float sign, aux, aux2, d, t;
+};
+__device__ __forceinline__ ProfileHead profile_head(float shp, float rt, float sh, float t_inf, float now) {
+  ProfileHead h;
+  h.t = now - t_inf;
+  h.d = h.t - sh;
+  h.sign = (sgnf(h.d + 1e-10f) + 1.0f) / 2.0f;
+  h.aux = inv_gamma(shp) * fast_pow(h.d * rt, shp - 1.0f);
+  h.aux2 = fast_exp((sh - h.t) * rt) * rt;
+  return h;
+}
 
 }  // namespace gj

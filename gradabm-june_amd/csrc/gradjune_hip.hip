@@ -18,6 +18,7 @@
 #include "../../include/gradjune_hip.h"
 #include "gj_device.h"
 #include "gj_tiled.h"
+#include "gj_agent.h"
 
 namespace gj {
 
@@ -84,65 +85,10 @@ struct P2Args {
 // a1 + a2   transmission profile and quarantine-masked copy
 //   reference: grad_june/transmission.py:39-51, grad_june/policies/quarantine_policies.py:13-33
 // ------------------------------------------------------------------------------------------
-// The profile's transcendental part, exp(-lgamma(shape)) * pow(x, shape - 1) * exp(e), costs ~690 instructions with
-// libm's lgammaf (~420) and powf (~200) - and a wave pays them for all 64 lanes whenever one lane holds an infected
-// agent, which made k_transmission arithmetic-bound at the 5-25 % prevalence of the timed steps.  Round 3:
-//   1 / Gamma(shape)  by the recurrence to [1, 2] and Abramowitz & Stegun 6.1.36 (degree 8, |eps| <= 3e-7 there; measured
-//                     3.5e-7 relative in fp32), libm only for shapes outside (0.25, 16);
-//   pow(x, y)         = exp2(y * log2(x)) on the hardware's v_log_f32 / v_exp_f32 (1 ulp each): the error of the
-//                     exponent, |y log2 x| * 2^-23, is ~1e-6 relative in the result; 0 / inf at x == 0 as powf; x < 0: NaN for a
-//                     non-integer y and +-|x|^y for an integer one, as powf / torch.pow;
-//   exp(e)            = exp2(e * log2(e)): ~|e| * 1e-7.
-// Together ~2e-6 relative against the reference's fp32 torch ops (themselves ~1e-7); the parity tests hold the
-// transmissions to 2e-5.  ~60 instructions.
-__device__ __forceinline__ float inv_gamma(float x) {
-  if (!(x > 0.25f && x < 16.0f)) return expf(-lgammaf(x));        // (also NaN)
-  float up = 1.0f, down = 1.0f;           // Gamma(x_in) = Gamma(x) * up / down
-  while (x > 2.0f) {
-    x -= 1.0f;
-    up *= x;
-  }
-  while (x < 1.0f) {
-    down *= x;
-    x += 1.0f;
-  }
-  const float z = x - 1.0f;
-  float g = 0.035868343f;
-  g = g * z - 0.193527818f;
-  g = g * z + 0.482199394f;
-  g = g * z - 0.756704078f;
-  g = g * z + 0.918206857f;
-  g = g * z - 0.897056937f;
-  g = g * z + 0.988205891f;
-  g = g * z - 0.577191652f;
-  g = g * z + 1.0f;                       // Gamma(1 + z), 0 <= z <= 1
-  return down / (g * up);
-}
-__device__ __forceinline__ float fast_pow(float x, float y) {
-  if (y == 0.0f) return 1.0f;             // powf(x, 0) == 1 for every x
-  if (x < 0.0f) {
-    // torch.pow / powf of a negative base: finite for an INTEGER exponent (sign by its parity), NaN otherwise.  A
-    // constant integer shape with t < shift is the case that matters (transmission.py:45-49: sign == 0 there, and
-    // 0 * finite == 0 where 0 * NaN would poison the venue sums).  Rare: not worth libm's powf in the
-    // instruction stream of a launch that lives on its occupancy.
-    const float yi = truncf(y);
-    if (yi != y) return __builtin_nanf("");
-    const float r = __builtin_amdgcn_exp2f(y * __builtin_amdgcn_logf(-x));
-    const float h = 0.5f * yi;
-    return (truncf(h) != h) ? -r : r;     // odd exponent: the base's sign survives
-  }
-  return __builtin_amdgcn_exp2f(y * __builtin_amdgcn_logf(x));      // v_exp_f32(y * v_log_f32(x))
-}
-__device__ __forceinline__ float fast_exp(float e) { return __builtin_amdgcn_exp2f(e * 1.44269504088896341f); }
-
 __device__ __forceinline__ float transmission_value(float mx, float shp, float rt, float sh, float t_inf,
                                                     float inf, float now) {
-  const float t = now - t_inf;
-  const float d = t - sh;
-  const float sign = (sgnf(d + 1e-10f) + 1.0f) / 2.0f;
-  const float aux = inv_gamma(shp) * fast_pow(d * rt, shp - 1.0f);
-  const float aux2 = fast_exp((sh - t) * rt) * rt;
-  return mx * sign * aux * aux2 * inf;
+  const ProfileHead h = profile_head(shp, rt, sh, t_inf, now);
+  return mx * h.sign * h.aux * h.aux2 * inf;
 }
 
 // (Round 3, measured and not adopted: listing a chunk's infected agents in LDS and evaluating them densely, one per
@@ -462,379 +408,6 @@ __global__ __launch_bounds__(kThreads) void k_sample_infect(int64_t n, const flo
   }
 }
 
-// f1: disease-stage progression (reference grad_june/symptoms.py:204-247, 82-128), one lane per agent
-struct SymptomsArgs {
-  gj_symptoms_params P;
-  int64_t n;
-  const uint8_t* cls;
-  const float* new_inf;
-  float* cur;
-  float* nxt;
-  float* ttn;
-  const float* progresses;
-  const float* dwell;
-};
-
-__device__ __forceinline__ float dwell_sample(int kind, float loc, float scale, float z) {
-  const float v = loc + scale * z;
-  return kind == 1 ? __builtin_amdgcn_exp2f(v * 1.44269504088896341f) : v;      // LogNormal: exp on v_exp_f32
-}
-// The library's own draw for an agent at stage s that is due (no reference stream to reproduce: symptoms.py:82-128 draws
-// torch.bernoulli + rsample): progress with the table's probability, dwell time = LogNormal / Normal of one Box-Muller
-// normal.  On the hardware's transcendental units (v_log_f32, v_sqrt_f32, v_cos_f32 - whose argument is in revolutions -
-// v_exp_f32): the draws of a wave's due agents were half of the fused symptoms launch with libm's logf / cosf / expf.
-// ONE definition, shared by the update and its adjoint (which must replay the same draw).
-__device__ __forceinline__ void stage_draw(const gj_symptoms_params& P, int64_t a, int s, int age, bool& onward, float& d) {
-  uint32_t r[4];
-  philox4x32_10((uint64_t)(P.agent_offset + a), P.step | (1ull << 63), P.seed, r);
-  onward = u01(r[0]) < P.progress[s * 100 + age];
-  const float ln_u = __builtin_amdgcn_logf(u01(r[1])) * 0.693147180559945309f;        // ln(u) = log2(u) * ln(2)
-  const float z = __builtin_amdgcn_sqrtf(-2.0f * ln_u) * __builtin_amdgcn_cosf(u01(r[2]));   // cos(2 pi u)
-  d = onward ? dwell_sample(P.next_kind[s], P.next_loc[s], P.next_scale[s], z)
-             : dwell_sample(P.rec_kind[s], P.rec_loc[s], P.rec_scale[s], z);
-}
-
-// One agent's stage update (symptoms.py:204-247, 82-128).  Returns true when any of the three values changed.
-__device__ __forceinline__ bool symptoms_agent(const SymptomsArgs& S, int64_t a, float nw, int cls, float& cur,
-                                               float& nx, float& tt) {
-  const int n_stages = S.P.n_stages;
-  const float time = S.P.time;
-  const float cur0 = cur, nx0 = nx, tt0 = tt;
-  nx = nx + nw * (2.0f - nx);                       // newly infected: next stage = exposed, due now
-  tt = tt + nw * (time - tt);
-  const bool moving = (time >= tt) && (cur < (float)(n_stages - 1));
-  cur = cur - (cur - nx) * (moving ? 1.0f : 0.0f);
-  int s = (int)cur;
-  s = min(max(s, 0), n_stages - 1);
-  const int age = cls % 100;
-  if (moving && s >= 2 && s <= n_stages - 2 && cur == (float)s) {
-    bool onward;
-    float d;
-    if (S.progresses) {
-      onward = S.progresses[a] != 0.0f;
-      d = S.dwell[a];
-    } else {
-      stage_draw(S.P, a, s, age, onward, d);
-    }
-    if (onward) {
-      nx = nx + 1.0f;
-    } else {
-      nx = nx - nx;
-    }
-    tt = tt + d;
-  }
-  // (bit comparison: a NaN that stays a NaN has not changed)
-  return __float_as_uint(cur) != __float_as_uint(cur0) || __float_as_uint(nx) != __float_as_uint(nx0) ||
-         __float_as_uint(tt) != __float_as_uint(tt0);
-}
-
-__global__ __launch_bounds__(kThreads) void k_symptoms(const SymptomsArgs S) {
-  const int64_t a = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (a >= S.n) return;
-  float cur = S.cur[a], nx = S.nxt[a], tt = S.ttn[a];
-  symptoms_agent(S, a, S.new_inf[a], (int)S.cls[a], cur, nx, tt);
-  S.cur[a] = cur;
-  S.nxt[a] = nx;
-  S.ttn[a] = tt;
-}
-
-// f3: adjoint of k_symptoms w.r.t. the stage values and new_infected (oracle/gj_oracle.py:adjoint_symptoms).
-// Recomputes the branch the agent took from the PRE-step state and the same randomness.
-struct SymptomsAdjointArgs {
-  gj_symptoms_params P;
-  int64_t n;
-  const uint8_t* cls;
-  const float* new_inf;
-  const float* cur0;
-  const float* nxt0;
-  const float* ttn0;
-  const float* progresses;
-  const float* dwell;
-  const float* g_cur;
-  const float* g_nxt;
-  const float* g_ttn;
-  float* g_cur_in;
-  float* g_nxt_in;
-  float* g_ttn_in;
-  float* g_new;
-};
-
-__global__ __launch_bounds__(kThreads) void k_adjoint_symptoms(const SymptomsAdjointArgs S) {
-  const int64_t a = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (a >= S.n) return;
-  const int n_stages = S.P.n_stages;
-  const float time = S.P.time;
-  const float nw = S.new_inf[a];
-  const float c0 = S.cur0[a], x0 = S.nxt0[a], t0 = S.ttn0[a];
-  const float x1 = x0 + nw * (2.0f - x0);
-  const float t1 = t0 + nw * (time - t0);
-  const bool moving = (time >= t1) && (c0 < (float)(n_stages - 1));
-  const float m = moving ? 1.0f : 0.0f;
-  const float c1 = c0 - (c0 - x1) * m;
-  int s = (int)c1;
-  s = min(max(s, 0), n_stages - 1);
-  float gc1 = S.g_cur ? S.g_cur[a] : 0.0f;
-  float gx1 = S.g_nxt ? S.g_nxt[a] : 0.0f;
-  const float gt1 = S.g_ttn ? S.g_ttn[a] : 0.0f;
-  if (moving && s >= 2 && s <= n_stages - 2 && c1 == (float)s) {
-    bool onward;
-    float d;
-    if (S.progresses) {
-      onward = S.progresses[a] != 0.0f;
-      d = S.dwell[a];
-    } else {
-      stage_draw(S.P, a, s, (int)(S.cls[a] % 100), onward, d);
-    }
-    gc1 += gt1 * d / (float)s;              // time += dwell * (current == s) * current / s  (either branch)
-    if (onward) {
-      gc1 += gx1 / (float)s;                // next += (current == s) * current / s
-    } else {
-      gc1 -= gx1 * x1 / (float)s;           // next -= next * (current == s) * current / s
-      gx1 = 0.0f;
-    }
-  }
-  gx1 += gc1 * m;                           // current -= (current - next) * moving
-  S.g_cur_in[a] = gc1 * (1.0f - m);
-  S.g_nxt_in[a] = gx1 * (1.0f - nw);        // next += new_infected * (2 - next)
-  if (S.g_ttn_in) S.g_ttn_in[a] = gt1 * (1.0f - nw);   // time += new_infected * (now - time)
-  S.g_new[a] = gx1 * (2.0f - x0) + gt1 * (time - t0);
-}
-
-// f3: elementwise adjoints (see include/gradjune_hip.h)
-__global__ __launch_bounds__(kThreads) void k_adjoint_sample(
-    int64_t n, const float* __restrict__ susc0, const float* __restrict__ time0, const float* __restrict__ acc,
-    const float* __restrict__ noise, uint64_t seed, uint64_t step, int64_t agent_offset, float now, float dt,
-    const float* __restrict__ g_susc, const float* __restrict__ g_inf, const float* __restrict__ g_time,
-    const float* __restrict__ g_new, float* __restrict__ x_out, float* __restrict__ grad_susc,
-    float* __restrict__ grad_time) {
-  const int64_t a = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (a >= n) return;
-  const float s0 = susc0[a];
-  const float ac = acc[a];
-  const float ts = s0 * ac;
-  const bool inside = (ts >= 1e-6f) && (ts <= 100.0f);
-  const float p = not_infected_prob(ts, dt);
-  const float gs = g_susc ? g_susc[a] : 0.0f, gi = g_inf ? g_inf[a] : 0.0f, gt = g_time ? g_time[a] : 0.0f;
-  const float gn = g_new ? g_new[a] : 0.0f;
-  float e0, e1;
-  sampler_draws(noise, n, a, seed, step, agent_offset, e0, e1);
-  float y0, y1;
-  sampler_softmax<float>(p, e0, e1, y0, y1);
-  const float nu = sampler_decision(p, noise != nullptr, y0, y1, seed, step, agent_offset + a);
-  const SampleAdjoint<float> r = sample_adjoint<float>(p, s0, time0[a], y0, y1, nu, now, gs, gi, gt, gn);
-  const float ts_bar = inside ? r.nu_bar * r.dnu_dp * (-dt * p) : 0.0f;
-  x_out[a] = s0 * ts_bar;
-  grad_susc[a] = gs * r.h + ts_bar * ac;
-  grad_time[a] = gt * (1.0f - nu);
-}
-
-// f3, the seed: adjoint of sampling with one probability per agent group followed by infect_people (include/gradjune_hip.h,
-// gj_adjoint_seed).  Three launches.  (1) one lane per agent: the per-agent term c_a = -nu_bar * d nu / d p of
-// d loss / d fraction[group[a]] (in fp64 from the fp32 inputs, into a workspace) and the elementwise outputs.
-struct SeedAdjArgs {
-  int64_t n;
-  const float* p_not;       // [n_groups]
-  const int32_t* group;     // [n] or NULL (every agent in group 0)
-  int32_t n_groups;
-  const float* susc0;
-  const float* time0;
-  const float* noise;
-  uint64_t seed, step;
-  int64_t agent_offset;
-  float now;
-  const float* g_susc;
-  const float* g_inf;
-  const float* g_time;
-  const float* g_new;
-  double* contrib;          // [n]
-  float* grad_susc;         // [n] or NULL
-  float* grad_time;         // [n] or NULL
-};
-
-__global__ __launch_bounds__(kThreads) void k_adjoint_seed_agents(const SeedAdjArgs S) {
-  const int64_t a = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (a >= S.n) return;
-  const int32_t g = S.group ? S.group[a] : 0;
-  const float s0 = S.susc0[a];
-  const float gs = S.g_susc ? S.g_susc[a] : 0.0f, gt = S.g_time ? S.g_time[a] : 0.0f;
-  if ((uint32_t)g >= (uint32_t)S.n_groups) {   // no group: not seeded (nu = 0), no term; the label is not an index
-    S.contrib[a] = 0.0;
-    if (S.grad_susc) S.grad_susc[a] = gs * ((s0 > 0.0f) ? 1.0f : ((s0 == 0.0f) ? 0.5f : 0.0f));
-    if (S.grad_time) S.grad_time[a] = gt;
-    return;
-  }
-  const float gi = S.g_inf ? S.g_inf[a] : 0.0f, gn = S.g_new ? S.g_new[a] : 0.0f;
-  const float p = S.p_not[g];
-  double e0, e1;                                                // (injected draws: the fp32 values; the library's own:
-  sampler_draws(S.noise, S.n, a, S.seed, S.step, S.agent_offset, e0, e1);   //  exp_pair's products taken in fp64)
-  float y0f = 0.0f, y1f = 0.0f;                                 // the decision is the forward's: taken in its arithmetic
-  if (S.noise) sampler_softmax<float>(p, (float)e0, (float)e1, y0f, y1f);
-  const float nu = sampler_decision(p, S.noise != nullptr, y0f, y1f, S.seed, S.step, S.agent_offset + a);
-  double y0, y1;
-  sampler_softmax<double>(p, e0, e1, y0, y1);
-  const SampleAdjoint<double> r = sample_adjoint<double>(p, s0, S.time0[a], y0, y1, nu, S.now, gs, gi, gt, gn);
-  S.contrib[a] = -(r.nu_bar * r.dnu_dp);       // d fraction = -d p
-  if (S.grad_susc) S.grad_susc[a] = gs * (float)r.h;
-  if (S.grad_time) S.grad_time[a] = gt * (1.0f - nu);
-}
-
-// (2) one WAVE per (group, chunk): the chunk's <= GJ_SEED_CHUNK terms, read through the label-sorted agent list, are
-// added in fp64 - every lane its terms in list order, then the lanes by a butterfly - and written as partial[chunk].
-// (3) one wave per group adds its chunks' partials the same way.  No atomics: the order of every sum is a function of
-// the labels alone, so two launches give the same bits.  Every index read from the tables is checked before use.
-struct SeedSumArgs {
-  int64_t n, n_sorted, n_chunks;
-  int32_t n_groups;
-  const double* contrib;
-  const int64_t* order;        // [n_sorted] or NULL (identity)
-  const int64_t* seg_offsets;  // [n_groups + 1] or NULL ({0, n})
-  const int64_t* chunk_first;  // [n_groups + 1] or NULL ({0, n_chunks})
-  const int32_t* chunk_group;  // [n_chunks] or NULL (0)
-  double* partial;             // [n_chunks]
-  double* out;                 // [n_groups]
-};
-
-__device__ __forceinline__ double wave_sum_f64(double x) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) x += __shfl_xor(x, off, kWave);
-  return x;
-}
-
-__global__ __launch_bounds__(kThreads) void k_adjoint_seed_chunks(const SeedSumArgs S) {
-  const int64_t c = (int64_t)blockIdx.x * (kThreads / kWave) + threadIdx.x / kWave;
-  const int lane = threadIdx.x % kWave;
-  if (c >= S.n_chunks) return;                 // (whole waves leave: the shuffles below see full waves)
-  const int32_t g = S.chunk_group ? S.chunk_group[c] : 0;
-  double acc = 0.0;
-  if ((uint32_t)g < (uint32_t)S.n_groups) {
-    const int64_t k = c - (S.chunk_first ? S.chunk_first[g] : 0);
-    const int64_t s0 = S.seg_offsets ? S.seg_offsets[g] : 0, s1 = S.seg_offsets ? S.seg_offsets[g + 1] : S.n;
-    if (k >= 0 && s0 >= 0 && k <= (S.n_sorted - s0) / GJ_SEED_CHUNK) {
-      const int64_t begin = s0 + k * GJ_SEED_CHUNK;
-      int64_t end = begin + GJ_SEED_CHUNK;
-      if (end > s1) end = s1;
-      if (end > S.n_sorted) end = S.n_sorted;
-      for (int64_t j = begin + lane; j < end; j += kWave) {
-        const int64_t a = S.order ? S.order[j] : j;
-        if ((uint64_t)a < (uint64_t)S.n) acc += S.contrib[a];
-      }
-    }
-  }
-  acc = wave_sum_f64(acc);
-  if (lane == 0) S.partial[c] = acc;
-}
-
-__global__ __launch_bounds__(kThreads) void k_adjoint_seed_finish(const SeedSumArgs S) {
-  const int64_t g = (int64_t)blockIdx.x * (kThreads / kWave) + threadIdx.x / kWave;
-  const int lane = threadIdx.x % kWave;
-  if (g >= S.n_groups) return;
-  int64_t c0 = S.chunk_first ? S.chunk_first[g] : 0, c1 = S.chunk_first ? S.chunk_first[g + 1] : S.n_chunks;
-  if (c0 < 0) c0 = 0;
-  if (c1 > S.n_chunks) c1 = S.n_chunks;
-  double acc = 0.0;
-  for (int64_t c = c0 + lane; c < c1; c += kWave) acc += S.partial[c];
-  acc = wave_sum_f64(acc);
-  if (lane == 0) S.out[g] = acc;
-}
-
-__global__ __launch_bounds__(kThreads) void k_adjoint_transmission(
-    int64_t n, const float* __restrict__ mx, const float* __restrict__ shp, const float* __restrict__ rt,
-    const float* __restrict__ sh, const float* __restrict__ time0, const float* __restrict__ inf0, float now,
-    const float* __restrict__ trans_bar, const float* __restrict__ g_inf, float* __restrict__ grad_inf,
-    float* __restrict__ grad_time) {
-  const int64_t a = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (a >= n) return;
-  const float tb = trans_bar[a];
-  const float t = now - time0[a];
-  const float d = t - sh[a];
-  const float sign = (sgnf(d + 1e-10f) + 1.0f) / 2.0f;
-  const float aux = inv_gamma(shp[a]) * fast_pow(d * rt[a], shp[a] - 1.0f);
-  const float aux2 = fast_exp((sh[a] - t) * rt[a]) * rt[a];
-  const float base = mx[a] * sign * aux * aux2;              // d trans / d is_infected
-  const float inf = inf0[a];
-  float dtdt = 0.0f;                                         // d trans / d t
-  if (inf != 0.0f) dtdt = base * inf * ((shp[a] - 1.0f) / d - rt[a]);
-  grad_inf[a] = (g_inf ? g_inf[a] : 0.0f) + tb * base;
-  grad_time[a] = grad_time[a] - tb * dtdt;                   // d t / d infection_time = -1
-}
-
-// psi(x) = d lgamma / dx (torch.digamma, the derivative torch's autograd gives lgamma), for the adjoint of the profile's
-// 1 / Gamma(shape).  x < 0: reflection psi(x) = psi(1 - x) - pi / tan(pi x), NaN at the poles; x == 0: -inf (torch:
-// copysign(inf, -x)).  x > 0: the recurrence psi(x) = psi(x + 1) - 1/x up to x >= 6, then the asymptotic series to
-// x^-6 (truncation: next term 1/(240 x^8) < 2.6e-9 there).  The error is that of fp32 rounding of the sum: a few ulp
-// of the largest term, i.e. ~1e-6 absolute for x >= 0.25 and a few ulp of 1/x below (x = 0.02: psi ~ -50, ~1e-5) -
-// over inv_gamma's fast range (0.25, 16) and its libm fallback range alike.  NaN in, NaN out.  No libm: v_log_f32
-// and (x < 0 only) v_sin/v_cos.
-__device__ __forceinline__ float digamma(float x) {
-  if (x == 0.0f) return copysignf(__builtin_inff(), -x);
-  float refl = 0.0f;
-  if (x < 0.0f) {
-    const float r = x - truncf(x);                     // (-1, 0]; tan(pi x) = tan(pi r)
-    if (r == 0.0f) return __builtin_nanf("");          // negative integer: a pole
-    // v_sin_f32 / v_cos_f32 take revolutions: sin(pi r) = sin(2 pi * r / 2)
-    refl = 3.14159265358979f * __builtin_amdgcn_cosf(0.5f * r) / __builtin_amdgcn_sinf(0.5f * r);
-    x = 1.0f - x;
-  }
-  float acc = 0.0f;
-  while (x < 6.0f) {                                   // (false for NaN)
-    acc += 1.0f / x;
-    x += 1.0f;
-  }
-  const float ix = 1.0f / x, ix2 = ix * ix;
-  float s = ix2 * (1.0f / 252.0f);
-  s = ix2 * (1.0f / 120.0f - s);
-  s = ix2 * (1.0f / 12.0f - s);
-  const float lnx = __builtin_amdgcn_logf(x) * 0.693147180559945309f;
-  return lnx - 0.5f * ix - s - acc - refl;
-}
-
-// The profile's adjoint w.r.t. its own per-agent parameters, on top of what k_adjoint_transmission computes (the same
-// grad_inf / grad_time, bit for bit).  With T the profile, d = t - shift, u = d * rate:
-//   dT/d max_inf = sign * aux * aux2 * is_infected   (not T / max_inf: max_inf == 0 is allowed)
-//   dT/d shape   = T * (ln u - psi(shape))           (torch: pow'(exponent) = pow * ln(base), masked to 0 at base == 0
-//                                                     with exponent >= 0; lgamma' = digamma)
-//   dT/d rate    = T * (shape / rate - d)
-//   dT/d shift   = T * (rate - (shape - 1) / d)      (= -dT/dt: the infection_time term shares it)
-// Each NULL output is neither computed nor written: a launch moves bytes only for the parameters that need a gradient.
-// is_infected == 0 gives 0 in every output.  (25 VGPRs, 0 scratch, occupancy 8: hipcc --offload-arch=gfx950
-// -O3 -ffp-contract=off -Rpass-analysis=kernel-resource-usage, the `resources` target of csrc/Makefile.)
-__global__ __launch_bounds__(kThreads) void k_adjoint_transmission_params(
-    int64_t n, const float* __restrict__ mx, const float* __restrict__ shp, const float* __restrict__ rt,
-    const float* __restrict__ sh, const float* __restrict__ time0, const float* __restrict__ inf0, float now,
-    const float* __restrict__ trans_bar, const float* __restrict__ g_inf, float* __restrict__ grad_inf,
-    float* __restrict__ grad_time, float* __restrict__ grad_mx, float* __restrict__ grad_shp,
-    float* __restrict__ grad_rt, float* __restrict__ grad_sh) {
-  const int64_t a = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (a >= n) return;
-  const float tb = trans_bar[a];
-  const float s = shp[a], r = rt[a];
-  const float t = now - time0[a];
-  const float d = t - sh[a];
-  const float sign = (sgnf(d + 1e-10f) + 1.0f) / 2.0f;
-  const float aux = inv_gamma(s) * fast_pow(d * r, s - 1.0f);
-  const float aux2 = fast_exp((sh[a] - t) * r) * r;
-  const float base = mx[a] * sign * aux * aux2;              // d trans / d is_infected
-  const float inf = inf0[a];
-  float p_mx = 0.0f, p_shp = 0.0f, p_rt = 0.0f, dtdt = 0.0f;  // d trans / d parameter; d trans / d t = -dT/d shift
-  if (inf != 0.0f) {
-    const float T = base * inf;
-    dtdt = T * ((s - 1.0f) / d - r);                         // (k_adjoint_transmission's op sequence)
-    if (grad_mx) p_mx = sign * aux * aux2 * inf;
-    if (grad_shp) {
-      const float u = d * r;
-      const float lnu = (u == 0.0f && s >= 1.0f) ? 0.0f : __builtin_amdgcn_logf(u) * 0.693147180559945309f;
-      p_shp = T * lnu - T * digamma(s);
-    }
-    if (grad_rt) p_rt = T * (s / r - d);
-  }
-  grad_inf[a] = (g_inf ? g_inf[a] : 0.0f) + tb * base;
-  grad_time[a] = grad_time[a] - tb * dtdt;                   // d t / d infection_time = -1
-  if (grad_mx) grad_mx[a] = tb * p_mx;
-  if (grad_shp) grad_shp[a] = tb * p_shp;
-  if (grad_rt) grad_rt[a] = tb * p_rt;
-  if (grad_sh) grad_sh[a] = 0.0f - tb * dtdt;               // (0 - x: no -0 for the uninfected)
-}
-
 // f3: d loss / d log_beta of the networks on one edge set (include/gradjune_hip.h, gj_adjoint_beta_*)
 struct AdjBetaArgs {
   int64_t n_venues;
@@ -888,8 +461,7 @@ __global__ __launch_bounds__(kAdjBetaThreads) void k_adjoint_beta_partial(const 
   const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
 #pragma unroll
   for (int k = 0; k < GJ_MAX_NETS_PER_SET; ++k) {
-    double x = acc[k];
-    for (int off = kWave / 2; off > 0; off >>= 1) x += __shfl_xor(x, off, kWave);
+    const double x = wave_sum(acc[k]);
     if (lane == 0) part[wave][k] = x;
   }
   __syncthreads();
@@ -906,329 +478,6 @@ __global__ void k_adjoint_beta_finish(int32_t n_cols, const double* partial, con
   double x = 0.0;
   for (int b = 0; b < GJ_ADJ_BETA_BLOCKS; ++b) x += partial[(int64_t)b * GJ_MAX_NETS + c];
   out[c] = x * (double)(*scale) * 2.302585092994046;      // ln(10)
-}
-
-// f2: per-step result reductions (reference grad_june/runner.py:167,198-224), one streaming pass
-struct StatsArgs {
-  int64_t n;
-  const uint8_t* cls;
-  const float* inf;
-  const float* stage;
-  int32_t n_bins;
-  int32_t edges[GJ_MAX_AGE_BINS + 1];
-  int32_t dead;
-  int32_t vec4;     // all three arrays 16-byte (cls: 4-byte) aligned
-  double* out;
-};
-
-__global__ __launch_bounds__(kThreads) void k_step_stats(const StatsArgs S) {
-  constexpr int kOut = GJ_MAX_AGE_BINS + 2;
-  __shared__ double part[kThreads / kWave][kOut];
-  double acc[kOut];
-#pragma unroll
-  for (int k = 0; k < kOut; ++k) acc[k] = 0.0;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  auto take = [&](float inf, float stage, int cls) {
-    const int age = cls % 100;
-    acc[0] += inf;
-#pragma unroll
-    for (int b = 0; b < GJ_MAX_AGE_BINS; ++b)
-      if (b < S.n_bins && age > S.edges[b] && age < S.edges[b + 1]) acc[1 + b] += inf;
-    if (stage == (float)S.dead) acc[GJ_MAX_AGE_BINS + 1] += 1.0;
-  };
-  int64_t first_scalar = 0;
-  if (S.vec4) {   // 16-byte aligned arrays: four agents per lane and load (the scalar form is latency-bound)
-    const int64_t n4 = S.n >> 2;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-      const float4 f = reinterpret_cast<const float4*>(S.inf)[i];
-      const float4 g = reinterpret_cast<const float4*>(S.stage)[i];
-      const uint32_t c = reinterpret_cast<const uint32_t*>(S.cls)[i];
-      take(f.x, g.x, (int)(c & 0xFF));
-      take(f.y, g.y, (int)((c >> 8) & 0xFF));
-      take(f.z, g.z, (int)((c >> 16) & 0xFF));
-      take(f.w, g.w, (int)(c >> 24));
-    }
-    first_scalar = n4 << 2;
-  }
-  for (int64_t a = first_scalar + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; a < S.n; a += stride)
-    take(S.inf[a], S.stage[a], (int)S.cls[a]);
-  const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
-#pragma unroll
-  for (int k = 0; k < kOut; ++k) {
-    double v = acc[k];
-    for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
-    if (lane == 0) part[wave][k] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < kOut) {
-    double v = 0.0;
-    for (int w = 0; w < kThreads / kWave; ++w) v += part[w][threadIdx.x];
-    const int k = threadIdx.x;
-    int dst = -1;
-    if (k == 0) dst = 0;
-    else if (k <= GJ_MAX_AGE_BINS) dst = (k - 1 < S.n_bins) ? k : -1;
-    else dst = 1 + S.n_bins;
-    if (dst >= 0 && v != 0.0) atomicAdd(&S.out[dst], v);
-  }
-}
-
-// f1 + f2 in one pass (gj_symptoms_step_stats): the stage update of four agents per lane, written back only where a
-// value changed (early in an epidemic almost nobody moves: the three arrays are then read, not rewritten), and the
-// Runner's reductions taken from the registers that hold the updated stages.
-__global__ __launch_bounds__(kThreads) void k_symptoms_stats(const SymptomsArgs S, const StatsArgs R) {
-  constexpr int kOut = GJ_MAX_AGE_BINS + 2;
-  __shared__ double part[kThreads / kWave][kOut];
-  double acc[kOut];
-#pragma unroll
-  for (int k = 0; k < kOut; ++k) acc[k] = 0.0;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  auto take = [&](float inf, float stage, int cls) {
-    const int age = cls % 100;
-    acc[0] += inf;
-#pragma unroll
-    for (int b = 0; b < GJ_MAX_AGE_BINS; ++b)
-      if (b < R.n_bins && age > R.edges[b] && age < R.edges[b + 1]) acc[1 + b] += inf;
-    if (stage == (float)R.dead) acc[GJ_MAX_AGE_BINS + 1] += 1.0;
-  };
-  int64_t first_scalar = 0;
-  if (R.vec4) {
-    const int64_t n4 = S.n >> 2;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-      // all six loads issued before the first use
-      const float4 nw = reinterpret_cast<const float4*>(S.new_inf)[i];
-      float4 c = reinterpret_cast<const float4*>(S.cur)[i];
-      float4 x = reinterpret_cast<const float4*>(S.nxt)[i];
-      float4 t = reinterpret_cast<const float4*>(S.ttn)[i];
-      const float4 f = reinterpret_cast<const float4*>(R.inf)[i];
-      const uint32_t cl = reinterpret_cast<const uint32_t*>(S.cls)[i];
-      bool ch = symptoms_agent(S, 4 * i, nw.x, (int)(cl & 0xFF), c.x, x.x, t.x);
-      ch |= symptoms_agent(S, 4 * i + 1, nw.y, (int)((cl >> 8) & 0xFF), c.y, x.y, t.y);
-      ch |= symptoms_agent(S, 4 * i + 2, nw.z, (int)((cl >> 16) & 0xFF), c.z, x.z, t.z);
-      ch |= symptoms_agent(S, 4 * i + 3, nw.w, (int)(cl >> 24), c.w, x.w, t.w);
-      if (ch) {
-        reinterpret_cast<float4*>(S.cur)[i] = c;
-        reinterpret_cast<float4*>(S.nxt)[i] = x;
-        reinterpret_cast<float4*>(S.ttn)[i] = t;
-      }
-      take(f.x, c.x, (int)(cl & 0xFF));
-      take(f.y, c.y, (int)((cl >> 8) & 0xFF));
-      take(f.z, c.z, (int)((cl >> 16) & 0xFF));
-      take(f.w, c.w, (int)(cl >> 24));
-    }
-    first_scalar = n4 << 2;
-  }
-  for (int64_t a = first_scalar + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; a < S.n; a += stride) {
-    float cur = S.cur[a], nx = S.nxt[a], tt = S.ttn[a];
-    const int cls = (int)S.cls[a];
-    if (symptoms_agent(S, a, S.new_inf[a], cls, cur, nx, tt)) {
-      S.cur[a] = cur;
-      S.nxt[a] = nx;
-      S.ttn[a] = tt;
-    }
-    take(R.inf[a], cur, cls);
-  }
-  const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
-#pragma unroll
-  for (int k = 0; k < kOut; ++k) {
-    double v = acc[k];
-    for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
-    if (lane == 0) part[wave][k] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < kOut) {
-    double v = 0.0;
-    for (int w = 0; w < kThreads / kWave; ++w) v += part[w][threadIdx.x];
-    const int k = threadIdx.x;
-    int dst = -1;
-    if (k == 0) dst = 0;
-    else if (k <= GJ_MAX_AGE_BINS) dst = (k - 1 < R.n_bins) ? k : -1;
-    else dst = 1 + R.n_bins;
-    if (dst >= 0 && v != 0.0) atomicAdd(&R.out[dst], v);
-  }
-}
-
-// f2 by agent group (gj_group_stats): segmented sums of is_infected and of the deaths indicator over an int32 label.
-// Summed as 64-bit integers (is_infected in 32.32 fixed point, deaths as a count), so every order of the additions
-// gives the same bits.  Each lane carries ONE open run (label, two sums) across its agents; a run is closed when the
-// lane meets another label.  Closing is done by the whole wave: the lanes that close the same label fold their sums
-// with shuffles and one of them adds (two rounds, which is what a wave that straddles a boundary of sorted labels
-// needs; lanes still open after them add on their own).  LDS = true: the adds go to this workgroup's histogram in LDS,
-// which is added to the workspace at the end, one global atomic per non-zero accumulator.  LDS = false: the adds are
-// global atomics on the workspace.  A workgroup owns a CONTIGUOUS share of the agents, so that sorted labels give it
-// few groups.
-constexpr int kGroupFxBits = 32;
-constexpr int kGroupLdsMax = 4096;       // 2 * 8 B * 4096 = 64 KiB of LDS per workgroup: two workgroups per CU
-constexpr int kGroupLdsThreads = 1024, kGroupLdsBlocks = 512;
-constexpr int kGroupAdjLdsMax = 2048;    // gj_adjoint_group_stats stages 2 * 4 B * 2048 = 16 KiB per workgroup (above
-                                         // that, filling the copy costs more than the gathers it saves)
-constexpr uint32_t kGroupBadLabel = 1u, kGroupBadValue = 2u;    // GJ_GROUP_ERR_LABEL / GJ_GROUP_ERR_VALUE
-
-struct GroupArgs {
-  int64_t n;
-  const int32_t* group;
-  const float* inf;
-  const float* stage;
-  int32_t n_groups;
-  int32_t dead;
-  int32_t vec4;     // all three arrays 16-byte aligned
-  fx_t* ws;         // [2 * n_groups] sums, then the error word
-};
-
-__device__ __forceinline__ fx_t wave_sum_u64(fx_t v) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
-  return v;
-}
-
-template <bool LDS>
-__global__ __launch_bounds__(LDS ? kGroupLdsThreads : kThreads) void k_group_stats(const GroupArgs S) {
-  extern __shared__ fx_t hist[];     // LDS: [2 * n_groups]
-  const int G = S.n_groups;
-  if (LDS) {
-    for (int i = threadIdx.x; i < 2 * G; i += blockDim.x) hist[i] = 0;
-    __syncthreads();
-  }
-  const int lane = threadIdx.x % kWave;
-  int run = -1;            // label of this lane's open run
-  fx_t rc = 0, rd = 0;     // its sums: cases (fixed point), deaths (count)
-  uint32_t err = 0;
-  auto add = [&](int g, fx_t c, fx_t d) {
-    fx_t* dst = LDS ? hist : S.ws;
-    if (c) atomicAdd(&dst[g], c);
-    if (d) atomicAdd(&dst[G + g], d);
-  };
-  // wave-convergent: closes the run of every lane with `closing` set
-  auto close_runs = [&](bool closing) {
-    closing = closing && run >= 0;
-#pragma unroll 1
-    for (int round = 0; round < 2; ++round) {
-      const unsigned long long m = __ballot(closing);
-      if (m == 0) return;
-      const int leader = __ffsll((long long)m) - 1;
-      const int label = __shfl(run, leader, kWave);
-      const bool mine = closing && run == label;
-      const fx_t c = wave_sum_u64(mine ? rc : 0), d = wave_sum_u64(mine ? rd : 0);
-      if (lane == leader) add(label, c, d);
-      if (mine) closing = false, run = -1, rc = 0, rd = 0;
-    }
-    if (closing) add(run, rc, rd), run = -1, rc = 0, rd = 0;
-  };
-  // wave-convergent: one agent per lane (`on` = this lane has one)
-  auto take = [&](bool on, int g, float inf, float stage) {
-    if (on && (uint32_t)g >= (uint32_t)G) err |= kGroupBadLabel, on = false;   // never an index: the agent is skipped
-    const bool differs = on && g != run;
-    if (__any(differs && run >= 0)) close_runs(differs);
-    if (!on) return;
-    run = g;
-    const bool ok = fabsf(inf) <= fx_max<kGroupFxBits>();      // false for NaN too
-    if (!ok) err |= kGroupBadValue;
-    rc += to_fx<kGroupFxBits>(ok ? inf : 0.0f);
-    rd += (stage == (float)S.dead) ? 1u : 0u;
-  };
-  // this workgroup's share, in units of four agents (vec4) or of one
-  const int64_t units = S.vec4 ? (S.n >> 2) : S.n;
-  const int64_t per = (units + gridDim.x - 1) / gridDim.x;
-  const int64_t u0 = (int64_t)blockIdx.x * per, u1 = (u0 + per < units) ? u0 + per : units;
-  for (int64_t base = u0; base < u1; base += blockDim.x) {     // (the same trip count for every lane of a wave)
-    const int64_t i = base + threadIdx.x;
-    const bool on = i < u1;
-    if (S.vec4) {
-      int4 g = make_int4(0, 0, 0, 0);
-      float4 f = make_float4(0.f, 0.f, 0.f, 0.f), s = f;
-      if (on) {
-        g = reinterpret_cast<const int4*>(S.group)[i];
-        f = reinterpret_cast<const float4*>(S.inf)[i];
-        s = reinterpret_cast<const float4*>(S.stage)[i];
-      }
-      take(on, g.x, f.x, s.x);
-      take(on, g.y, f.y, s.y);
-      take(on, g.z, f.z, s.z);
-      take(on, g.w, f.w, s.w);
-    } else {
-      take(on, on ? S.group[i] : 0, on ? S.inf[i] : 0.f, on ? S.stage[i] : 0.f);
-    }
-  }
-  if (S.vec4 && blockIdx.x == gridDim.x - 1 && threadIdx.x < kWave) {     // the n % 4 agents behind the last float4
-    const int64_t a = (units << 2) + threadIdx.x;
-    const bool on = a < S.n;
-    take(on, on ? S.group[a] : 0, on ? S.inf[a] : 0.f, on ? S.stage[a] : 0.f);
-  }
-  close_runs(true);
-  if (err) atomicOr(reinterpret_cast<uint32_t*>(S.ws + 2 * (int64_t)G), err);
-  if (LDS) {
-    __syncthreads();
-    for (int i = threadIdx.x; i < 2 * G; i += blockDim.x) {
-      const fx_t v = hist[i];
-      if (v) atomicAdd(&S.ws[i], v);
-    }
-  }
-}
-
-// out += the sums as doubles (once, so the rounding does not depend on any order); the sums are zeroed for the next call
-__global__ __launch_bounds__(kThreads) void k_group_finish(int32_t n_groups, fx_t* ws, double* out) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= 2 * (int64_t)n_groups) return;
-  const fx_t v = ws[i];
-  if (v == 0) return;
-  ws[i] = 0;
-  out[i] += (i < n_groups) ? (double)(long long)v * (1.0 / (double)(1ull << kGroupFxBits)) : (double)v;
-}
-
-// adjoint of gj_group_stats: a gather through the labels
-struct GroupAdjArgs {
-  int64_t n;
-  const int32_t* group;
-  const float* stage;
-  const float* g_cases;
-  const float* g_deaths;
-  float* grad_inf;
-  float* grad_stage;
-  int32_t n_groups;
-  int32_t dead;
-  int32_t vec4;
-};
-
-template <bool LDS>
-__global__ __launch_bounds__(kThreads) void k_adjoint_group_stats(const GroupAdjArgs S) {
-  extern __shared__ float staged[];     // LDS: g_cases [n_groups], g_deaths [n_groups]
-  const int G = S.n_groups;
-  const float* gc = S.g_cases;
-  const float* gd = S.g_deaths;
-  if (LDS) {
-    for (int i = threadIdx.x; i < G; i += blockDim.x) {
-      staged[i] = gc ? gc[i] : 0.0f;
-      staged[G + i] = gd ? gd[i] : 0.0f;
-    }
-    __syncthreads();
-    gc = staged;
-    gd = staged + G;
-  }
-  const float dead = (float)S.dead;
-  auto cases = [&](int g) { return ((uint32_t)g < (uint32_t)G && gc) ? gc[g] : 0.0f; };
-  auto deaths = [&](int g, float st) {      // autograd of (stage == dead) * stage / dead: (g / dead) * mask
-    const float v = ((uint32_t)g < (uint32_t)G && gd) ? gd[g] : 0.0f;
-    return v / dead * (st == dead ? 1.0f : 0.0f);
-  };
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  int64_t first_scalar = 0;
-  if (S.vec4) {
-    const int64_t n4 = S.n >> 2;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-      const int4 g = reinterpret_cast<const int4*>(S.group)[i];
-      if (S.grad_inf) reinterpret_cast<float4*>(S.grad_inf)[i] = make_float4(cases(g.x), cases(g.y), cases(g.z), cases(g.w));
-      if (S.grad_stage) {
-        const float4 s = reinterpret_cast<const float4*>(S.stage)[i];
-        reinterpret_cast<float4*>(S.grad_stage)[i] =
-            make_float4(deaths(g.x, s.x), deaths(g.y, s.y), deaths(g.z, s.z), deaths(g.w, s.w));
-      }
-    }
-    first_scalar = n4 << 2;
-  }
-  for (int64_t a = first_scalar + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; a < S.n; a += stride) {
-    const int g = S.group[a];
-    if (S.grad_inf) S.grad_inf[a] = cases(g);
-    if (S.grad_stage) S.grad_stage[a] = deaths(g, S.stage[a]);
-  }
 }
 
 // a2 alone: q*transmission for a caller-supplied transmission vector
@@ -1257,6 +506,25 @@ __global__ __launch_bounds__(kThreads) void k_unpack(int64_t n, const int32_t* _
 static inline int launch_status() {
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? GJ_OK : (int)e;
+}
+
+template <typename K, typename... Args>
+static int launch(K kernel, int64_t blocks, int threads, size_t lds, hipStream_t stream, const Args&... args) {
+  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3((unsigned)threads), lds, stream, args...);
+  return launch_status();
+}
+
+// workgroups for n items at `per_block` items each (one lane per item: kThreads): at least one, at most `cap` (0: no cap)
+static inline int64_t grid_for(int64_t n, int64_t cap = 0, int per_block = kThreads) {
+  int64_t blocks = (n + per_block - 1) / per_block;
+  if (cap > 0 && blocks > cap) blocks = cap;
+  return blocks < 1 ? 1 : blocks;
+}
+
+// every pointer 16-byte aligned (NULL counts as aligned): what selects a kernel's four-agents-per-lane path
+template <typename... P>
+static inline bool aligned16(const P*... p) {
+  return ((... | (uintptr_t)p) % 16) == 0;
 }
 
 static int check_tiled(const gj_plan* plan);
@@ -1322,6 +590,49 @@ static int group_networks(const gj_plan* plan, const gj_step_params* p, Groups* 
   return GJ_OK;
 }
 
+// The networks of group g as every kernel argument block takes them.  Entries past nk are 0.
+struct NetGroup {
+  int32_t nk;
+  int32_t raw;                               // the set's transmissions are the raw ones (household), not q * transmission
+  int32_t leisure;                           // any network of the set uses a table
+  float beta[GJ_MAX_NETS_PER_SET];
+  int32_t mask[GJ_MAX_NETS_PER_SET];
+  int32_t table[GJ_MAX_NETS_PER_SET];        // -1: no leisure table
+  int32_t age75[GJ_MAX_NETS_PER_SET];
+};
+
+// (RAW and masked kinds cannot mix on a set - group_networks - so the first network decides)
+static inline bool group_is_raw(const gj_step_params* p, const Groups& G, int g) {
+  return p->nets[G.first[g]].mask_kind == GJ_MASK_RAW;
+}
+
+static NetGroup classify_group(const gj_step_params* p, const Groups& G, int g) {
+  NetGroup C = {};
+  C.nk = G.nk[g];
+  C.raw = group_is_raw(p, G, g);
+  for (int k = 0; k < C.nk; ++k) {
+    const gj_network& N = p->nets[G.first[g] + k];
+    const bool tabled = N.mask_kind >= GJ_MASK_QL;
+    C.beta[k] = N.beta;
+    C.mask[k] = N.mask_kind;
+    C.table[k] = tabled ? N.table : -1;
+    C.age75[k] = N.mask_kind == GJ_MASK_QL_AGE75;
+    if (tabled) C.leisure = 1;
+  }
+  return C;
+}
+
+// a set either is a leisure set (every network has a table) or, where the kernel needs it, has exactly one network
+static int check_group(const NetGroup& C, bool plain_is_single = true) {
+  if (C.leisure) {
+    for (int k = 0; k < C.nk; ++k)
+      if (C.table[k] < 0) return GJ_E_PLAN;
+  } else if (plain_is_single && C.nk != 1) {
+    return GJ_E_PLAN;   // several networks on one set need per-network tables
+  }
+  return GJ_OK;
+}
+
 // full: the launch reads/writes is_infected and infection_time too (a1, a9)
 static int check_state(const gj_plan* plan, const gj_agent_state* st, const gj_step_params* p, bool full = true) {
   if (!st) return GJ_E_NULL;
@@ -1337,14 +648,9 @@ static int do_transmission(const gj_plan* plan, const gj_agent_state* st, const 
   if (!st->max_infectiousness || !st->shape || !st->rate || !st->shift) return GJ_E_NULL;
   const int64_t n = plan->n_agents;
   if (n == 0) return GJ_OK;
-  const int64_t n4 = (n + 3) / 4;
-  int64_t blocks = (n4 + kThreads - 1) / kThreads;
-  if (blocks > 256 * 16) blocks = 256 * 16;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(k_transmission, dim3((unsigned)blocks), dim3(kThreads), 0, stream, n, st->max_infectiousness,
-                     st->shape, st->rate, st->shift, st->infection_time, st->is_infected, st->current_stage,
-                     st->transmission, st->q_transmission, p->now, p->has_quarantine, p->q_threshold, p->clock);
-  return launch_status();
+  return launch(k_transmission, grid_for((n + 3) / 4, 256 * 16), kThreads, 0, stream, n, st->max_infectiousness,
+                st->shape, st->rate, st->shift, st->infection_time, st->is_infected, st->current_stage,
+                st->transmission, st->q_transmission, p->now, p->has_quarantine, p->q_threshold, p->clock);
 }
 
 static int do_venue_reduce(const gj_plan* plan, const gj_agent_state* st, const gj_step_params* p, const Groups& G,
@@ -1363,20 +669,14 @@ static int do_venue_reduce(const gj_plan* plan, const gj_agent_state* st, const 
     S.v_pc = E.v_pcontact;
     S.cum = E.cum;
     S.stride = E.cum_stride;
-    S.nk = G.nk[g];
-    S.raw = p->nets[G.first[g]].mask_kind == GJ_MASK_RAW;
-    S.leisure = 0;
-    for (int k = 0; k < G.nk[g]; ++k) {
-      const gj_network& N = p->nets[G.first[g] + k];
-      S.beta[k] = N.beta;
-      S.table[k] = N.mask_kind >= GJ_MASK_QL ? N.table : -1;
-      if (N.mask_kind >= GJ_MASK_QL) S.leisure = 1;
-    }
-    if (S.leisure) {
-      // a set either is a leisure set (every network has a table) or is not
-      for (int k = 0; k < G.nk[g]; ++k)
-        if (S.table[k] < 0) return GJ_E_PLAN;
-    }
+    const NetGroup C = classify_group(p, G, g);
+    S.nk = C.nk;
+    S.raw = C.raw;
+    S.leisure = C.leisure;
+    memcpy(S.beta, C.beta, sizeof(S.beta));
+    memcpy(S.table, C.table, sizeof(S.table));
+    // (on purpose: the CSR kernels loop over the networks of a plain set, so several of them on one set are accepted)
+    if (const int rc = check_group(C, /*plain_is_single=*/false)) return rc;
   }
   A.blocks = plan->blocks;
   A.trans = st->transmission;
@@ -1385,8 +685,7 @@ static int do_venue_reduce(const gj_plan* plan, const gj_agent_state* st, const 
   A.tables = plan->tables;
   A.partial = plan->partial;
   A.day_type = p->day_type;
-  hipLaunchKernelGGL(k_venue_reduce, dim3((unsigned)plan->n_blocks), dim3(kThreads), 0, stream, A);
-  int rc = launch_status();
+  int rc = launch(k_venue_reduce, plan->n_blocks, kThreads, 0, stream, A);
   if (rc != GJ_OK) return rc;
   if (plan->n_long_rows > 0) {
     CombineArgs C;
@@ -1398,10 +697,7 @@ static int do_venue_reduce(const gj_plan* plan, const gj_agent_state* st, const 
     C.rows = plan->long_rows;
     C.partial = plan->partial;
     C.n_rows = plan->n_long_rows;
-    const int64_t threads = (int64_t)plan->n_long_rows * GJ_MAX_NETS_PER_SET;
-    hipLaunchKernelGGL(k_combine_long, dim3((unsigned)((threads + kThreads - 1) / kThreads)), dim3(kThreads), 0,
-                       stream, C);
-    rc = launch_status();
+    rc = launch(k_combine_long, grid_for((int64_t)plan->n_long_rows * GJ_MAX_NETS_PER_SET), kThreads, 0, stream, C);
   }
   return rc;
 }
@@ -1421,17 +717,11 @@ static int do_agent_gather(const gj_plan* plan, const gj_agent_state* st, const 
     S.a_venue = E.a_venue;
     S.cum = E.cum;
     S.stride = E.cum_stride;
-    S.nk = G.nk[g];
-    for (int k = 0; k < GJ_MAX_NETS_PER_SET; ++k) {
-      S.mask[k] = 0;
-      S.table[k] = 0;
-    }
-    for (int k = 0; k < G.nk[g]; ++k) {
-      const gj_network& N = p->nets[G.first[g] + k];
-      S.mask[k] = N.mask_kind;
-      S.table[k] = N.mask_kind >= GJ_MASK_QL ? N.table : 0;
-      if (N.mask_kind >= GJ_MASK_QL) P.any_leisure = 1;
-    }
+    const NetGroup C = classify_group(p, G, g);   // not checked: the kernel takes any mix of kinds, network by network
+    S.nk = C.nk;
+    memcpy(S.mask, C.mask, sizeof(S.mask));
+    for (int k = 0; k < GJ_MAX_NETS_PER_SET; ++k) S.table[k] = C.table[k] < 0 ? 0 : C.table[k];   // (no table: 0, unread)
+    P.any_leisure |= C.leisure;
   }
   P.n_agents = n;
   P.cls = plan->agent_class;
@@ -1454,9 +744,7 @@ static int do_agent_gather(const gj_plan* plan, const gj_agent_state* st, const 
   P.step = p->step;
   P.agent_offset = p->agent_offset;
   P.clock = p->clock;
-  const int64_t blocks = (n + kThreads - 1) / kThreads;
-  hipLaunchKernelGGL(k_agent_gather, dim3((unsigned)blocks), dim3(kThreads), 0, stream, P);
-  return launch_status();
+  return launch(k_agent_gather, grid_for(n), kThreads, 0, stream, P);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1536,7 +824,7 @@ static void fill_set_a(const gj_plan* plan, const gj_step_params* p, const Group
     sets[s].J = S.n_blocks;
     sets[s].active = (S.n_blocks > 0 && tiled_edges(plan, s) > 0) ? G.nk[g] : 0;
     sets[s].presum = uses_presum(plan, s);
-    sets[s].raw = p->nets[G.first[g]].mask_kind == GJ_MASK_RAW;
+    sets[s].raw = group_is_raw(p, G, g);
     sets[s].wide = S.desc_wide;          // 0 / 1: descriptor format, 2: explicit slots
     sets[s].direct = S.ell_k != 0;
     sets[s].multi_slots = S.multi_slots;
@@ -1547,6 +835,11 @@ static void fill_set_a(const gj_plan* plan, const gj_step_params* p, const Group
 static size_t slice_lds(const gj_tiled* T, size_t elem) { return (size_t)T->slice_agents * elem; }
 // phase D: 64-bit sums + two flag bits per agent (saturated up / down, gj_tiled.h fx_flag)
 static size_t agents_lds(const gj_tiled* T) { return (size_t)T->slice_agents * sizeof(fx_t) + 2 * ((size_t)T->slice_agents / 8); }
+
+// the direct forms read four agents' classes as one dword (see gj_plan.agent_class)
+static inline bool classes_by_dword(const gj_plan* plan) {
+  return plan->agent_class && (uintptr_t)plan->agent_class % 4 == 0;
+}
 
 // pass 1 of the sets in its direct form: LDS tables of fixed-point sums per workgroup (k_tile_presum)
 static int presum_fill(const gj_plan* plan, const gj_step_params* p, const Groups& G, int g, TPSet* X) {
@@ -1561,25 +854,15 @@ static int presum_fill(const gj_plan* plan, const gj_step_params* p, const Group
   X->planes = S.ell_k / 2;
   X->V = (int32_t)E.n_venues;
   X->stride = E.cum_stride;
-  X->nk = G.nk[g];
-  X->raw = p->nets[G.first[g]].mask_kind == GJ_MASK_RAW;
-  X->leisure = 0;
+  const NetGroup C = classify_group(p, G, g);
+  X->nk = C.nk;
+  X->raw = C.raw;
+  X->leisure = C.leisure;
   X->_pad = 0;
-  for (int k = 0; k < GJ_MAX_NETS_PER_SET; ++k) X->table[k] = X->age75[k] = 0;
-  for (int k = 0; k < G.nk[g]; ++k) {
-    const gj_network& N = p->nets[G.first[g] + k];
-    X->table[k] = N.mask_kind >= GJ_MASK_QL ? N.table : -1;
-    X->age75[k] = N.mask_kind == GJ_MASK_QL_AGE75;
-    if (N.mask_kind >= GJ_MASK_QL) X->leisure = 1;
-  }
-  if (X->leisure) {
-    if (!plan->agent_class || (uintptr_t)plan->agent_class % 4 != 0) return GJ_E_PLAN;
-    for (int k = 0; k < G.nk[g]; ++k)
-      if (X->table[k] < 0) return GJ_E_PLAN;
-  } else if (G.nk[g] != 1) {
-    return GJ_E_PLAN;
-  }
-  return GJ_OK;
+  memcpy(X->table, C.table, sizeof(X->table));
+  memcpy(X->age75, C.age75, sizeof(X->age75));
+  if (C.leisure && !classes_by_dword(plan)) return GJ_E_PLAN;
+  return check_group(C);
 }
 
 static int tiled_presum(const gj_plan* plan, const gj_agent_state* st, const gj_step_params* p, const Groups& G,
@@ -1615,15 +898,14 @@ static int tiled_presum(const gj_plan* plan, const gj_agent_state* st, const gj_
   P.n_agents = plan->n_agents;
   P.trans = st->transmission;
   P.qtrans = p->has_quarantine ? st->q_transmission : st->transmission;
-  if ((uintptr_t)P.trans % 16 != 0 || (uintptr_t)P.qtrans % 16 != 0) return GJ_E_PLAN;
+  if (!aligned16(P.trans, P.qtrans)) return GJ_E_PLAN;
   P.cls = plan->agent_class;
   P.tables = plan->tables;
   P.day_type = p->day_type;
   P.transpose = p->transpose;
   int rc = allow_lds(k_tile_presum, lds);
   if (rc) return rc;
-  hipLaunchKernelGGL(k_tile_presum, dim3((unsigned)T->presum_wgs), dim3(kTileThreads), lds, stream, P);
-  return launch_status();
+  return launch(k_tile_presum, T->presum_wgs, kTileThreads, lds, stream, P);
 }
 
 static int tiled_presum_reduce(const gj_plan* plan, const gj_step_params* p, const Groups& G, hipStream_t stream) {
@@ -1646,14 +928,14 @@ static int tiled_presum_reduce(const gj_plan* plan, const gj_step_params* p, con
     X.stride = E.cum_stride;
     X.nk = G.nk[g];
     X.first = (int32_t)total;
-    for (int k = 0; k < GJ_MAX_NETS_PER_SET; ++k) X.beta[k] = k < G.nk[g] ? p->nets[G.first[g] + k].beta : 0.0f;
+    const NetGroup C = classify_group(p, G, g);
+    memcpy(X.beta, C.beta, sizeof(X.beta));
     total += (int64_t)X.V * X.nk;
   }
   if (R.n_sets == 0 || total == 0) return GJ_OK;
   if (total > INT32_MAX) return GJ_E_RANGE;
   R.total = (int32_t)total;
-  hipLaunchKernelGGL(k_presum_reduce, dim3((unsigned)((total + kWave - 1) / kWave)), dim3(kThreads), 0, stream, R);
-  return launch_status();
+  return launch(k_presum_reduce, grid_for(total, 0, kWave), kThreads, 0, stream, R);
 }
 
 static int tiled_scatter(const gj_plan* plan, const gj_agent_state* st, const gj_step_params* p, const Groups& G,
@@ -1670,8 +952,7 @@ static int tiled_scatter(const gj_plan* plan, const gj_agent_state* st, const gj
   const size_t lds = slice_lds(T, sizeof(float));
   int rc = allow_lds(k_tile_scatter, lds);
   if (rc) return rc;
-  hipLaunchKernelGGL(k_tile_scatter, dim3((unsigned)T->n_slices), dim3(kTileThreads), lds, stream, A);
-  rc = launch_status();
+  rc = launch(k_tile_scatter, T->n_slices, kTileThreads, lds, stream, A);
   if (rc) return rc;
   return tiled_presum(plan, st, p, G, stream);
 }
@@ -1716,31 +997,22 @@ static int tiled_venues(const gj_plan* plan, const gj_agent_state* st, const gj_
     X.nk = S.n_blocks > 0 ? G.nk[g] : 0;
     if (uses_presum(plan, s)) X.nk = 0;          // pass 1 of the set is k_tile_presum's, pass 2 phase D's: nothing here
     X.direct = S.ell_k != 0;
-    X.leisure = 0;
-    for (int k = 0; k < G.nk[g]; ++k) {
-      const gj_network& N = p->nets[G.first[g] + k];
-      X.beta[k] = N.beta;
-      X.table[k] = N.mask_kind >= GJ_MASK_QL ? N.table : -1;
-      X.age75[k] = N.mask_kind == GJ_MASK_QL_AGE75;
-      if (N.mask_kind >= GJ_MASK_QL) X.leisure = 1;
-    }
-    if (X.leisure) {
-      if (!S.e_cls && E.n_edges > 0) return GJ_E_PLAN;
-      for (int k = 0; k < G.nk[g]; ++k)
-        if (X.table[k] < 0) return GJ_E_PLAN;
-    } else if (G.nk[g] != 1) {
-      return GJ_E_PLAN;   // several networks on one set need per-network tables
-    }
+    const NetGroup C = classify_group(p, G, g);
+    X.leisure = C.leisure;
+    memcpy(X.beta, C.beta, sizeof(X.beta));
+    memcpy(X.table, C.table, sizeof(X.table));
+    memcpy(X.age75, C.age75, sizeof(X.age75));
+    if (C.leisure && !S.e_cls && E.n_edges > 0) return GJ_E_PLAN;
+    if (const int rc = check_group(C)) return rc;
     X.pv_blk = nullptr;
     X.blk_r0 = nullptr;
     X.x = nullptr;
     X.n_x = 0;
     if (S.run_pv_blk && mode != 2) {     // run form: phase B reads the primary edges' values from the per-agent array
       if (X.leisure) return GJ_E_PLAN;
-      const bool raw = p->nets[G.first[g]].mask_kind == GJ_MASK_RAW;
-      X.x = (p->has_quarantine && !raw) ? st->q_transmission : st->transmission;
+      X.x = (p->has_quarantine && !C.raw) ? st->q_transmission : st->transmission;
       if (!X.x) return GJ_E_NULL;
-      if ((uintptr_t)X.x % 16 != 0 || (uintptr_t)S.run_pv_blk % 16 != 0) return GJ_E_PLAN;
+      if (!aligned16(X.x, S.run_pv_blk)) return GJ_E_PLAN;
       X.pv_blk = S.run_pv_blk;
       X.blk_r0 = S.run_blk_r0;
       X.n_x = plan->n_ext_agents;
@@ -1758,8 +1030,7 @@ static int tiled_venues(const gj_plan* plan, const gj_agent_state* st, const gj_
   B.transpose = p->transpose;
   int rc = allow_lds(k_tile_venues, lds);
   if (rc) return rc;
-  hipLaunchKernelGGL(k_tile_venues, dim3((unsigned)T->n_work), dim3(kTileThreads), lds, stream, B);
-  rc = launch_status();
+  rc = launch(k_tile_venues, T->n_work, kTileThreads, lds, stream, B);
   if (rc || mode == 2) return rc;
   return tiled_presum_reduce(plan, p, G, stream);
 }
@@ -1818,24 +1089,14 @@ static int tiled_agents(const gj_plan* plan, const gj_agent_state* st, const gj_
     X.win_n = run ? S.run_win_n : nullptr;
     if (run && (uintptr_t)S.run_pv_win % 8 != 0) return GJ_E_PLAN;
     X.stride = E.cum_stride;
-    X.nk = G.nk[g];
-    X.raw = p->nets[G.first[g]].mask_kind == GJ_MASK_RAW;
-    X.leisure = 0;
-    for (int k = 0; k < GJ_MAX_NETS_PER_SET; ++k) X.table[k] = X.age75[k] = 0;
-    for (int k = 0; k < G.nk[g]; ++k) {
-      const gj_network& N = p->nets[G.first[g] + k];
-      X.table[k] = N.mask_kind >= GJ_MASK_QL ? N.table : -1;
-      X.age75[k] = N.mask_kind == GJ_MASK_QL_AGE75;
-      if (N.mask_kind >= GJ_MASK_QL) X.leisure = 1;
-    }
-    if (X.leisure) {
-      // the direct form reads four agents' classes as one dword (see gj_plan.agent_class)
-      if (!plan->agent_class || (uintptr_t)plan->agent_class % 4 != 0) return GJ_E_PLAN;
-      for (int k = 0; k < G.nk[g]; ++k)
-        if (X.table[k] < 0) return GJ_E_PLAN;
-    } else if (G.nk[g] != 1) {
-      return GJ_E_PLAN;
-    }
+    const NetGroup C = classify_group(p, G, g);
+    X.nk = C.nk;
+    X.raw = C.raw;
+    X.leisure = C.leisure;
+    memcpy(X.table, C.table, sizeof(X.table));
+    memcpy(X.age75, C.age75, sizeof(X.age75));
+    if (C.leisure && !classes_by_dword(plan)) return GJ_E_PLAN;
+    if (const int rc = check_group(C)) return rc;
   }
   D.table_floats = D.table1_floats = 0;
   D._pad3 = 0;
@@ -1871,18 +1132,53 @@ static int tiled_agents(const gj_plan* plan, const gj_agent_state* st, const gj_
     const size_t direct_lds = 4 * ((size_t)2 * kClassWeightFloats + (size_t)cap0 + kWave + (size_t)cap1 + kWave);
     if (direct_lds > lds) lds = direct_lds;
   }
-  {
-    uintptr_t bits = (uintptr_t)D.susceptibility | (uintptr_t)D.not_infected_probs | (uintptr_t)D.new_infected |
-                     (uintptr_t)D.trans_susc | (uintptr_t)D.acc_scratch | (uintptr_t)D.agent_sums;
-    D.io_vec4 = (bits % 16 == 0) ? 1 : 0;
-  }
+  D.io_vec4 = aligned16(D.susceptibility, D.not_infected_probs, D.new_infected, D.trans_susc, D.acc_scratch, D.agent_sums);
   int rc = allow_lds(k_tile_agents, lds);
   if (rc) return rc;
-  hipLaunchKernelGGL(k_tile_agents, dim3((unsigned)owned_slices), dim3(kTileThreads), lds, stream, D);
-  rc = launch_status();
+  rc = launch(k_tile_agents, owned_slices, kTileThreads, lds, stream, D);
   if (rc || !D.acc_scratch) return rc;
-  hipLaunchKernelGGL(k_tile_epilogue, dim3((unsigned)((plan->n_agents + 255) / 256)), dim3(256), 0, stream, D);
-  return launch_status();
+  return launch(k_tile_epilogue, grid_for(plan->n_agents), kThreads, 0, stream, D);
+}
+
+// ---- argument rules that several entry points share ----
+// the symptoms update's inputs (gj_symptoms_update, gj_adjoint_symptoms, gj_symptoms_step_stats)
+static int check_symptoms(const uint8_t* agent_class, const float* new_infected, const float* current_stage,
+                          const float* next_stage, const float* time_to_next_stage, const gj_symptoms_params* params,
+                          const float* progresses, const float* dwell) {
+  if (!agent_class || !new_infected || !current_stage || !next_stage || !time_to_next_stage || !params)
+    return GJ_E_NULL;
+  if (params->n_stages < 3 || params->n_stages > GJ_MAX_STAGES) return GJ_E_RANGE;
+  if ((progresses == nullptr) != (dwell == nullptr)) return GJ_E_NULL;   // inject both or neither
+  if (!progresses && !params->progress) return GJ_E_NULL;
+  return GJ_OK;
+}
+
+// the per-step statistics' arguments and grid (gj_step_stats, gj_symptoms_step_stats); vec4: every array the kernel reads
+// four agents at a time is 16-byte aligned
+static StatsArgs stats_args(int64_t n, const uint8_t* agent_class, const float* is_infected, const float* current_stage,
+                            int32_t n_bins, const int32_t* bin_edges, int32_t dead_stage, double* out, bool vec4) {
+  StatsArgs S;
+  S.n = n;
+  S.cls = agent_class;
+  S.inf = is_infected;
+  S.stage = current_stage;
+  S.n_bins = n_bins;
+  for (int b = 0; b <= GJ_MAX_AGE_BINS; ++b) S.edges[b] = (b <= n_bins) ? bin_edges[b] : 0;
+  S.dead = dead_stage;
+  S.vec4 = (vec4 && (uintptr_t)agent_class % 4 == 0) ? 1 : 0;
+  S.out = out;
+  return S;
+}
+// lanes of a kernel that takes four agents per lane where vec4 holds (+ 3: the scalar tail's lanes)
+static inline int64_t vec4_lanes(int64_t n, int vec4) { return vec4 ? (n >> 2) + 3 : n; }
+
+// the required arguments of the transmission adjoint (gj_adjoint_transmission, gj_adjoint_transmission_params)
+static int check_profile_adjoint(const gj_agent_state* st, const float* trans_bar, const float* grad_inf_out,
+                                 const float* grad_time_inout) {
+  if (!st || !trans_bar || !grad_inf_out || !grad_time_inout) return GJ_E_NULL;
+  if (!st->max_infectiousness || !st->shape || !st->rate || !st->shift || !st->infection_time || !st->is_infected)
+    return GJ_E_NULL;
+  return GJ_OK;
 }
 
 }  // namespace gj
@@ -1946,10 +1242,8 @@ int gj_quarantine_transmission(const gj_plan* plan, const gj_agent_state* state,
   if (rc) return rc;
   if (!params->has_quarantine || plan->n_agents == 0) return GJ_OK;
   const int64_t n = plan->n_agents;
-  hipLaunchKernelGGL(gj::k_quarantine_transmission, dim3((unsigned)((n + gj::kThreads - 1) / gj::kThreads)),
-                     dim3(gj::kThreads), 0, (hipStream_t)stream, n, state->current_stage, state->transmission,
-                     state->q_transmission, params->q_threshold);
-  return gj::launch_status();
+  return gj::launch(gj::k_quarantine_transmission, gj::grid_for(n), gj::kThreads, 0, (hipStream_t)stream, n,
+                    state->current_stage, state->transmission, state->q_transmission, params->q_threshold);
 }
 
 int gj_venue_reduce(const gj_plan* plan, const gj_agent_state* state, const gj_step_params* params, void* stream) {
@@ -1994,11 +1288,9 @@ int gj_sample_infect(int64_t n_agents, const float* not_infected_probs, const fl
   const int n_state = (susceptibility != nullptr) + (is_infected != nullptr) + (infection_time != nullptr);
   if (n_state != 0 && n_state != 3) return GJ_E_NULL;   // all three or none (sample only)
   if (n_state == 0 && !new_infected) return GJ_E_NULL;
-  const int64_t blocks = (n_agents + gj::kThreads - 1) / gj::kThreads;
-  hipLaunchKernelGGL(gj::k_sample_infect, dim3((unsigned)blocks), dim3(gj::kThreads), 0, (hipStream_t)stream, n_agents,
-                     not_infected_probs, exp_noise, seed, step, agent_offset, now, new_infected, susceptibility,
-                     is_infected, infection_time);
-  return gj::launch_status();
+  return gj::launch(gj::k_sample_infect, gj::grid_for(n_agents), gj::kThreads, 0, (hipStream_t)stream, n_agents,
+                    not_infected_probs, exp_noise, seed, step, agent_offset, now, new_infected, susceptibility,
+                    is_infected, infection_time);
 }
 
 int gj_adjoint_sample(int64_t n, const float* susceptibility0, const float* infection_time0, const float* acc,
@@ -2008,10 +1300,9 @@ int gj_adjoint_sample(int64_t n, const float* susceptibility0, const float* infe
   if (n < 0) return GJ_E_RANGE;
   if (n == 0) return GJ_OK;
   if (!susceptibility0 || !infection_time0 || !acc || !x_out || !grad_susc_out || !grad_time_out) return GJ_E_NULL;
-  hipLaunchKernelGGL(gj::k_adjoint_sample, dim3((unsigned)((n + gj::kThreads - 1) / gj::kThreads)), dim3(gj::kThreads),
-                     0, (hipStream_t)stream, n, susceptibility0, infection_time0, acc, exp_noise, seed, step,
-                     agent_offset, now, delta_time, g_susc, g_inf, g_time, g_new, x_out, grad_susc_out, grad_time_out);
-  return gj::launch_status();
+  return gj::launch(gj::k_adjoint_sample, gj::grid_for(n), gj::kThreads, 0, (hipStream_t)stream, n, susceptibility0,
+                    infection_time0, acc, exp_noise, seed, step, agent_offset, now, delta_time, g_susc, g_inf, g_time,
+                    g_new, x_out, grad_susc_out, grad_time_out);
 }
 
 int gj_adjoint_seed(int64_t n, const float* p_not_by_group, const int32_t* group, int32_t n_groups,
@@ -2051,9 +1342,9 @@ int gj_adjoint_seed(int64_t n, const float* p_not_by_group, const int32_t* group
     R.chunk_group = nullptr;
   }
   constexpr int kWaves = gj::kThreads / gj::kWave;
-  const int64_t agent_blocks = (n + gj::kThreads - 1) / gj::kThreads;
-  const int64_t chunk_blocks = (R.n_chunks + kWaves - 1) / kWaves;
-  const int64_t group_blocks = ((int64_t)n_groups + kWaves - 1) / kWaves;
+  const int64_t agent_blocks = gj::grid_for(n);
+  const int64_t chunk_blocks = gj::grid_for(R.n_chunks, 0, kWaves);      // one wave per chunk, per group
+  const int64_t group_blocks = gj::grid_for(n_groups, 0, kWaves);
   if (agent_blocks > 0x7fffffff || chunk_blocks > 0x7fffffff) return GJ_E_RANGE;
   if (n > 0 && (!p_not_by_group || !susceptibility0 || !infection_time0 || !contrib_workspace)) return GJ_E_NULL;
   if (R.n_chunks > 0 && !partial_workspace) return GJ_E_NULL;
@@ -2077,34 +1368,24 @@ int gj_adjoint_seed(int64_t n, const float* p_not_by_group, const int32_t* group
     A.contrib = contrib_workspace;
     A.grad_susc = grad_susc_out;
     A.grad_time = grad_time_out;
-    hipLaunchKernelGGL(gj::k_adjoint_seed_agents, dim3((unsigned)agent_blocks), dim3(gj::kThreads), 0,
-                       (hipStream_t)stream, A);
-    int rc = gj::launch_status();
+    const int rc = gj::launch(gj::k_adjoint_seed_agents, agent_blocks, gj::kThreads, 0, (hipStream_t)stream, A);
     if (rc) return rc;
   }
   if (R.n_chunks > 0) {
-    hipLaunchKernelGGL(gj::k_adjoint_seed_chunks, dim3((unsigned)chunk_blocks), dim3(gj::kThreads), 0,
-                       (hipStream_t)stream, R);
-    int rc = gj::launch_status();
+    const int rc = gj::launch(gj::k_adjoint_seed_chunks, chunk_blocks, gj::kThreads, 0, (hipStream_t)stream, R);
     if (rc) return rc;
   }
-  hipLaunchKernelGGL(gj::k_adjoint_seed_finish, dim3((unsigned)group_blocks), dim3(gj::kThreads), 0, (hipStream_t)stream,
-                     R);
-  return gj::launch_status();
+  return gj::launch(gj::k_adjoint_seed_finish, group_blocks, gj::kThreads, 0, (hipStream_t)stream, R);
 }
 
 int gj_adjoint_transmission(int64_t n, const gj_agent_state* st, float now, const float* trans_bar,
                             const float* g_inf, float* grad_inf_out, float* grad_time_inout, void* stream) {
   if (n < 0) return GJ_E_RANGE;
   if (n == 0) return GJ_OK;
-  if (!st || !trans_bar || !grad_inf_out || !grad_time_inout) return GJ_E_NULL;
-  if (!st->max_infectiousness || !st->shape || !st->rate || !st->shift || !st->infection_time || !st->is_infected)
-    return GJ_E_NULL;
-  hipLaunchKernelGGL(gj::k_adjoint_transmission, dim3((unsigned)((n + gj::kThreads - 1) / gj::kThreads)),
-                     dim3(gj::kThreads), 0, (hipStream_t)stream, n, st->max_infectiousness, st->shape, st->rate,
-                     st->shift, st->infection_time, st->is_infected, now, trans_bar, g_inf, grad_inf_out,
-                     grad_time_inout);
-  return gj::launch_status();
+  if (const int rc = gj::check_profile_adjoint(st, trans_bar, grad_inf_out, grad_time_inout)) return rc;
+  return gj::launch(gj::k_adjoint_transmission, gj::grid_for(n), gj::kThreads, 0, (hipStream_t)stream, n,
+                    st->max_infectiousness, st->shape, st->rate, st->shift, st->infection_time, st->is_infected, now,
+                    trans_bar, g_inf, grad_inf_out, grad_time_inout);
 }
 
 int gj_adjoint_transmission_params(int64_t n, const gj_agent_state* st, float now, const float* trans_bar,
@@ -2113,14 +1394,11 @@ int gj_adjoint_transmission_params(int64_t n, const gj_agent_state* st, float no
                                    float* grad_shift_out, void* stream) {
   if (n < 0) return GJ_E_RANGE;
   if (n == 0) return GJ_OK;
-  if (!st || !trans_bar || !grad_inf_out || !grad_time_inout) return GJ_E_NULL;
-  if (!st->max_infectiousness || !st->shape || !st->rate || !st->shift || !st->infection_time || !st->is_infected)
-    return GJ_E_NULL;
-  hipLaunchKernelGGL(gj::k_adjoint_transmission_params, dim3((unsigned)((n + gj::kThreads - 1) / gj::kThreads)),
-                     dim3(gj::kThreads), 0, (hipStream_t)stream, n, st->max_infectiousness, st->shape, st->rate,
-                     st->shift, st->infection_time, st->is_infected, now, trans_bar, g_inf, grad_inf_out,
-                     grad_time_inout, grad_max_infectiousness_out, grad_shape_out, grad_rate_out, grad_shift_out);
-  return gj::launch_status();
+  if (const int rc = gj::check_profile_adjoint(st, trans_bar, grad_inf_out, grad_time_inout)) return rc;
+  return gj::launch(gj::k_adjoint_transmission_params, gj::grid_for(n), gj::kThreads, 0, (hipStream_t)stream, n,
+                    st->max_infectiousness, st->shape, st->rate, st->shift, st->infection_time, st->is_infected, now,
+                    trans_bar, g_inf, grad_inf_out, grad_time_inout, grad_max_infectiousness_out, grad_shape_out,
+                    grad_rate_out, grad_shift_out);
 }
 
 int gj_adjoint_beta_partial(int64_t n_venues, int32_t stride, int32_t nk, const float* cum_fwd, const float* cum_bwd,
@@ -2144,16 +1422,14 @@ int gj_adjoint_beta_partial(int64_t n_venues, int32_t stride, int32_t nk, const 
     if (k < nk && (cols[k] < 0 || cols[k] >= GJ_MAX_NETS)) return GJ_E_RANGE;
   }
   A.partial = partial;
-  hipLaunchKernelGGL(gj::k_adjoint_beta_partial, dim3(GJ_ADJ_BETA_BLOCKS), dim3(gj::kAdjBetaThreads), 0, (hipStream_t)stream, A);
-  return gj::launch_status();
+  return gj::launch(gj::k_adjoint_beta_partial, GJ_ADJ_BETA_BLOCKS, gj::kAdjBetaThreads, 0, (hipStream_t)stream, A);
 }
 
 int gj_adjoint_beta_finish(int32_t n_cols, const double* partial, const float* scale, double* out, void* stream) {
   if (n_cols < 0 || n_cols > GJ_MAX_NETS) return GJ_E_RANGE;
   if (n_cols == 0) return GJ_OK;
   if (!partial || !scale || !out) return GJ_E_NULL;
-  hipLaunchKernelGGL(gj::k_adjoint_beta_finish, dim3(1), dim3(64), 0, (hipStream_t)stream, n_cols, partial, scale, out);
-  return gj::launch_status();
+  return gj::launch(gj::k_adjoint_beta_finish, 1, 64, 0, (hipStream_t)stream, n_cols, partial, scale, out);
 }
 
 int gj_symptoms_update(int64_t n, const uint8_t* agent_class, const float* new_infected, float* current_stage,
@@ -2161,24 +1437,12 @@ int gj_symptoms_update(int64_t n, const uint8_t* agent_class, const float* new_i
                        const float* progresses, const float* dwell, void* stream) {
   if (n < 0) return GJ_E_RANGE;
   if (n == 0) return GJ_OK;
-  if (!agent_class || !new_infected || !current_stage || !next_stage || !time_to_next_stage || !params)
-    return GJ_E_NULL;
-  if (params->n_stages < 3 || params->n_stages > GJ_MAX_STAGES) return GJ_E_RANGE;
-  if ((progresses == nullptr) != (dwell == nullptr)) return GJ_E_NULL;   // inject both or neither
-  if (!progresses && !params->progress) return GJ_E_NULL;
-  gj::SymptomsArgs S;
-  S.P = *params;
-  S.n = n;
-  S.cls = agent_class;
-  S.new_inf = new_infected;
-  S.cur = current_stage;
-  S.nxt = next_stage;
-  S.ttn = time_to_next_stage;
-  S.progresses = progresses;
-  S.dwell = dwell;
-  hipLaunchKernelGGL(gj::k_symptoms, dim3((unsigned)((n + gj::kThreads - 1) / gj::kThreads)), dim3(gj::kThreads), 0,
-                     (hipStream_t)stream, S);
-  return gj::launch_status();
+  if (const int rc = gj::check_symptoms(agent_class, new_infected, current_stage, next_stage, time_to_next_stage, params,
+                                        progresses, dwell))
+    return rc;
+  const gj::SymptomsArgs S = {*params, n, agent_class, new_infected, current_stage, next_stage, time_to_next_stage,
+                              progresses, dwell};
+  return gj::launch(gj::k_symptoms, gj::grid_for(n), gj::kThreads, 0, (hipStream_t)stream, S);
 }
 
 int gj_adjoint_symptoms(int64_t n, const uint8_t* agent_class, const float* new_infected,
@@ -2188,12 +1452,10 @@ int gj_adjoint_symptoms(int64_t n, const uint8_t* agent_class, const float* new_
                         float* g_next_in, float* g_time_in, float* g_new_infected, void* stream) {
   if (n < 0) return GJ_E_RANGE;
   if (n == 0) return GJ_OK;
-  if (!agent_class || !new_infected || !current_stage0 || !next_stage0 || !time_to_next_stage0 || !params)
-    return GJ_E_NULL;
   if (!g_current_in || !g_next_in || !g_new_infected) return GJ_E_NULL;
-  if (params->n_stages < 3 || params->n_stages > GJ_MAX_STAGES) return GJ_E_RANGE;
-  if ((progresses == nullptr) != (dwell == nullptr)) return GJ_E_NULL;   // inject both or neither
-  if (!progresses && !params->progress) return GJ_E_NULL;
+  if (const int rc = gj::check_symptoms(agent_class, new_infected, current_stage0, next_stage0, time_to_next_stage0,
+                                        params, progresses, dwell))
+    return rc;
   gj::SymptomsAdjointArgs S;
   S.P = *params;
   S.n = n;
@@ -2211,9 +1473,7 @@ int gj_adjoint_symptoms(int64_t n, const uint8_t* agent_class, const float* new_
   S.g_nxt_in = g_next_in;
   S.g_ttn_in = g_time_in;
   S.g_new = g_new_infected;
-  hipLaunchKernelGGL(gj::k_adjoint_symptoms, dim3((unsigned)((n + gj::kThreads - 1) / gj::kThreads)),
-                     dim3(gj::kThreads), 0, (hipStream_t)stream, S);
-  return gj::launch_status();
+  return gj::launch(gj::k_adjoint_symptoms, gj::grid_for(n), gj::kThreads, 0, (hipStream_t)stream, S);
 }
 
 int gj_step_stats(int64_t n, const uint8_t* agent_class, const float* is_infected, const float* current_stage,
@@ -2222,21 +1482,10 @@ int gj_step_stats(int64_t n, const uint8_t* agent_class, const float* is_infecte
   if (!out || (n_bins > 0 && !bin_edges)) return GJ_E_NULL;
   if (n == 0) return GJ_OK;
   if (!agent_class || !is_infected || !current_stage) return GJ_E_NULL;
-  gj::StatsArgs S;
-  S.n = n;
-  S.cls = agent_class;
-  S.inf = is_infected;
-  S.stage = current_stage;
-  S.n_bins = n_bins;
-  for (int b = 0; b <= GJ_MAX_AGE_BINS; ++b) S.edges[b] = (b <= n_bins) ? bin_edges[b] : 0;
-  S.dead = dead_stage;
-  S.out = out;
-  S.vec4 = (((uintptr_t)is_infected | (uintptr_t)current_stage) % 16 == 0 && (uintptr_t)agent_class % 4 == 0) ? 1 : 0;
-  int64_t blocks = ((S.vec4 ? (n >> 2) + 3 : n) + gj::kThreads - 1) / gj::kThreads;
-  if (blocks > 2048) blocks = 2048;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(gj::k_step_stats, dim3((unsigned)blocks), dim3(gj::kThreads), 0, (hipStream_t)stream, S);
-  return gj::launch_status();
+  const gj::StatsArgs S = gj::stats_args(n, agent_class, is_infected, current_stage, n_bins, bin_edges, dead_stage, out,
+                                         gj::aligned16(is_infected, current_stage));
+  return gj::launch(gj::k_step_stats, gj::grid_for(gj::vec4_lanes(n, S.vec4), 2048), gj::kThreads, 0,
+                    (hipStream_t)stream, S);
 }
 
 int gj_symptoms_step_stats(int64_t n, const uint8_t* agent_class, const float* new_infected, float* current_stage,
@@ -2246,38 +1495,17 @@ int gj_symptoms_step_stats(int64_t n, const uint8_t* agent_class, const float* n
   if (n < 0 || n_bins < 0 || n_bins > GJ_MAX_AGE_BINS) return GJ_E_RANGE;
   if (!out || (n_bins > 0 && !bin_edges)) return GJ_E_NULL;
   if (n == 0) return GJ_OK;
-  if (!agent_class || !new_infected || !current_stage || !next_stage || !time_to_next_stage || !params || !is_infected)
-    return GJ_E_NULL;
-  if (params->n_stages < 3 || params->n_stages > GJ_MAX_STAGES) return GJ_E_RANGE;
-  if ((progresses == nullptr) != (dwell == nullptr)) return GJ_E_NULL;   // inject both or neither
-  if (!progresses && !params->progress) return GJ_E_NULL;
-  gj::SymptomsArgs S;
-  S.P = *params;
-  S.n = n;
-  S.cls = agent_class;
-  S.new_inf = new_infected;
-  S.cur = current_stage;
-  S.nxt = next_stage;
-  S.ttn = time_to_next_stage;
-  S.progresses = progresses;
-  S.dwell = dwell;
-  gj::StatsArgs R;
-  R.n = n;
-  R.cls = agent_class;
-  R.inf = is_infected;
-  R.stage = current_stage;
-  R.n_bins = n_bins;
-  for (int b = 0; b <= GJ_MAX_AGE_BINS; ++b) R.edges[b] = (b <= n_bins) ? bin_edges[b] : 0;
-  R.dead = dead_stage;
-  R.out = out;
-  const uintptr_t bits = (uintptr_t)new_infected | (uintptr_t)current_stage | (uintptr_t)next_stage |
-                         (uintptr_t)time_to_next_stage | (uintptr_t)is_infected;
-  R.vec4 = (bits % 16 == 0 && (uintptr_t)agent_class % 4 == 0) ? 1 : 0;
-  int64_t blocks = ((R.vec4 ? (n >> 2) + 3 : n) + gj::kThreads - 1) / gj::kThreads;
-  if (blocks > 4096) blocks = 4096;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(gj::k_symptoms_stats, dim3((unsigned)blocks), dim3(gj::kThreads), 0, (hipStream_t)stream, S, R);
-  return gj::launch_status();
+  if (!is_infected) return GJ_E_NULL;
+  if (const int rc = gj::check_symptoms(agent_class, new_infected, current_stage, next_stage, time_to_next_stage, params,
+                                        progresses, dwell))
+    return rc;
+  const gj::SymptomsArgs S = {*params, n, agent_class, new_infected, current_stage, next_stage, time_to_next_stage,
+                              progresses, dwell};
+  const gj::StatsArgs R =
+      gj::stats_args(n, agent_class, is_infected, current_stage, n_bins, bin_edges, dead_stage, out,
+                     gj::aligned16(new_infected, current_stage, next_stage, time_to_next_stage, is_infected));
+  return gj::launch(gj::k_symptoms_stats, gj::grid_for(gj::vec4_lanes(n, R.vec4), 4096), gj::kThreads, 0,
+                    (hipStream_t)stream, S, R);
 }
 
 int gj_group_stats(int64_t n, const int32_t* group, int32_t n_groups, const float* is_infected,
@@ -2293,24 +1521,18 @@ int gj_group_stats(int64_t n, const int32_t* group, int32_t n_groups, const floa
   S.stage = current_stage;
   S.n_groups = n_groups;
   S.dead = dead_stage;
-  S.vec4 = (((uintptr_t)group | (uintptr_t)is_infected | (uintptr_t)current_stage) % 16 == 0) ? 1 : 0;
+  S.vec4 = gj::aligned16(group, is_infected, current_stage);
   S.ws = (gj::fx_t*)workspace;
   const int64_t units = S.vec4 ? (n >> 2) + 1 : n;
-  if (n_groups <= gj::kGroupLdsMax) {       // regimes (i) and (iii): a histogram in LDS per workgroup
-    int64_t blocks = (units + gj::kGroupLdsThreads - 1) / gj::kGroupLdsThreads;
-    if (blocks > gj::kGroupLdsBlocks) blocks = gj::kGroupLdsBlocks;
-    hipLaunchKernelGGL(gj::k_group_stats<true>, dim3((unsigned)blocks), dim3(gj::kGroupLdsThreads),
-                       (size_t)n_groups * 2 * sizeof(gj::fx_t), (hipStream_t)stream, S);
-  } else {                                  // regime (ii): one global atomic per run of equal labels in a wave
-    int64_t blocks = (units + gj::kThreads - 1) / gj::kThreads;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(gj::k_group_stats<false>, dim3((unsigned)blocks), dim3(gj::kThreads), 0, (hipStream_t)stream, S);
-  }
-  int rc = gj::launch_status();
+  const int rc =
+      n_groups <= gj::kGroupLdsMax       // regimes (i) and (iii): a histogram in LDS per workgroup
+          ? gj::launch(gj::k_group_stats<true>, gj::grid_for(units, gj::kGroupLdsBlocks, gj::kGroupLdsThreads),
+                       gj::kGroupLdsThreads, (size_t)n_groups * 2 * sizeof(gj::fx_t), (hipStream_t)stream, S)
+          // regime (ii): one global atomic per run of equal labels in a wave
+          : gj::launch(gj::k_group_stats<false>, gj::grid_for(units, 2048), gj::kThreads, 0, (hipStream_t)stream, S);
   if (rc) return rc;
-  hipLaunchKernelGGL(gj::k_group_finish, dim3((unsigned)((2 * (int64_t)n_groups + gj::kThreads - 1) / gj::kThreads)),
-                     dim3(gj::kThreads), 0, (hipStream_t)stream, n_groups, S.ws, out);
-  return gj::launch_status();
+  return gj::launch(gj::k_group_finish, gj::grid_for(2 * (int64_t)n_groups), gj::kThreads, 0, (hipStream_t)stream,
+                    n_groups, S.ws, out);
 }
 
 int gj_adjoint_group_stats(int64_t n, const int32_t* group, int32_t n_groups, const float* current_stage,
@@ -2330,19 +1552,12 @@ int gj_adjoint_group_stats(int64_t n, const int32_t* group, int32_t n_groups, co
   S.grad_stage = grad_stage;
   S.n_groups = n_groups;
   S.dead = dead_stage;
-  const uintptr_t bits = (uintptr_t)group | (uintptr_t)grad_is_infected | (uintptr_t)grad_stage |
-                         (grad_stage ? (uintptr_t)current_stage : 0);
-  S.vec4 = (bits % 16 == 0) ? 1 : 0;
-  int64_t blocks = ((S.vec4 ? (n >> 2) + 3 : n) + gj::kThreads - 1) / gj::kThreads;
-  if (blocks > 2048) blocks = 2048;
-  if (blocks < 1) blocks = 1;
+  S.vec4 = gj::aligned16(group, grad_is_infected, grad_stage, grad_stage ? current_stage : nullptr);   // (stage: read for grad_stage only)
+  const int64_t blocks = gj::grid_for(gj::vec4_lanes(n, S.vec4), 2048);
   if (n_groups <= gj::kGroupAdjLdsMax)
-    hipLaunchKernelGGL(gj::k_adjoint_group_stats<true>, dim3((unsigned)blocks), dim3(gj::kThreads),
-                       (size_t)n_groups * 2 * sizeof(float), (hipStream_t)stream, S);
-  else
-    hipLaunchKernelGGL(gj::k_adjoint_group_stats<false>, dim3((unsigned)blocks), dim3(gj::kThreads), 0,
-                       (hipStream_t)stream, S);
-  return gj::launch_status();
+    return gj::launch(gj::k_adjoint_group_stats<true>, blocks, gj::kThreads, (size_t)n_groups * 2 * sizeof(float),
+                      (hipStream_t)stream, S);
+  return gj::launch(gj::k_adjoint_group_stats<false>, blocks, gj::kThreads, 0, (hipStream_t)stream, S);
 }
 
 int gj_step(const gj_plan* plan, const gj_agent_state* state, const gj_step_params* params, const gj_step_io* io,
@@ -2409,26 +1624,21 @@ __global__ void k_clock_advance(gj_clock* clock, double delta_now) {
 
 int gj_clock_advance(gj_clock* clock, double delta_now, void* stream) {
   if (!clock) return GJ_E_NULL;
-  hipLaunchKernelGGL(gj::k_clock_advance, dim3(1), dim3(1), 0, (hipStream_t)stream, clock, delta_now);
-  return gj::launch_status();
+  return gj::launch(gj::k_clock_advance, 1, 1, 0, (hipStream_t)stream, clock, delta_now);
 }
 
 int gj_pack_f32(int64_t n, const int32_t* index, const float* src, float* out, void* stream) {
   if (n < 0) return GJ_E_RANGE;
   if (n == 0) return GJ_OK;
   if (!index || !src || !out) return GJ_E_NULL;
-  hipLaunchKernelGGL(gj::k_pack, dim3((unsigned)((n + gj::kThreads - 1) / gj::kThreads)), dim3(gj::kThreads), 0,
-                     (hipStream_t)stream, n, index, src, out);
-  return gj::launch_status();
+  return gj::launch(gj::k_pack, gj::grid_for(n), gj::kThreads, 0, (hipStream_t)stream, n, index, src, out);
 }
 
 int gj_unpack_f32(int64_t n, const int32_t* index, const float* in, float* dst, void* stream) {
   if (n < 0) return GJ_E_RANGE;
   if (n == 0) return GJ_OK;
   if (!index || !in || !dst) return GJ_E_NULL;
-  hipLaunchKernelGGL(gj::k_unpack, dim3((unsigned)((n + gj::kThreads - 1) / gj::kThreads)), dim3(gj::kThreads), 0,
-                     (hipStream_t)stream, n, index, in, dst);
-  return gj::launch_status();
+  return gj::launch(gj::k_unpack, gj::grid_for(n), gj::kThreads, 0, (hipStream_t)stream, n, index, in, dst);
 }
 
 int gj_event_create(void** event) {
