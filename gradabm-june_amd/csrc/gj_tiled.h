@@ -8,6 +8,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/gradjune_hip.h"
 #include "gj_device.h"
 
@@ -34,9 +36,6 @@ constexpr int kVenueUnrollC = GJ_VENUE_UNROLL_C;  // same, phase C
 #define GJ_CUM_BATCH 8
 #endif
 constexpr int kCumBatch = GJ_CUM_BATCH;        // venues per lane whose p_contact loads are in flight together (cum write-out)
-#ifndef GJ_DMA_WIDE
-#define GJ_DMA_WIDE 0
-#endif
 
 // LDS float atomics run at 0.33 lanes/clk/CU on gfx950 (measured, tools/microbench/lds_atomics.hip)
 // against 4.9 for ds_add_u64 and 7.3 for ds_add_u32, so the per-venue and per-agent sums are kept
@@ -52,7 +51,7 @@ typedef unsigned long long fx_t;
 template <int BITS>
 __device__ __forceinline__ constexpr float fx_max() { return (float)(1ull << (50 - BITS)); }
 template <int BITS>
-__device__ __forceinline__ fx_t to_fx(float x) {      // |x| <= fx_max<BITS>() (fx_add checks)
+__device__ __forceinline__ fx_t to_fx(float x) {      // |x| <= fx_max<BITS>() (the callers check)
   constexpr double scale = (double)(1ull << BITS);
   constexpr double magic = 6755399441055744.0;       // 1.5 * 2^52
   const double d = __builtin_fma((double)x, scale, magic);
@@ -79,12 +78,6 @@ __device__ __forceinline__ void fx_flag(uint32_t* flags, int words, int i, float
   if (!(x < 0.0f)) atomicOr(&flags[i >> 5], bit);             // positive, +inf or NaN
   if (!(x > 0.0f)) atomicOr(&flags[words + (i >> 5)], bit);   // negative, -inf or NaN
 }
-template <int BITS>
-__device__ __forceinline__ void fx_add(fx_t* sums, uint32_t* flags, int words, int i, float x) {
-  const bool ok = fabsf(x) <= fx_max<BITS>();
-  atomicAdd(&sums[i], to_fx<BITS>(ok ? x : 0.0f));
-  if (__builtin_expect(!ok, 0)) fx_flag(flags, words, i, x);
-}
 __device__ __forceinline__ float fx_special(uint32_t pos, uint32_t neg, float v) {
   return (pos & neg) ? __builtin_nanf("") : (pos ? kSaturated : (neg ? -kSaturated : v));
 }
@@ -94,18 +87,34 @@ __device__ __forceinline__ float fx_read(const fx_t* sums, const uint32_t* flags
   return fx_special(pos, neg, from_fx<BITS>(sums[i]));
 }
 constexpr int kFxVenue = 36, kFxAgent = 32;
+// Whether a value can be summed at all - |x| inside the window, not a NaN - is checked on the BIT PATTERNS: as unsigned
+// integers the patterns of |x| order like the magnitudes, NaN and the infinities above every finite value.  So one
+// maximum over a batch's patterns and one compare decide for the whole batch (the common path stays branch-free).
+__device__ __forceinline__ uint32_t abs_bits(float x) { return __float_as_uint(x) & 0x7FFFFFFFu; }
+template <int N>
+__device__ __forceinline__ uint32_t max_abs_bits(const float (&x)[N]) {
+  uint32_t m = 0u;
+#pragma unroll
+  for (int q = 0; q < N; ++q) m = max(m, abs_bits(x[q]));
+  return m;
+}
+template <int BITS>
+constexpr uint32_t fx_limit_bits() { return (uint32_t)(127 + 50 - BITS) << 23; }      // the pattern of fx_max<BITS>() = 2^(50 - BITS)
+constexpr uint32_t kAgentLimitBits = fx_limit_bits<kFxAgent>();
+static_assert(kAgentLimitBits == 0x48800000u, "the pattern of fx_max<kFxAgent>() = 262144.0f");
 
 // Element `idx` of a wave-uniform array through a 32-bit BYTE offset (scalar base + vector offset addressing: no
 // 64-bit address arithmetic per lane - phases A and D issue instructions, they do not wait).  The array must be
 // smaller than 4 GiB (check_tiled).
 template <typename T>
-__device__ __forceinline__ T at32(const T* base, int idx) {
-  return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + (uint64_t)((uint32_t)idx * (uint32_t)sizeof(T)));
+__device__ __forceinline__ T* elem32(T* base, int idx) {      // (T may be const)
+  using Byte = typename std::conditional<std::is_const<T>::value, const char, char>::type;
+  return reinterpret_cast<T*>(reinterpret_cast<Byte*>(base) + (uint64_t)((uint32_t)idx * (uint32_t)sizeof(T)));
 }
 template <typename T>
-__device__ __forceinline__ void put32(T* base, int idx, T v) {
-  *reinterpret_cast<T*>(reinterpret_cast<char*>(base) + (uint64_t)((uint32_t)idx * (uint32_t)sizeof(T))) = v;
-}
+__device__ __forceinline__ T at32(const T* base, int idx) { return *elem32(base, idx); }
+template <typename T>
+__device__ __forceinline__ void put32(T* base, int idx, T v) { *elem32(base, idx) = v; }
 
 // Non-temporal accesses for the streams that are written once and read once per step and are larger than the caches:
 // the per-edge workspace `val` (B's loads, C's stores, D's loads), the ELL rows of the direct form, the transmission
@@ -117,13 +126,9 @@ typedef float gj_v4f __attribute__((ext_vector_type(4)));
 typedef unsigned int gj_v4u __attribute__((ext_vector_type(4)));
 typedef unsigned int gj_v2u __attribute__((ext_vector_type(2)));
 template <typename T>
-__device__ __forceinline__ T at32nt(const T* base, int idx) {
-  return __builtin_nontemporal_load(reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + (uint64_t)((uint32_t)idx * (uint32_t)sizeof(T))));
-}
+__device__ __forceinline__ T at32nt(const T* base, int idx) { return __builtin_nontemporal_load(elem32(base, idx)); }
 template <typename T>
-__device__ __forceinline__ void put32nt(T* base, int idx, T v) {
-  __builtin_nontemporal_store(v, reinterpret_cast<T*>(reinterpret_cast<char*>(base) + (uint64_t)((uint32_t)idx * (uint32_t)sizeof(T))));
-}
+__device__ __forceinline__ void put32nt(T* base, int idx, T v) { __builtin_nontemporal_store(v, elem32(base, idx)); }
 __device__ __forceinline__ uint4 load_nt(const uint4* p) {
   const gj_v4u v = __builtin_nontemporal_load(reinterpret_cast<const gj_v4u*>(p));
   return make_uint4(v.x, v.y, v.z, v.w);
@@ -214,38 +219,79 @@ __device__ __noinline__ int chunk_slot_walk(const TSetA& T, int row, int i, int 
   return T.tile_jpos[row + j] + (i - T.tile_sptr[row + j]);
 }
 
+// The edges of one (set, slice) in slice-major order - [seg0, seg1) of a_la - and their 64-edge chunks: chunk c holds
+// the edges seg0 + 64 c + lane, its descriptor is chunk_desc[c_base + c].  Functions take it BY VALUE: taken by reference
+// next to their int& outputs, hipcc issued the header's loads again inside phase D's loop (two more dependent global
+// loads per set).  Same-call A/B against the build before the refactor, medians of three rounds on C3: k_tile_agents
+// 164.0 us against 161.7 by reference, 161.5 against 161.1 by value.
+struct Segment {
+  int row, seg0, seg1, c_base, n_chunks;
+  __device__ __forceinline__ Segment(const TSetA& T, int s)
+      : row(s * T.J), seg0(T.tile_sptr[row]), seg1(T.tile_sptr[row + T.J]), c_base(T.chunk_ptr[s]),
+        n_chunks(T.chunk_ptr[s + 1] - c_base) {}
+  // the edge of `lane` in chunk u of the batch that starts at chunk c, and whether there is one
+  __device__ __forceinline__ int edge(int c, int u, int lane) const { return seg0 + (c + u) * kWave + lane; }
+  __device__ __forceinline__ bool has(int c, int u, int lane) const { return (c + u < n_chunks) && (edge(c, u, lane) < seg1); }
+  // clamped into the segment: what the unconditional index loads read where there is no edge
+  __device__ __forceinline__ int edge_clamped(int c, int u, int lane) const { return min(edge(c, u, lane), seg1 - 1); }
+};
+
 // One batch of chunks of a set: the block-major slot of this lane's edge in each of them.  The batch's
 // descriptors are consecutive in memory, so ONE coalesced load brings them in (lane l holds dword l of
 // the batch); each chunk's words are then broadcast with v_readlane into scalars.  Straight-line, so the
 // whole batch is in flight; a wave-uniform branch takes the table walk for batches that contain a chunk
 // the descriptor cannot express.
 template <bool WIDE, int U>
-__device__ __forceinline__ int batch_desc_load(const TSetA& T, int c_base, int n_chunks, int c0, int lane) {
+__device__ __forceinline__ int batch_desc_load(const TSetA& T, const Segment G, int c0, int lane) {
   constexpr int W = WIDE ? 8 : 4;                       // dwords per descriptor
   static_assert(U * W <= kWave, "a batch's descriptors must fit one wave-wide load");
   const int32_t* desc = reinterpret_cast<const int32_t*>(T.chunk_desc);
   const int u_l = min(lane / W, U - 1), k_l = lane % W;
-  return at32(desc, (c_base + min(c0 + u_l, n_chunks - 1)) * W + k_l);
+  return at32(desc, (G.c_base + min(c0 + u_l, G.n_chunks - 1)) * W + k_l);
+}
+// The first of a batch's two memory round trips, shared by phases A and D: the descriptors and the local agent
+// indices of batch c.
+template <bool WIDE, int kU>
+__device__ __forceinline__ void batch_stage1(const TSetA& T, const Segment G, int c, int lane, int& word, int (&la)[kU]) {
+  const int cc = min(c, G.n_chunks - 1);                      // past the end: a harmless re-load of the last chunk
+  word = batch_desc_load<WIDE, kU>(T, G, cc, lane);           // first: the slots wait on it
+#pragma unroll
+  for (int u = 0; u < kU; ++u) la[u] = at32(T.a_la, G.edge_clamped(cc, u, lane));
 }
 
+// The descriptor of chunk u of a batch, broadcast into scalars from the lanes that loaded it (batch_desc_load), and
+// THE place that turns it into this lane's slot.
+template <bool WIDE>
+struct ChunkDesc {
+  static constexpr int W = WIDE ? 8 : 4;
+  int w[W];
+  __device__ __forceinline__ ChunkDesc(int word, int u) {
+#pragma unroll
+    for (int k = 0; k < W; ++k) w[k] = __builtin_amdgcn_readlane(word, u * W + k);
+  }
+  // the chunk spans more tiles than the descriptor expresses: slot() does not hold; j0 is its row of multi_slots or -
+  // in a plan without the rows - the block from which its lanes walk the tile tables
+  __device__ __forceinline__ bool multi() const { return WIDE ? ((w[W - 1] & 0x100) != 0) : ((w[2] >> 16) != 0); }
+  __device__ __forceinline__ int j0() const { return WIDE ? (int)((unsigned)w[W - 1] >> 9) : w[3]; }
+  __device__ __forceinline__ int slot(int lane) const {
+    if constexpr (WIDE) {
+      return chunk_slot_wide(make_int4(w[0], w[1], w[2], w[3]), make_int4(w[4], w[5], w[6], w[7]), lane);
+    } else {
+      return chunk_slot_fast(make_int4(w[0], w[1], w[2], 0), lane);
+    }
+  }
+};
+
 template <bool WIDE, int U>
-__device__ __forceinline__ void batch_slots(const TSetA& T, const int word, int row, int seg0, int seg1, int c0,
-                                            int lane, int (&slot)[U]) {
+__device__ __forceinline__ void batch_slots(const TSetA& T, const Segment G, const int word, int c0, int lane,
+                                            int (&slot)[U]) {
   constexpr int W = WIDE ? 8 : 4;
   const int k_l = lane % W;
   const bool flag = WIDE ? (k_l == 7 && (word & 0x100)) : (k_l == 2 && (word >> 16));
   const bool any_multi = __builtin_amdgcn_ballot_w64(flag) != 0ull;
-#define GJ_DW(u, k) __builtin_amdgcn_readlane(word, (u) * W + (k))
   if (!any_multi) {
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
-      if (!WIDE) {
-        slot[u] = chunk_slot_fast(make_int4(GJ_DW(u, 0), GJ_DW(u, 1), GJ_DW(u, 2), 0), lane);
-      } else {
-        slot[u] = chunk_slot_wide(make_int4(GJ_DW(u, 0), GJ_DW(u, 1), GJ_DW(u, 2), GJ_DW(u, 3)),
-                                  make_int4(GJ_DW(u, 4), GJ_DW(u, 5), GJ_DW(u, 6), GJ_DW(u, 7)), lane);
-      }
-    }
+    for (int u = 0; u < U; ++u) slot[u] = ChunkDesc<WIDE>(word, u).slot(lane);
   } else if (T.multi_slots) {
     // A batch that holds a chunk its descriptor cannot express (more tiles than segments): that chunk's lanes take
     // their slots from row j0 of multi_slots.  Branch-free: EVERY chunk of the batch issues the load (row 0 where it is
@@ -255,101 +301,65 @@ __device__ __forceinline__ void batch_slots(const TSetA& T, const int word, int 
     bool mu[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-      const int w = WIDE ? GJ_DW(u, 7) : GJ_DW(u, 2);
-      mu[u] = WIDE ? ((w & 0x100) != 0) : ((w >> 16) != 0);
-      const int j0 = WIDE ? (int)((unsigned)w >> 9) : GJ_DW(u, 3);
-      ms[u] = at32(T.multi_slots, (mu[u] ? j0 : 0) * kWave + lane);
+      const ChunkDesc<WIDE> d(word, u);
+      mu[u] = d.multi();
+      ms[u] = at32(T.multi_slots, (mu[u] ? d.j0() : 0) * kWave + lane);
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-      int f;
-      if (!WIDE) {
-        f = chunk_slot_fast(make_int4(GJ_DW(u, 0), GJ_DW(u, 1), GJ_DW(u, 2), 0), lane);
-      } else {
-        f = chunk_slot_wide(make_int4(GJ_DW(u, 0), GJ_DW(u, 1), GJ_DW(u, 2), GJ_DW(u, 3)),
-                            make_int4(GJ_DW(u, 4), GJ_DW(u, 5), GJ_DW(u, 6), GJ_DW(u, 7)), lane);
-      }
+      const int f = ChunkDesc<WIDE>(word, u).slot(lane);
       slot[u] = mu[u] ? ms[u] : f;
     }
   } else {
     // a plan without the rows (rounds 1-3): the lanes of such a chunk walk the tile tables
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-      const int i = min(seg0 + (c0 + u) * kWave + lane, seg1 - 1);
-      if (!WIDE) {
-        const int4 d = make_int4(GJ_DW(u, 0), GJ_DW(u, 1), GJ_DW(u, 2), GJ_DW(u, 3));
-        slot[u] = (d.z >> 16) ? chunk_slot_slow(T, d, row, i, lane) : chunk_slot_fast(d, lane);
+      const int i = G.edge_clamped(c0, u, lane);
+      const ChunkDesc<WIDE> d(word, u);
+      if constexpr (WIDE) {
+        slot[u] = d.multi() ? chunk_slot_walk(T, G.row, i, d.j0()) : d.slot(lane);
       } else {
-        const int4 d0 = make_int4(GJ_DW(u, 0), GJ_DW(u, 1), GJ_DW(u, 2), GJ_DW(u, 3));
-        const int4 d1 = make_int4(GJ_DW(u, 4), GJ_DW(u, 5), GJ_DW(u, 6), GJ_DW(u, 7));
-        slot[u] = (d1.w & 0x100) ? chunk_slot_walk(T, row, i, (int)((unsigned)d1.w >> 9))
-                                 : chunk_slot_wide(d0, d1, lane);
+        slot[u] = d.multi() ? chunk_slot_slow(T, make_int4(d.w[0], d.w[1], d.w[2], d.w[3]), G.row, i, lane) : d.slot(lane);
       }
     }
   }
-#undef GJ_DW
 }
 
 // Phase A's inner loop for one set.  The kernel is bound by loads in flight (one workgroup of 16 waves per CU),
 // so besides the 16-chunk batches the loop is software-pipelined: batch k+1's index / descriptor loads are
 // issued before batch k's values are read from LDS and stored (vmcnt counts in order, so waiting for batch k
 // leaves them in flight).  Two register sets alternate so that nothing is copied.
-#ifndef GJ_SCATTER_PIPELINE
-#define GJ_SCATTER_PIPELINE 1
-#endif
 template <bool WIDE, int kU, bool NT = false>
 __device__ __forceinline__ void scatter_batches(const TSetA& T, const float* lds_x, int s, int wave, int lane) {
-  const int row = s * T.J;
-  const int seg0 = T.tile_sptr[row], seg1 = T.tile_sptr[row + T.J];
-  const int c_base = T.chunk_ptr[s];
-  const int n_chunks = T.chunk_ptr[s + 1] - c_base;
+  const Segment G(T, s);
   constexpr int kStride = kTileWaves * kU;
-  auto stage1 = [&](int c, int& word, int (&la)[kU]) {        // descriptors + local agent indices of batch c
-    const int cc = min(c, n_chunks - 1);                      // past the end: a harmless re-load of the last chunk
-    word = batch_desc_load<WIDE, kU>(T, c_base, n_chunks, cc, lane);   // first: the slots wait on it
-#pragma unroll
-    for (int u = 0; u < kU; ++u) la[u] = at32(T.a_la, min(seg0 + (cc + u) * kWave + lane, seg1 - 1));
-  };
+  auto stage1 = [&](int c, int& word, int (&la)[kU]) { batch_stage1<WIDE, kU>(T, G, c, lane, word, la); };
   auto stage2 = [&](int c, int word, const int (&la)[kU]) {
     int slot[kU];
-    batch_slots<WIDE, kU>(T, word, row, seg0, seg1, c, lane, slot);
-#ifdef GJ_DIAG_EXTRA_VALU      // diagnostics (tools/ab.py): N no-op VALU instructions per edge - is the launch bound by instruction issue?
-#pragma unroll
-    for (int u = 0; u < kU; ++u)
-#pragma unroll
-      for (int r = 0; r < GJ_DIAG_EXTRA_VALU; ++r) asm volatile("v_add_u32 %0, %0, 0" : "+v"(slot[u]));
-#endif
+    batch_slots<WIDE, kU>(T, G, word, c, lane, slot);
 #pragma unroll
     for (int u = 0; u < kU; ++u) {
-      const int i = seg0 + (c + u) * kWave + lane;
-      if ((c + u < n_chunks) && (i < seg1)) {
+      if (G.has(c, u, lane)) {
         if (NT) put32nt(T.val, slot[u], lds_x[la[u]]); else put32(T.val, slot[u], lds_x[la[u]]);
       }
     }
   };
   int c0 = wave * kU;
-  if (c0 >= n_chunks) return;
+  if (c0 >= G.n_chunks) return;
   int laA[kU], wordA;
-#if GJ_SCATTER_PIPELINE
   int laB[kU], wordB;
   stage1(c0, wordA, laA);
   while (true) {
     const int c1 = c0 + kStride;
     stage1(c1, wordB, laB);
     stage2(c0, wordA, laA);
-    if (c1 >= n_chunks) break;
+    if (c1 >= G.n_chunks) break;
     const int c2 = c1 + kStride;
     stage1(c2, wordA, laA);
     stage2(c1, wordB, laB);
-    if (c2 >= n_chunks) break;
+    if (c2 >= G.n_chunks) break;
     c0 = c2;
   }
-#else
-  for (; c0 < n_chunks; c0 += kStride) {
-    stage1(c0, wordA, laA);
-    stage2(c0, wordA, laA);
-  }
-#endif
 }
 
 // 16-chunk batches pay off when a slice has several hundred chunks of the set to stream (C3 at 10 M agents: 459,
@@ -376,84 +386,60 @@ __device__ __forceinline__ void scatter_set(const TSetA& T, const float* lds_x, 
   }
 }
 
+// A batch's values into the per-agent fixed-point sums.  Straight-line: every lane adds (0 where there is no edge; la
+// is a valid local index either way); the batch that holds a value which cannot be summed - |x| > 262144 or a NaN,
+// max_abs_bits - takes the per-element form and flags the agent.
+template <int kU>
+__device__ __forceinline__ void agent_add_batch(fx_t* lds_acc, uint32_t* lds_flags, int flag_words, const int (&la)[kU],
+                                                const float (&x)[kU]) {
+  if (__builtin_expect(max_abs_bits(x) <= kAgentLimitBits, 1)) {
+#pragma unroll
+    for (int u = 0; u < kU; ++u) atomicAdd(&lds_acc[la[u]], to_fx<kFxAgent>(x[u]));
+  } else {
+#pragma unroll
+    for (int u = 0; u < kU; ++u) {
+      if (abs_bits(x[u]) <= kAgentLimitBits) {
+        atomicAdd(&lds_acc[la[u]], to_fx<kFxAgent>(x[u]));
+      } else {
+        fx_flag(lds_flags, flag_words, la[u], x[u]);
+      }
+    }
+  }
+}
+
 // Phase D's inner loop for one set.  (Measured, not adopted: software-pipelining this loop - the next batch's
 // index / descriptor loads issued behind the current value loads - and 16 instead of 8 chunks per batch both
-// left the kernel at 0.25 ms on C3: it is bound by the ~0.5 KB granularity of the per-tile value reads.)
+// left the kernel at 0.25 ms on C3: it is bound by the ~0.5 KB granularity of the per-tile value reads.  That was
+// before the adds became branch-free; the pipeline below, with a batch's value loads issued first, came after.)
 #ifndef GJ_UNROLL_D_NARROW
 #define GJ_UNROLL_D_NARROW 8       // chunks in flight per wave on sets with 16-byte descriptors (16: 8 % slower, registers)
-#endif
-#ifndef GJ_GATHER_PIPELINE
-#define GJ_GATHER_PIPELINE 1
 #endif
 template <bool WIDE>
 __device__ __forceinline__ void gather_set(const TSetA& T, fx_t* lds_acc, uint32_t* lds_flags, int flag_words, int s,
                                            int wave, int lane) {
-  const int row = s * T.J;
-  const int seg0 = T.tile_sptr[row], seg1 = T.tile_sptr[row + T.J];
-  const int c_base = T.chunk_ptr[s];
-  const int n_chunks = T.chunk_ptr[s + 1] - c_base;
+  const Segment G(T, s);
   constexpr int kU = WIDE ? kUnroll : GJ_UNROLL_D_NARROW;
   constexpr int kStride = kTileWaves * kU;
   // A batch costs two dependent memory round trips (descriptors + local agent indices, then the values at the slots
   // the descriptors give), ~2 us each while every CU streams.  The next batch's first trip is issued before the
   // current batch's values are waited for (vmcnt counts in order), so a batch costs one.
-  auto stage1 = [&](int c, int& word, int (&la)[kU]) {        // descriptors + local agent indices of batch c
-    const int cc = min(c, n_chunks - 1);                      // past the end: a harmless re-load of the last chunk
-    word = batch_desc_load<WIDE, kU>(T, c_base, n_chunks, cc, lane);
-#pragma unroll
-    for (int u = 0; u < kU; ++u) la[u] = at32(T.a_la, min(seg0 + (cc + u) * kWave + lane, seg1 - 1));
-  };
+  auto stage1 = [&](int c, int& word, int (&la)[kU]) { batch_stage1<WIDE, kU>(T, G, c, lane, word, la); };
   auto values = [&](int c, int word, float (&v)[kU]) {        // the batch's value loads (issued, not waited for)
     int slot[kU];
-    batch_slots<WIDE, kU>(T, word, row, seg0, seg1, c, lane, slot);
+    batch_slots<WIDE, kU>(T, G, word, c, lane, slot);
 #pragma unroll
-    for (int u = 0; u < kU; ++u) {
-      const int i = seg0 + (c + u) * kWave + lane;
-      const bool ok = (c + u < n_chunks) && (i < seg1);
-      v[u] = at32nt(T.val, ok ? slot[u] : 0);
-    }
+    for (int u = 0; u < kU; ++u) v[u] = at32nt(T.val, G.has(c, u, lane) ? slot[u] : 0);
   };
   auto add = [&](int c, const int (&la)[kU], const float (&v)[kU]) {
-    // straight-line: every lane adds (0 where there is no edge; la is a valid local index either way).  Whether a value
-    // can be summed at all - |x| <= 262144, not a NaN - is checked once per batch on the bit patterns (as unsigned
-    // integers they order like the magnitudes, NaN and the infinities above every finite value); the batch that holds
-    // such a value takes the per-element form and flags the agent
-    constexpr uint32_t kLimit = 0x48800000u;            // bit pattern of fx_max<kFxAgent>() = 262144.0f
-    static_assert(kFxAgent == 32, "kLimit is the pattern of 2^(50 - kFxAgent)");
     float x[kU];
-    uint32_t m = 0u;
 #pragma unroll
-    for (int u = 0; u < kU; ++u) {
-      const int i = seg0 + (c + u) * kWave + lane;
-      const bool edge = (c + u < n_chunks) && (i < seg1);
-      x[u] = edge ? v[u] : 0.0f;
-      m = max(m, __float_as_uint(x[u]) & 0x7FFFFFFFu);
-    }
-#ifdef GJ_DIAG_EXTRA_VALU
-#pragma unroll
-    for (int u = 0; u < kU; ++u)
-#pragma unroll
-      for (int r = 0; r < GJ_DIAG_EXTRA_VALU; ++r) asm volatile("v_add_f32 %0, %0, 0" : "+v"(x[u]));
-#endif
-    if (__builtin_expect(m <= kLimit, 1)) {
-#pragma unroll
-      for (int u = 0; u < kU; ++u) atomicAdd(&lds_acc[la[u]], to_fx<kFxAgent>(x[u]));
-    } else {
-#pragma unroll
-      for (int u = 0; u < kU; ++u) {
-        if ((__float_as_uint(x[u]) & 0x7FFFFFFFu) <= kLimit) {
-          atomicAdd(&lds_acc[la[u]], to_fx<kFxAgent>(x[u]));
-        } else {
-          fx_flag(lds_flags, flag_words, la[u], x[u]);
-        }
-      }
-    }
+    for (int u = 0; u < kU; ++u) x[u] = G.has(c, u, lane) ? v[u] : 0.0f;
+    agent_add_batch<kU>(lds_acc, lds_flags, flag_words, la, x);
   };
   int c0 = wave * kU;
-  if (c0 >= n_chunks) return;
+  if (c0 >= G.n_chunks) return;
   int laA[kU], wordA;
   float v[kU];
-#if GJ_GATHER_PIPELINE
   int laB[kU], wordB;
   stage1(c0, wordA, laA);
   while (true) {
@@ -461,21 +447,14 @@ __device__ __forceinline__ void gather_set(const TSetA& T, fx_t* lds_acc, uint32
     values(c0, wordA, v);
     stage1(c1, wordB, laB);           // behind the value loads: in flight while they are waited for and added
     add(c0, laA, v);
-    if (c1 >= n_chunks) break;
+    if (c1 >= G.n_chunks) break;
     const int c2 = c1 + kStride;
     values(c1, wordB, v);
     stage1(c2, wordA, laA);
     add(c1, laB, v);
-    if (c2 >= n_chunks) break;
+    if (c2 >= G.n_chunks) break;
     c0 = c2;
   }
-#else
-  for (; c0 < n_chunks; c0 += kStride) {
-    stage1(c0, wordA, laA);
-    values(c0, wordA, v);
-    add(c0, laA, v);
-  }
-#endif
 }
 
 // Sets whose tiles hold a handful of edges (a rank's halo half of a heavy-tailed set, a 1e8-agent world in one
@@ -484,66 +463,40 @@ __device__ __forceinline__ void gather_set(const TSetA& T, fx_t* lds_acc, uint32
 // for its phase B).  Such a set carries the slot of every edge explicitly instead: 4 more bytes per edge and pass,
 // coalesced, straight-line.
 template <int kU>
-__device__ __forceinline__ void scatter_explicit(const TSetA& T, const float* lds_x, int s, int wave, int lane) {
-  const int row = s * T.J;
-  const int seg0 = T.tile_sptr[row], seg1 = T.tile_sptr[row + T.J];
-  const int n_chunks = T.chunk_ptr[s + 1] - T.chunk_ptr[s];
+__device__ __forceinline__ void explicit_stage1(const TSetA& T, const Segment G, int c0, int lane, int (&la)[kU], int (&sl)[kU]) {
   const int32_t* slots = reinterpret_cast<const int32_t*>(T.chunk_desc);
-  for (int c0 = wave * kU; c0 < n_chunks; c0 += kTileWaves * kU) {
+#pragma unroll
+  for (int u = 0; u < kU; ++u) {
+    const int i = G.edge_clamped(c0, u, lane);
+    la[u] = at32(T.a_la, i);
+    sl[u] = at32(slots, i);
+  }
+}
+template <int kU>
+__device__ __forceinline__ void scatter_explicit(const TSetA& T, const float* lds_x, int s, int wave, int lane) {
+  const Segment G(T, s);
+  for (int c0 = wave * kU; c0 < G.n_chunks; c0 += kTileWaves * kU) {
     int la[kU], sl[kU];
+    explicit_stage1<kU>(T, G, c0, lane, la, sl);
 #pragma unroll
-    for (int u = 0; u < kU; ++u) {
-      const int i = min(seg0 + (c0 + u) * kWave + lane, seg1 - 1);
-      la[u] = at32(T.a_la, i);
-      sl[u] = at32(slots, i);
-    }
-#pragma unroll
-    for (int u = 0; u < kU; ++u) {
-      const int i = seg0 + (c0 + u) * kWave + lane;
-      if ((c0 + u < n_chunks) && (i < seg1)) put32(T.val, sl[u], lds_x[la[u]]);
-    }
+    for (int u = 0; u < kU; ++u)
+      if (G.has(c0, u, lane)) put32(T.val, sl[u], lds_x[la[u]]);
   }
 }
 
 template <int kU>
 __device__ __forceinline__ void gather_explicit(const TSetA& T, fx_t* lds_acc, uint32_t* lds_flags, int flag_words, int s,
                                                 int wave, int lane) {
-  const int row = s * T.J;
-  const int seg0 = T.tile_sptr[row], seg1 = T.tile_sptr[row + T.J];
-  const int n_chunks = T.chunk_ptr[s + 1] - T.chunk_ptr[s];
-  const int32_t* slots = reinterpret_cast<const int32_t*>(T.chunk_desc);
-  constexpr uint32_t kLimit = 0x48800000u;              // fx_max<kFxAgent>() = 262144.0f (see gather_set)
-  for (int c0 = wave * kU; c0 < n_chunks; c0 += kTileWaves * kU) {
+  const Segment G(T, s);
+  for (int c0 = wave * kU; c0 < G.n_chunks; c0 += kTileWaves * kU) {
     int la[kU], sl[kU];
-#pragma unroll
-    for (int u = 0; u < kU; ++u) {
-      const int i = min(seg0 + (c0 + u) * kWave + lane, seg1 - 1);
-      la[u] = at32(T.a_la, i);
-      sl[u] = at32(slots, i);
-    }
+    explicit_stage1<kU>(T, G, c0, lane, la, sl);
     float x[kU];
 #pragma unroll
     for (int u = 0; u < kU; ++u) x[u] = at32(T.val, sl[u]);
-    uint32_t m = 0u;
 #pragma unroll
-    for (int u = 0; u < kU; ++u) {
-      const int i = seg0 + (c0 + u) * kWave + lane;
-      x[u] = ((c0 + u < n_chunks) && (i < seg1)) ? x[u] : 0.0f;
-      m = max(m, __float_as_uint(x[u]) & 0x7FFFFFFFu);
-    }
-    if (__builtin_expect(m <= kLimit, 1)) {
-#pragma unroll
-      for (int u = 0; u < kU; ++u) atomicAdd(&lds_acc[la[u]], to_fx<kFxAgent>(x[u]));
-    } else {
-#pragma unroll
-      for (int u = 0; u < kU; ++u) {
-        if ((__float_as_uint(x[u]) & 0x7FFFFFFFu) <= kLimit) {
-          atomicAdd(&lds_acc[la[u]], to_fx<kFxAgent>(x[u]));
-        } else {
-          fx_flag(lds_flags, flag_words, la[u], x[u]);
-        }
-      }
-    }
+    for (int u = 0; u < kU; ++u) x[u] = G.has(c0, u, lane) ? x[u] : 0.0f;
+    agent_add_batch<kU>(lds_acc, lds_flags, flag_words, la, x);
   }
 }
 
@@ -619,6 +572,29 @@ struct TileBArgs {
   int32_t _pad;
 };
 
+// The two class weights of a leisure network for agent class c (sex * 100 + age) on a day type: l, the table's entry,
+// and lw, the same with the network's age > 75 mask.  The forward weighs the transmitting side (pass 1) with l and the
+// receiving side (pass 2) with lw.
+struct ClassWeights {
+  float l, lw;
+};
+__device__ __forceinline__ ClassWeights class_weights(const float* tables, int table, int age75, int day_type, int c) {
+  const float l = tables[(int64_t)table * GJ_TABLE_SIZE + day_type * 200 + c];
+  return {l, age75 ? l * (((c % 100) > 75) ? 1.0f : 0.0f) : l};
+}
+// [nk][200] weights of a set's networks (TSet: TSetB, TPSet or TDirect) for the transmitting and / or the receiving side
+// (template arguments: which are wanted) - THE place where `transpose` exchanges the two (backward pass).
+template <bool TRANSMITTING, bool RECEIVING, typename TSet>
+__device__ __forceinline__ void fill_class_weights(float* transmitting, float* receiving, const TSet& T, const float* tables,
+                                                   int day_type, int transpose, int tid) {
+  for (int i = tid; i < T.nk * 200; i += kTileThreads) {
+    const int k = i / 200, c = i % 200;
+    const ClassWeights w = class_weights(tables, T.table[k], T.age75[k], day_type, c);
+    if (TRANSMITTING) transmitting[i] = transpose ? w.lw : w.l;
+    if (RECEIVING) receiving[i] = transpose ? w.l : w.lw;
+  }
+}
+
 // Phase B, a group of 8 slots that holds a value which cannot be summed (rare; kept out of line so that its registers
 // do not count against the launch's two workgroups per CU).
 __device__ __noinline__ void venue_group_slow(fx_t* sums, uint32_t* vflags, int words, uint32_t limit, int base_k, int l0,
@@ -629,7 +605,7 @@ __device__ __noinline__ void venue_group_slow(fx_t* sums, uint32_t* vflags, int 
 #pragma unroll
   for (int q = 0; q < 8; ++q) {
     if (lv[q] == 0xFFFF) continue;
-    if ((__float_as_uint(x[q]) & 0x7FFFFFFFu) <= limit) {      // |x| inside the set's window (<= 16384 = fx_max<kFxVenue>())
+    if (abs_bits(x[q]) <= limit) {      // |x| inside the set's window (<= 16384 = fx_max<kFxVenue>())
       atomicAdd(&sums[base_k + lv[q]], to_fx<kFxVenue>(x[q]));
     } else {
       fx_flag(vflags, words, base_k + lv[q], x[q]);
@@ -637,13 +613,37 @@ __device__ __noinline__ void venue_group_slow(fx_t* sums, uint32_t* vflags, int 
   }
 }
 
-struct Slots8 {           // 8 consecutive block-major slots: 16 bytes of local venue indices
-  uint32_t w[4];
+// the class (sex * 100 + age) of agent j of the four whose classes one dword holds
+__device__ __forceinline__ int class_byte(uint32_t four, int j) { return (four >> (8 * j)) & 0xFF; }
+
+// 8 consecutive block-major slots: 16 bytes of local venue indices (0xFFFF: a pad slot), their values (phase B) and
+// 8 bytes of agent classes (leisure sets).
+struct Group8 {
+  uint32_t w[4], c[2];
+  float v[8];
+  __device__ __forceinline__ Group8(uint4 raw, uint2 craw, float4 xa = make_float4(0.0f, 0.0f, 0.0f, 0.0f),
+                                    float4 xb = make_float4(0.0f, 0.0f, 0.0f, 0.0f))
+      : w{raw.x, raw.y, raw.z, raw.w}, c{craw.x, craw.y}, v{xa.x, xa.y, xa.z, xa.w, xb.x, xb.y, xb.z, xb.w} {}
   __device__ __forceinline__ int lv(int q) const { return (w[q >> 1] >> ((q & 1) * 16)) & 0xFFFF; }
+  __device__ __forceinline__ float x(int q) const { return v[q]; }
+  __device__ __forceinline__ int cls(int q) const { return class_byte(c[q >> 2], q & 3); }
+  __device__ __forceinline__ void drop(int q) { w[q >> 1] |= 0xFFFFu << ((q & 1) * 16); }      // slot q becomes a pad slot
+  // all eight slots belong to one venue (every word the same, both halves of a word equal) and are not padding
+  __device__ __forceinline__ bool one_venue() const {
+    return (w[0] == w[1]) && (w[1] == w[2]) && (w[2] == w[3]) && ((w[0] >> 16) == (w[0] & 0xFFFFu)) && (lv(0) != 0xFFFF);
+  }
+  // the same slots with every value weighted by its agent's class (tk: one network's [200] weights)
+  __device__ __forceinline__ Group8 weighted(const float* tk) const {
+    Group8 g = *this;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) g.v[q] = tk[cls(q)] * v[q];
+    return g;
+  }
 };
 
+// timing diagnostics (tools/venue_timeline.py, a -DGJ_DIAG_STAMPS build): start / end time and XCD of every workgroup
+// of the last venue launch
 #ifdef GJ_DIAG_STAMPS
-// timing diagnostics (tools/venue_timeline.py): start / end time and XCD of every workgroup of the last venue launch
 constexpr int kDiagVenueSlots = 8192;
 __device__ unsigned long long gj_diag_venue[3 * kDiagVenueSlots];
 struct VenueStamp {
@@ -657,7 +657,251 @@ struct VenueStamp {
     }
   }
 };
+#else
+struct VenueStamp {};
 #endif
+
+// One (set, venue block) work item of the venue launch: the geometry every phase of the workgroup reads, and the layout
+// of the item's LDS.  The phases hand their results on through that LDS only, and each takes the arrays it reads or
+// writes as arguments: `sums` / `vflags` (phase B -> cum write-out), `cumf` (cum write-out or read-back -> phase C),
+// `tabs` (table set-up -> phases B and C).
+struct VenueItem {
+  const TSetB& T;
+  int tid, nk;
+  int v0, nv;               // the block's venues [v0, v0 + nv)
+  int g0, g1;               // its groups of 8 slots
+  fx_t* sums;               // [nk][nv] fixed-point sums (phase B), then 64 scratch sums, one per lane of a wave
+  float* cumf;              // cum of (k, lv) at float index 2 * (k * nv + lv): the low half of its sum's slot (phase C)
+  float* tabs;              // leisure: [nk][200] pass-1 weights, then [nk][200] pass-2 weights
+  uint32_t* vflags;         // two bits per sum (fx_flag)
+  int vwords;
+  int dummy;                // the lane's scratch sum: what does not count is added there
+  __device__ __forceinline__ VenueItem(const TSetB& T_, int j, float* lds, int tid_)
+      : T(T_), tid(tid_), nk(T_.nk), v0(T_.blk_v0[j]), nv(T_.blk_v0[j + 1] - v0), g0(T_.blk_e0[j] >> 3),
+        g1(T_.blk_e0[j + 1] >> 3), sums(reinterpret_cast<fx_t*>(lds)), cumf(lds), tabs(lds + 2 * ((size_t)nk * nv + 64)),
+        vflags(reinterpret_cast<uint32_t*>(tabs + (T_.leisure ? 2 * nk * 200 : 0))), vwords((nk * nv + 64 + 31) / 32),
+        dummy(nk * nv + (tid_ & 63)) {}
+  __device__ __forceinline__ const uint4* lv8() const { return reinterpret_cast<const uint4*>(T.e_lv); }
+  __device__ __forceinline__ const uint2* cls8() const { return reinterpret_cast<const uint2*>(T.e_cls); }
+  __device__ __forceinline__ float4* val4() const { return reinterpret_cast<float4*>(T.val); }
+};
+
+// Phase B, one group of one network (sums at base_k).  Straight-line: a run of one venue is summed left to right in a
+// register and added where the run ends; every slot position issues an add, the ones that are not the end of a run (or
+// are padding) add to a scratch slot of the lane's own.  (Branches per slot made this launch issue three times the
+// instructions: it is bound by instruction issue, SQ_ACTIVE_INST_ANY x waves per SIMD ~ 0.8.)
+// Every slot's value goes to fixed point FIRST and a run of one venue is merged as integers: exact, so a venue's sum
+// does not depend on where the block boundaries and the padding put its runs relative to the 8-slot groups - the
+// tile geometry (eb_target, sv_max, slices) and the partition cannot change a single bit of `cum`.  (Round 2 merged
+// the runs in fp32 and converted the run totals: 8-18 us faster on C3 from box to box and not
+// exact.  Measured and ruled out as the cause of that gap, tools/ab.py: instruction count - this form has 12 per slot
+// against 19 -, zero / non-zero scratch adds, LDS operations in flight, registers reused behind an LDS operation.)
+// The range check is made ONCE per group on the bit patterns (max_abs_bits), and a slot that is not the end of a run
+// adds whatever the running sum is to the lane's scratch sum instead of selecting a zero.
+__device__ __forceinline__ void run_sums(const VenueItem& W, const Group8& G, int base_k, fx_t* sums, uint32_t* vflags) {
+  // (wave-uniform, at most the pattern of fx_max<kFxVenue>() = 16384.0f; smaller for a set with venues of more than
+  // 4 096 attendees, so that attendees x window stays inside the 64-bit sum: no sum can wrap)
+  const uint32_t kLimit = W.T.term_limit;
+  static_assert(kFxVenue == 36, "term_limit is derived from 2^(50 - kFxVenue) (fill_set_b)");
+  if (__builtin_expect(max_abs_bits(G.v) > kLimit, 0)) {            // a NaN / infinity / out-of-window term: saturates or poisons its venue
+    venue_group_slow(sums, vflags, W.vwords, kLimit, base_k, G.lv(0), G.lv(1), G.lv(2), G.lv(3), G.lv(4), G.lv(5),
+                     G.lv(6), G.lv(7), G.x(0), G.x(1), G.x(2), G.x(3), G.x(4), G.x(5), G.x(6), G.x(7));
+    return;
+  }
+  fx_t s8 = 0;
+#pragma unroll
+  for (int q = 0; q < 8; ++q) {
+    const fx_t f = to_fx<kFxVenue>(G.x(q));
+    const bool first = (q == 0) || (G.lv(q) != G.lv(q - (q > 0)));
+    s8 = first ? f : s8 + f;
+    const bool last = (q == 7) || (G.lv(q + (q < 7)) != G.lv(q));
+    const bool take = last && G.lv(q) != 0xFFFF;
+    atomicAdd(&sums[take ? base_k + G.lv(q) : W.dummy], s8);
+  }
+}
+// 512 consecutive slots of ONE venue (a wave's 64 groups): the slots' fixed-point terms are added up per lane, then
+// across the wave (integer adds: the same sum, bit for bit), and ONE lane adds the total - instead of 512 LDS
+// atomics per network of which 448 go to scratch sums and 64 to one address.  What makes the case common: venues far
+// larger than a tile's width - the leisure venues of a JUNE world (every resident of the k nearest super areas:
+// 15 000 attendees, six networks per slot), the giant venues of BASELINE config 5, schools on a world with a geography.
+// (Same-call A/B against the build without it: the june preset 440 -> 401 us per step.)
+__device__ __forceinline__ bool one_venue_sum(const VenueItem& W, const Group8& G, int target, fx_t* sums) {      // false: a term outside the window - generic path
+  if (__builtin_amdgcn_ballot_w64(max_abs_bits(G.v) > W.T.term_limit) != 0ull) return false;
+  fx_t s = 0;
+#pragma unroll
+  for (int q = 0; q < 8; ++q) s += to_fx<kFxVenue>(G.x(q));
+  s = wave_sum<fx_t>(s);
+  if ((W.tid & (kWave - 1)) == 0) atomicAdd(&sums[target], s);
+  return true;
+}
+
+__device__ __forceinline__ void venue_zero(const VenueItem& W, fx_t* sums, uint32_t* vflags) {
+  for (int i = W.tid; i < W.nk * W.nv + 64; i += kTileThreads) sums[i] = 0;
+  for (int i = W.tid; i < 2 * W.vwords; i += kTileThreads) vflags[i] = 0u;
+}
+
+// Phase B over the block's tiled groups: each lane takes 8 consecutive slots (48 bytes), merges runs of one venue in
+// registers and adds each run to the block's LDS sums; kVenueUnroll such groups are loaded before the first is used.
+__device__ __forceinline__ void venue_sums_tiled(const VenueItem& W, const float* weights, fx_t* sums, uint32_t* vflags) {
+  const TSetB& T = W.T;
+  auto add_group = [&](const Group8& G) {
+    // every lane of the wave, all of them active, holds eight slots of the same venue
+    const bool mine = G.one_venue() && (G.lv(0) == __builtin_amdgcn_readfirstlane(G.lv(0)));
+    const bool one_venue = __builtin_amdgcn_ballot_w64(mine) == ~0ull;
+    if (!T.leisure) {
+      if (!(one_venue && one_venue_sum(W, G, G.lv(0), sums))) run_sums(W, G, 0, sums, vflags);
+    } else {
+      for (int k = 0; k < W.nk; ++k) {
+        const Group8 Gk = G.weighted(weights + k * 200);
+        if (!(one_venue && one_venue_sum(W, Gk, k * W.nv + G.lv(0), sums))) run_sums(W, Gk, k * W.nv, sums, vflags);
+      }
+    }
+  };
+  for (int g = W.g0 + W.tid; g < W.g1; g += kVenueUnroll * kTileThreads) {
+    uint4 raw[kVenueUnroll];
+    float4 xa[kVenueUnroll], xb[kVenueUnroll];
+    uint2 craw[kVenueUnroll];
+#pragma unroll
+    for (int u = 0; u < kVenueUnroll; ++u) {     // clamped, unconditional: all loads in flight together
+      const int gu = min(g + u * kTileThreads, W.g1 - 1);
+      raw[u] = W.lv8()[gu];
+      xa[u] = load_nt(W.val4() + 2 * gu);        // read once, written by phase A: non-temporal
+      xb[u] = load_nt(W.val4() + 2 * gu + 1);
+      craw[u] = T.leisure ? W.cls8()[gu] : make_uint2(0u, 0u);
+    }
+#pragma unroll
+    for (int u = 0; u < kVenueUnroll; ++u)
+      if (g + u * kTileThreads < W.g1) add_group(Group8(raw[u], craw[u], xa[u], xb[u]));
+  }
+}
+
+// Phase B over the block's run-form groups: the agents [r0, r1) have their primary venue in this block; agent a is a
+// slot with value x[a] and local venue pv_blk[a] - the same straight-line groups of 8 as above, read from the per-agent
+// arrays themselves (consecutive agents of one venue are a run).  Agents of the neighbouring blocks in the first / last
+// group are masked; the last group of the world may reach past x.
+__device__ __forceinline__ void venue_sums_runs(const VenueItem& W, int j, fx_t* sums, uint32_t* vflags) {
+  const TSetB& T = W.T;
+  const int r0 = T.blk_r0[j], r1 = T.blk_r0[j + 1];
+  const uint4* pv8 = reinterpret_cast<const uint4*>(T.pv_blk);
+  const float4* x4 = reinterpret_cast<const float4*>(T.x);
+  const int ga = r0 >> 3, gb = (r1 + 7) >> 3;
+  const int g_in = (int)(T.n_x >> 3);            // groups wholly inside x
+  for (int g = ga + W.tid; g < gb; g += kVenueUnroll * kTileThreads) {
+    uint4 raw[kVenueUnroll];
+    float4 xa[kVenueUnroll], xb[kVenueUnroll];
+#pragma unroll
+    for (int u = 0; u < kVenueUnroll; ++u) {
+      const int gu = min(g + u * kTileThreads, gb - 1);
+      raw[u] = pv8[gu];
+      if (gu < g_in) {
+        xa[u] = x4[2 * gu];
+        xb[u] = x4[2 * gu + 1];
+      } else {
+        float t[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) t[q] = ((int64_t)gu * 8 + q < T.n_x) ? T.x[(int64_t)gu * 8 + q] : 0.0f;
+        xa[u] = make_float4(t[0], t[1], t[2], t[3]);
+        xb[u] = make_float4(t[4], t[5], t[6], t[7]);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kVenueUnroll; ++u) {
+      const int gu = g + u * kTileThreads;
+      if (gu >= gb) continue;
+      Group8 G(raw[u], make_uint2(0u, 0u), xa[u], xb[u]);
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const int a = gu * 8 + q;
+        if (!(a >= r0 && a < r1)) G.drop(q);
+      }
+      run_sums(W, G, 0, sums, vflags);
+    }
+  }
+}
+
+// cum = (beta * p_contact) * sum per venue and network, to memory and to `cumf`.  A lane's p_contact loads are issued
+// kCumBatch at a time: one venue per iteration (load, wait, convert, store) made this write-out a chain of
+// nv / 1024 = 16 memory round trips per workgroup - most of what a household item (25 us) spent its time on.
+__device__ __forceinline__ void venue_cum_write(const VenueItem& W, const fx_t* sums, const uint32_t* vflags, float* cumf) {
+  const TSetB& T = W.T;
+  for (int l0 = W.tid; l0 < W.nv; l0 += kCumBatch * kTileThreads) {
+    float pc[kCumBatch];
+#pragma unroll
+    for (int u = 0; u < kCumBatch; ++u) pc[u] = T.v_pc[W.v0 + min(l0 + u * kTileThreads, W.nv - 1)];   // clamped, unconditional
+    for (int k = 0; k < W.nk; ++k) {
+      const float beta = T.beta[k];
+#pragma unroll
+      for (int u = 0; u < kCumBatch; ++u) {
+        const int lv = l0 + u * kTileThreads;
+        if (lv < W.nv) {
+          const float c = (beta * pc[u]) * fx_read<kFxVenue>(sums, vflags, W.vwords, k * W.nv + lv);
+          T.cum[(int64_t)(W.v0 + lv) * T.stride + k] = c;
+          cumf[2 * (k * W.nv + lv)] = c;      // low half of the lane's own 8-byte slot
+        }
+      }
+    }
+  }
+}
+// mode 2 (phase C only): `cumf` from the cum an earlier launch wrote
+__device__ __forceinline__ void venue_cum_read(const VenueItem& W, float* cumf) {
+  const TSetB& T = W.T;
+  for (int k = 0; k < W.nk; ++k) {
+    for (int l0 = W.tid; l0 < W.nv; l0 += kCumBatch * kTileThreads) {
+      float c[kCumBatch];
+#pragma unroll
+      for (int u = 0; u < kCumBatch; ++u)
+        c[u] = T.cum[(int64_t)(W.v0 + min(l0 + u * kTileThreads, W.nv - 1)) * T.stride + k];
+#pragma unroll
+      for (int u = 0; u < kCumBatch; ++u) {
+        const int lv = l0 + u * kTileThreads;
+        if (lv < W.nv) cumf[2 * (k * W.nv + lv)] = c[u];
+      }
+    }
+  }
+}
+
+// Phase C: per slot, the venue's cum (leisure: weighted over the set's networks by the agent's class)
+__device__ __forceinline__ void venue_gather(const VenueItem& W, const float* weights, const float* cumf) {
+  const TSetB& T = W.T;
+  const int nk = W.nk, nv = W.nv;
+  for (int g = W.g0 + W.tid; g < W.g1; g += kVenueUnrollC * kTileThreads) {
+    uint4 raw[kVenueUnrollC];
+    uint2 craw[kVenueUnrollC];
+#pragma unroll
+    for (int u = 0; u < kVenueUnrollC; ++u) {
+      const int gu = min(g + u * kTileThreads, W.g1 - 1);
+      raw[u] = W.lv8()[gu];
+      craw[u] = T.leisure ? W.cls8()[gu] : make_uint2(0u, 0u);
+    }
+#pragma unroll
+    for (int u = 0; u < kVenueUnrollC; ++u) {
+      const int gu = g + u * kTileThreads;
+      if (gu >= W.g1) continue;
+      const Group8 G(raw[u], craw[u]);
+      float r[8];
+      if (!T.leisure) {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {      // straight-line: a pad slot reads venue 0 and keeps 0
+          const int lv = G.lv(q);
+          const float c = cumf[2 * (lv != 0xFFFF ? lv : 0)];
+          r[q] = (lv != 0xFFFF) ? c : 0.0f;
+        }
+      } else {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+          const int lv = G.lv(q);
+          const int c = G.cls(q);
+          const int li = lv != 0xFFFF ? lv : 0;
+          float a = 0.0f;
+          for (int k = 0; k < nk; ++k) a += weights[k * 200 + c] * cumf[2 * (k * nv + li)];
+          r[q] = (lv != 0xFFFF) ? a : 0.0f;
+        }
+      }
+      store_nt(W.val4() + 2 * gu, make_float4(r[0], r[1], r[2], r[3]));      // whole lines, read once by phase D
+      store_nt(W.val4() + 2 * gu + 1, make_float4(r[4], r[5], r[6], r[7]));
+    }
+  }
+}
 
 // One workgroup per (set, venue block) work item, heaviest first.  (Measured with per-workgroup timestamps,
 // tools/venue_timeline.py: 1 899 workgroups of 10-80 us on 512 slots, ~80 % of the slot-time used - a finished
@@ -665,298 +909,33 @@ struct VenueStamp {
 // several items each closed those gaps and took as long: with every slot busy the items stretch, the launch is bound
 // by the memory system at ~4.8 TB/s of measured traffic, not by the slots.)
 #ifndef GJ_VENUE_WAVES_PER_SIMD
-#define GJ_VENUE_WAVES_PER_SIMD 4      // 72 VGPRs, no scratch.  (8 = two workgroups per CU needs <= 64 VGPRs and spills 12 dwords
+#define GJ_VENUE_WAVES_PER_SIMD 4      // no scratch.  (8 = two workgroups per CU needs <= 64 VGPRs and spills 12 dwords
                                        // with the exact run merging: measured 207 vs 204 us - the second workgroup, worth 25 % in
                                        // round 1, no longer pays now that the direct form took half of phase C away)
 #endif
 __global__ __launch_bounds__(kTileThreads, GJ_VENUE_WAVES_PER_SIMD) void k_tile_venues(const TileBArgs B) {
   extern __shared__ __align__(16) float lds_s[];
-#ifdef GJ_DIAG_STAMPS
-  VenueStamp gj_stamp;
-#endif
-  const int tid = threadIdx.x;
+  [[maybe_unused]] const VenueStamp gj_stamp;
   const int set = B.work[2 * blockIdx.x], j = B.work[2 * blockIdx.x + 1];
   const TSetB& T = B.sets[set];
-  const int nk = T.nk;
-  if (nk == 0) return;
-  const int v0 = T.blk_v0[j], nv = T.blk_v0[j + 1] - v0;
-  const int g0 = T.blk_e0[j] >> 3, g1 = T.blk_e0[j + 1] >> 3;   // groups of 8 slots
-  fx_t* sums = reinterpret_cast<fx_t*>(lds_s);                    // [nk][nv] fixed-point sums (phase B)
-  float* cumf = lds_s;                                            // cum of (k, lv) at float index 2*(k*nv+lv) (phase C)
-  float* tabs = lds_s + 2 * ((size_t)nk * nv + 64);  // (64 scratch sums, one per lane of a wave, follow the sums)
-                                                     // [nk][200] pass-1 tables, then [nk][200] pass-2 weights
-  uint32_t* vflags = reinterpret_cast<uint32_t*>(tabs + (T.leisure ? 2 * nk * 200 : 0));   // two bits per sum (fx_flag)
-  const int vwords = (nk * nv + 64 + 31) / 32;
-  if (T.leisure) {
-    for (int i = tid; i < nk * 200; i += kTileThreads) {
-      const int k = i / 200, c = i % 200;
-      const float l = B.tables[(int64_t)T.table[k] * GJ_TABLE_SIZE + B.day_type * 200 + c];
-      const float lw = T.age75[k] ? l * (((c % 100) > 75) ? 1.0f : 0.0f) : l;
-      tabs[i] = B.transpose ? lw : l;                 // weights of the transmitting side (pass 1)
-      tabs[nk * 200 + i] = B.transpose ? l : lw;      // weights of the receiving side (pass 2)
-    }
-  }
-  const uint4* lv8 = reinterpret_cast<const uint4*>(T.e_lv);
-  const uint2* cls8 = reinterpret_cast<const uint2*>(T.e_cls);
-  float4* val4 = reinterpret_cast<float4*>(T.val);
+  if (T.nk == 0) return;
+  const VenueItem W(T, j, lds_s, threadIdx.x);
+  // table set-up: pass-1 weights, then pass-2 weights (read behind the barriers below)
+  if (T.leisure) fill_class_weights<true, true>(W.tabs, W.tabs + W.nk * 200, T, B.tables, B.day_type, B.transpose, W.tid);
   if (B.mode != 2) {
-    for (int i = tid; i < nk * nv + 64; i += kTileThreads) sums[i] = 0;
-    for (int i = tid; i < 2 * vwords; i += kTileThreads) vflags[i] = 0u;
-    __syncthreads();
-    // B: each lane takes 8 consecutive slots (48 bytes), merges runs of one venue in registers and adds
-    // each run to the block's LDS sums; kVenueUnroll such groups are loaded before the first is used
-    // Straight-line: a run of one venue is summed left to right in a register and added where the run ends; every
-    // slot position issues an add, the ones that are not the end of a run (or are padding) add 0 to a scratch slot of
-    // the lane's own.  (Branches per slot made this launch issue three times the instructions: it is bound by
-    // instruction issue, SQ_ACTIVE_INST_ANY x waves per SIMD ~ 0.8.)
-    const int dummy = nk * nv + (tid & 63);
-    // Every slot's value goes to fixed point FIRST and a run of one venue is merged as integers: exact, so a venue's sum
-    // does not depend on where the block boundaries and the padding put its runs relative to the 8-slot groups - the
-    // tile geometry (eb_target, sv_max, slices) cannot change a single bit of `cum`.  (Round 2 merged the runs in fp32
-    // and converted the run totals; the launch is bound by the memory system, the extra integer adds are free.)
-#if defined(GJ_DIAG_FLOAT_RUNS)      // round 2's form, kept for A/B timing only (tools/ab.py): runs merged in fp32
-    auto run_sums = [&](const int (&lv)[8], const float (&x)[8], int base_k) {
-      float s8 = x[0];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const bool last = (q == 7) || (lv[q + (q < 7)] != lv[q]);
-        const bool take = last && lv[q] != 0xFFFF;
-        fx_add<kFxVenue>(sums, vflags, vwords, take ? base_k + lv[q] : dummy, take ? s8 : 0.0f);
-        if (q < 7) s8 = last ? x[q + 1] : s8 + x[q + 1];
-      }
-    };
-#elif defined(GJ_DIAG_SLOT_ADDS)     // A/B: no run merging at all - every slot adds its own value to its venue
-    auto run_sums = [&](const int (&lv)[8], const float (&x)[8], int base_k) {
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const bool valid = lv[q] != 0xFFFF;
-        const bool ok = fabsf(x[q]) <= fx_max<kFxVenue>();
-        atomicAdd(&sums[valid ? base_k + lv[q] : dummy], to_fx<kFxVenue>((ok && valid) ? x[q] : 0.0f));
-        if (__builtin_expect(!ok && valid, 0)) fx_flag(vflags, vwords, base_k + lv[q], x[q]);
-      }
-    };
-#else
-    // Every slot's value goes to fixed point FIRST and a run of one venue is merged as integers: exact, so a venue's sum
-    // does not depend on where the block boundaries and the padding put its runs relative to the 8-slot groups - the
-    // tile geometry (eb_target, sv_max, slices) and the partition cannot change a single bit of `cum`.  (Round 2 merged
-    // the runs in fp32 and converted the run totals: GJ_DIAG_FLOAT_RUNS, 8-18 us faster on C3 from box to box and not
-    // exact.  Measured and ruled out as the cause of that gap, tools/ab.py: instruction count - this form has 12 per slot
-    // against 19 -, zero / non-zero scratch adds, LDS operations in flight, registers reused behind an LDS operation.)
-    // The range check is made ONCE per group on the bit patterns - as unsigned integers |x| <= 16384, NaN and the
-    // infinities order like their patterns - and a slot that is not the end of a run adds whatever the running sum is
-    // to the lane's scratch sum instead of selecting a zero.
-    auto run_sums = [&](const int (&lv)[8], const float (&x)[8], int base_k) {
-      // (wave-uniform, at most the pattern of fx_max<kFxVenue>() = 16384.0f; smaller for a set with venues of more than
-      // 4 096 attendees, so that attendees x window stays inside the 64-bit sum: no sum can wrap)
-      const uint32_t kLimit = T.term_limit;
-      static_assert(kFxVenue == 36, "term_limit is derived from 2^(50 - kFxVenue) (fill_set_b)");
-      uint32_t m = 0u;
-#pragma unroll
-      for (int q = 0; q < 8; ++q) m = max(m, __float_as_uint(x[q]) & 0x7FFFFFFFu);
-      if (__builtin_expect(m > kLimit, 0)) {            // a NaN / infinity / out-of-window term: saturates or poisons its venue
-        venue_group_slow(sums, vflags, vwords, kLimit, base_k, lv[0], lv[1], lv[2], lv[3], lv[4], lv[5], lv[6], lv[7], x[0],
-                         x[1], x[2], x[3], x[4], x[5], x[6], x[7]);
-        return;
-      }
-      fx_t s8 = 0;
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const fx_t f = to_fx<kFxVenue>(x[q]);
-        const bool first = (q == 0) || (lv[q] != lv[q - (q > 0)]);
-        s8 = first ? f : s8 + f;
-        const bool last = (q == 7) || (lv[q + (q < 7)] != lv[q]);
-        const bool take = last && lv[q] != 0xFFFF;
-        atomicAdd(&sums[take ? base_k + lv[q] : dummy], s8);
-      }
-    };
-#endif
-#ifndef GJ_WAVE_RUNS
-#define GJ_WAVE_RUNS 1
-#endif
-    // 512 consecutive slots of ONE venue (a wave's 64 groups): the slots' fixed-point terms are added up per lane, then
-    // across the wave (integer adds: the same sum, bit for bit), and ONE lane adds the total - instead of 512 LDS
-    // atomics per network of which 448 go to scratch sums and 64 to one address.  What makes the case common: venues far
-    // larger than a tile's width - the leisure venues of a JUNE world (every resident of the k nearest super areas:
-    // 15 000 attendees, six networks per slot), the giant venues of BASELINE config 5, schools on a world with a geography.
-    auto wave_sum = [&](const float (&xl)[8], int target) -> bool {      // false: a term outside the window - generic path
-      uint32_t m = 0u;
-#pragma unroll
-      for (int q = 0; q < 8; ++q) m = max(m, __float_as_uint(xl[q]) & 0x7FFFFFFFu);
-      if (__builtin_amdgcn_ballot_w64(m > T.term_limit) != 0ull) return false;
-      fx_t s = 0;
-#pragma unroll
-      for (int q = 0; q < 8; ++q) s += to_fx<kFxVenue>(xl[q]);
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, kWave);
-      if ((tid & (kWave - 1)) == 0) atomicAdd(&sums[target], s);
-      return true;
-    };
-    auto add_group = [&](const uint4 raw, const float4 xa, const float4 xb, const uint2 craw) {
-      const Slots8 L{{raw.x, raw.y, raw.z, raw.w}};
-      const float x[8] = {xa.x, xa.y, xa.z, xa.w, xb.x, xb.y, xb.z, xb.w};
-      int lv[8];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) lv[q] = L.lv(q);
-      bool one_venue = false;
-#if GJ_WAVE_RUNS
-      {
-        // (raw.x == raw.y == raw.z == raw.w and both halves of a word equal: all eight local venues are the same)
-        const bool mine = (raw.x == raw.y) && (raw.y == raw.z) && (raw.z == raw.w) && ((raw.x >> 16) == (raw.x & 0xFFFFu)) &&
-                          (lv[0] != 0xFFFF) && (lv[0] == __builtin_amdgcn_readfirstlane(lv[0]));
-        one_venue = __builtin_amdgcn_ballot_w64(mine) == ~0ull;         // every lane of the wave, all of them active
-      }
-#endif
-      if (!T.leisure) {
-        if (!(one_venue && wave_sum(x, lv[0]))) run_sums(lv, x, 0);
-      } else {
-        const uint32_t cw[2] = {craw.x, craw.y};
-        for (int k = 0; k < nk; ++k) {
-          const float* tk = tabs + k * 200;
-          float xl[8];
-#pragma unroll
-          for (int q = 0; q < 8; ++q) xl[q] = tk[(cw[q >> 2] >> ((q & 3) * 8)) & 0xFF] * x[q];
-          if (!(one_venue && wave_sum(xl, k * nv + lv[0]))) run_sums(lv, xl, k * nv);
-        }
-      }
-    };
-    for (int g = g0 + tid; g < g1; g += kVenueUnroll * kTileThreads) {
-      uint4 raw[kVenueUnroll];
-      float4 xa[kVenueUnroll], xb[kVenueUnroll];
-      uint2 craw[kVenueUnroll];
-#pragma unroll
-      for (int u = 0; u < kVenueUnroll; ++u) {     // clamped, unconditional: all loads in flight together
-        const int gu = min(g + u * kTileThreads, g1 - 1);
-        raw[u] = lv8[gu];
-        xa[u] = load_nt(val4 + 2 * gu);           // read once, written by phase A: non-temporal
-        xb[u] = load_nt(val4 + 2 * gu + 1);
-        craw[u] = T.leisure ? cls8[gu] : make_uint2(0u, 0u);
-      }
-#pragma unroll
-      for (int u = 0; u < kVenueUnroll; ++u)
-        if (g + u * kTileThreads < g1) add_group(raw[u], xa[u], xb[u], craw[u]);
-    }
-    if (T.pv_blk) {
-      // Run form: the agents [r0, r1) have their primary venue in this block; agent a is a slot with value x[a] and
-      // local venue pv_blk[a] - the same straight-line groups of 8 as above, read from the per-agent arrays themselves
-      // (consecutive agents of one venue are a run).  Agents of the neighbouring blocks in the first / last group are
-      // masked; the last group of the world may reach past x.
-      const int r0 = T.blk_r0[j], r1 = T.blk_r0[j + 1];
-      const uint4* pv8 = reinterpret_cast<const uint4*>(T.pv_blk);
-      const float4* x4 = reinterpret_cast<const float4*>(T.x);
-      const int ga = r0 >> 3, gb = (r1 + 7) >> 3;
-      const int g_in = (int)(T.n_x >> 3);            // groups wholly inside x
-      for (int g = ga + tid; g < gb; g += kVenueUnroll * kTileThreads) {
-        uint4 raw[kVenueUnroll];
-        float4 xa[kVenueUnroll], xb[kVenueUnroll];
-#pragma unroll
-        for (int u = 0; u < kVenueUnroll; ++u) {
-          const int gu = min(g + u * kTileThreads, gb - 1);
-          raw[u] = pv8[gu];
-          if (gu < g_in) {
-            xa[u] = x4[2 * gu];
-            xb[u] = x4[2 * gu + 1];
-          } else {
-            float t[8];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) t[q] = ((int64_t)gu * 8 + q < T.n_x) ? T.x[(int64_t)gu * 8 + q] : 0.0f;
-            xa[u] = make_float4(t[0], t[1], t[2], t[3]);
-            xb[u] = make_float4(t[4], t[5], t[6], t[7]);
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < kVenueUnroll; ++u) {
-          const int gu = g + u * kTileThreads;
-          if (gu >= gb) continue;
-          const Slots8 L{{raw[u].x, raw[u].y, raw[u].z, raw[u].w}};
-          const float x[8] = {xa[u].x, xa[u].y, xa[u].z, xa[u].w, xb[u].x, xb[u].y, xb[u].z, xb[u].w};
-          int lv[8];
-#pragma unroll
-          for (int q = 0; q < 8; ++q) {
-            const int a = gu * 8 + q;
-            lv[q] = (a >= r0 && a < r1) ? L.lv(q) : 0xFFFF;
-          }
-          run_sums(lv, x, 0);
-        }
-      }
-    }
-    __syncthreads();
-    // cum = (beta * p_contact) * sum per venue and network.  A lane's p_contact loads are issued kCumBatch at a time:
-    // one venue per iteration (load, wait, convert, store) made this write-out a chain of nv / 1024 = 16 memory round
-    // trips per workgroup - most of what a household item (25 us) spent its time on.
-    for (int l0 = tid; l0 < nv; l0 += kCumBatch * kTileThreads) {
-      float pc[kCumBatch];
-#pragma unroll
-      for (int u = 0; u < kCumBatch; ++u) pc[u] = T.v_pc[v0 + min(l0 + u * kTileThreads, nv - 1)];   // clamped, unconditional
-      for (int k = 0; k < nk; ++k) {
-        const float beta = T.beta[k];
-#pragma unroll
-        for (int u = 0; u < kCumBatch; ++u) {
-          const int lv = l0 + u * kTileThreads;
-          if (lv < nv) {
-            const float c = (beta * pc[u]) * fx_read<kFxVenue>(sums, vflags, vwords, k * nv + lv);
-            T.cum[(int64_t)(v0 + lv) * T.stride + k] = c;
-            cumf[2 * (k * nv + lv)] = c;      // low half of the lane's own 8-byte slot
-          }
-        }
-      }
-    }
+    venue_zero(W, W.sums, W.vflags);
+    __syncthreads();                            // the sums are zero and the tables written before the first add
+    venue_sums_tiled(W, W.tabs, W.sums, W.vflags);
+    if (T.pv_blk) venue_sums_runs(W, j, W.sums, W.vflags);
+    __syncthreads();                            // every wave's adds have landed
+    venue_cum_write(W, W.sums, W.vflags, W.cumf);
     if (B.mode == 1 || T.direct) return;
   } else {
     if (T.direct) return;
-    for (int k = 0; k < nk; ++k) {
-      for (int l0 = tid; l0 < nv; l0 += kCumBatch * kTileThreads) {
-        float c[kCumBatch];
-#pragma unroll
-        for (int u = 0; u < kCumBatch; ++u)
-          c[u] = T.cum[(int64_t)(v0 + min(l0 + u * kTileThreads, nv - 1)) * T.stride + k];
-#pragma unroll
-        for (int u = 0; u < kCumBatch; ++u) {
-          const int lv = l0 + u * kTileThreads;
-          if (lv < nv) cumf[2 * (k * nv + lv)] = c[u];
-        }
-      }
-    }
+    venue_cum_read(W, W.cumf);
   }
-  __syncthreads();
-  // C: per slot, the venue's cum (leisure: weighted over the set's networks by the agent's class)
-  for (int g = g0 + tid; g < g1; g += kVenueUnrollC * kTileThreads) {
-    uint4 raw[kVenueUnrollC];
-    uint2 craw[kVenueUnrollC];
-#pragma unroll
-    for (int u = 0; u < kVenueUnrollC; ++u) {
-      const int gu = min(g + u * kTileThreads, g1 - 1);
-      raw[u] = lv8[gu];
-      craw[u] = T.leisure ? cls8[gu] : make_uint2(0u, 0u);
-    }
-#pragma unroll
-    for (int u = 0; u < kVenueUnrollC; ++u) {
-      const int gu = g + u * kTileThreads;
-      if (gu >= g1) continue;
-      const Slots8 L{{raw[u].x, raw[u].y, raw[u].z, raw[u].w}};
-      float r[8];
-      if (!T.leisure) {
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {      // straight-line: a pad slot reads venue 0 and keeps 0
-          const int lv = L.lv(q);
-          const float c = cumf[2 * (lv != 0xFFFF ? lv : 0)];
-          r[q] = (lv != 0xFFFF) ? c : 0.0f;
-        }
-      } else {
-        const uint32_t cw[2] = {craw[u].x, craw[u].y};
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          const int lv = L.lv(q);
-          const int c = (cw[q >> 2] >> ((q & 3) * 8)) & 0xFF;
-          const int li = lv != 0xFFFF ? lv : 0;
-          float a = 0.0f;
-          for (int k = 0; k < nk; ++k) a += tabs[nk * 200 + k * 200 + c] * cumf[2 * (k * nv + li)];
-          r[q] = (lv != 0xFFFF) ? a : 0.0f;
-        }
-      }
-      store_nt(val4 + 2 * gu, make_float4(r[0], r[1], r[2], r[3]));      // whole lines, read once by phase D
-      store_nt(val4 + 2 * gu + 1, make_float4(r[4], r[5], r[6], r[7]));
-    }
-  }
+  __syncthreads();                              // cumf is complete
+  venue_gather(W, W.tabs + W.nk * 200, W.cumf);
 }
 
 // ---- pass 1 in the "direct" form (sets with few venues whose edges all belong to owned agents) ----------------------
@@ -1017,14 +996,7 @@ __global__ __launch_bounds__(kTileThreads) void k_tile_presum(const TilePArgs P)
       __syncthreads();                                   // the previous table has been written out
       for (int i = tid; i < n_sums + 64; i += kTileThreads) lds_p[i] = 0;
       for (int i = tid; i < (n_sums + 64 + 31) / 32; i += kTileThreads) flags[i] = 0u;
-      if (T.leisure) {
-        for (int i = tid; i < nk * 200; i += kTileThreads) {
-          const int k = i / 200, c = i % 200;
-          const float l = P.tables[(int64_t)T.table[k] * GJ_TABLE_SIZE + P.day_type * 200 + c];
-          const float lw = T.age75[k] ? l * (((c % 100) > 75) ? 1.0f : 0.0f) : l;
-          wtab[i] = P.transpose ? lw : l;
-        }
-      }
+      if (T.leisure) fill_class_weights<true, false>(wtab, nullptr, T, P.tables, P.day_type, P.transpose, tid);
       __syncthreads();
       for (int plane = 0; plane < T.planes; ++plane) {
         const uint16_t* ell = T.ell + plane * T.plane_stride + a_begin * 2;
@@ -1069,7 +1041,7 @@ __global__ __launch_bounds__(kTileThreads) void k_tile_presum(const TilePArgs P)
                 if (!T.leisure) {
                   fx_add_or_poison(lds_p, flags, in ? lv : dummy, in ? xv[j] : 0.0f);
                 } else {
-                  const int cj = (B.cl[u] >> (8 * j)) & 0xFF;
+                  const int cj = class_byte(B.cl[u], j);
                   for (int k = 0; k < nk; ++k)
                     fx_add_or_poison(lds_p, flags, in ? lv * nk + k : dummy, in ? wtab[k * 200 + cj] * xv[j] : 0.0f);
                 }
@@ -1170,14 +1142,13 @@ constexpr int GJ_MAX_DIRECT = GJ_MAX_SETS;      // every set may be in the direc
                                                 // up to 12 sets; 6 until round 3)
 constexpr int kClassWeightFloats = GJ_MAX_NETS_PER_SET * 200;
 struct TDirect {          // a set whose pass 2 is taken straight from the venues' cum
-  const uint16_t* ell;    // [planes][owned agents, padded to slices][K] venue ids, 0xFFFF = none
+  const uint16_t* ell;    // [planes][owned agents, padded to slices][2] venue ids (a pair of columns per plane), 0xFFFF = none
   const float* cum;       // [V * stride]
   int64_t plane_stride;   // elements of one plane
-  int32_t K, planes;      // K entries per agent and plane (1, or 2: a pair of columns per plane)
+  int32_t planes;
   int32_t V, stride, nk;
   int32_t region;         // which of the two LDS table regions its venue values are staged in
   int32_t group_venues;   // venues per staging group (== V unless the table is larger than region 0)
-  int32_t _pad;
   int32_t raw, leisure;
   int32_t table[GJ_MAX_NETS_PER_SET];
   int32_t age75[GJ_MAX_NETS_PER_SET];
@@ -1220,12 +1191,24 @@ struct TileDArgs {
   int32_t io_vec4;        // susceptibility and the optional per-agent outputs are 16-byte aligned
 };
 
+// `now` and `step` of the launch: from device memory when a captured step is replayed, else from the arguments
+struct StepClock {
+  float now;
+  uint64_t step;
+};
+__device__ __forceinline__ StepClock step_clock(const TileDArgs& D) {
+  return {D.clock ? D.clock->now : D.now, D.clock ? D.clock->step : D.step};
+}
+// a8 for one agent: the reference's sampler on injected draws (e0, e1), else the library's own noise (theta)
+__device__ __forceinline__ float new_infected_of(bool injected, float p, float e0, float e1, float theta) {
+  return injected ? gumbel_new_infected(p, e0, e1) : own_new_infected(p, theta);
+}
+
 // a7-a9 for one agent per lane, from the per-agent sums of phase D (split form)
 __global__ __launch_bounds__(256) void k_tile_epilogue(const TileDArgs D) {
   const int64_t a = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (a >= D.n_agents) return;
-  const float now = D.clock ? D.clock->now : D.now;
-  const uint64_t step = D.clock ? D.clock->step : D.step;
+  const StepClock clock = step_clock(D);
   float susc = D.susceptibility[a];
   float ts = susc * D.acc_scratch[a];
   if (D.trans_susc) D.trans_susc[a] = ts;
@@ -1239,12 +1222,12 @@ __global__ __launch_bounds__(256) void k_tile_epilogue(const TileDArgs D) {
   } else {
     e0 = e1 = 1.0f;
   }
-  const float nw = D.exp_noise ? gumbel_new_infected(p, e0, e1)
-                               : own_new_infected(p, infection_uniform(D.seed, step, D.agent_offset + a));
+  const float theta = D.exp_noise ? 0.0f : infection_uniform(D.seed, clock.step, D.agent_offset + a);
+  const float nw = new_infected_of(D.exp_noise != nullptr, p, e0, e1, theta);
   if (D.new_infected) D.new_infected[a] = nw;
   if (nw != 0.0f) {
     float inf = D.is_infected[a], t_inf = D.infection_time[a];
-    infect(nw, now, susc, inf, t_inf);
+    infect(nw, clock.now, susc, inf, t_inf);
     D.susceptibility[a] = susc;
     D.is_infected[a] = inf;
     D.infection_time[a] = t_inf;
@@ -1254,8 +1237,8 @@ __global__ __launch_bounds__(256) void k_tile_epilogue(const TileDArgs D) {
 // ---- phase D, direct form (sets with few venues; tiling.py build_ell) --------------------------------------------
 // acc32[i] += sum over agent i's ELL entries of the venue's cum (leisure sets: weighted over the set's networks by the
 // agent's class).  The venues' values pass through LDS in groups of table_floats / nk venues.  No atomics: a lane owns
-// QUADS of consecutive agents, 4 * (tid + m * 1024) + 0..3, so one quad's rows are a single 8K-byte load, its classes
-// one dword and its sums one 16-byte LDS access.  A lane's quads are loaded in batches that fit its registers (K <= 2:
+// QUADS of consecutive agents, 4 * (tid + m * 1024) + 0..3, so one quad's rows are a single 16-byte load, its classes
+// one dword and its sums one 16-byte LDS access.  A lane's quads are loaded in batches that fit its registers (two columns per plane:
 // all of the slice's at once, BEFORE the table is staged, so that the two latencies overlap and a set with several
 // venue groups reads its rows once).
 constexpr int kQuadsPerLane = (kMaxSliceAgents + 4 * kTileThreads - 1) / (4 * kTileThreads);   // 5
@@ -1340,7 +1323,7 @@ __device__ __forceinline__ void direct_add(const TileDArgs& D, const TDirect& T,
         if (k >= nk) break;
         float w[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) w[j] = wtab[k * 200 + ((b.cls[u] >> (8 * j)) & 0xFF)];
+        for (int j = 0; j < 4; ++j) w[j] = wtab[k * 200 + class_byte(b.cls[u], j)];
 #pragma unroll
         for (int j = 0; j < 4; ++j)
 #pragma unroll
@@ -1363,33 +1346,12 @@ __device__ __forceinline__ void direct_add(const TileDArgs& D, const TDirect& T,
 // of a leisure set the receiving side's class weights are computed into that set's weight buffer.
 __device__ __forceinline__ void direct_stage(const TileDArgs& D, const TDirect& T, float* wtab, float* tab, int v0,
                                              int nv, int tid) {
-  if (T.leisure && v0 == 0) {
-    for (int i = tid; i < T.nk * 200; i += kTileThreads) {
-      const int k = i / 200, c = i % 200;
-      const float l = D.tables[(int64_t)T.table[k] * GJ_TABLE_SIZE + D.day_type * 200 + c];
-      const float lw = T.age75[k] ? l * (((c % 100) > 75) ? 1.0f : 0.0f) : l;
-      wtab[i] = D.transpose ? l : lw;       // weights of the receiving side (pass 2)
-    }
-  }
-#ifndef GJ_DIAG_NO_DIRECT_TABLE
+  if (T.leisure && v0 == 0) fill_class_weights<false, true>(nullptr, wtab, T, D.tables, D.day_type, D.transpose, tid);
   const float* src = T.cum + (int64_t)v0 * T.stride;
   const int n = nv * T.stride;
   const int lane = tid % kWave, wave = __builtin_amdgcn_readfirstlane(tid / kWave);
-#if GJ_DMA_WIDE
-  // gfx950's 16-byte LDS-DMA (global_load_lds_dwordx4): 1 KiB per wave-instruction instead of 256 bytes - a quarter of
-  // the instructions for the whole pieces, the 4-byte form for the remainder (a lane must not read past the table).
-  // Only when both ends are 16-byte aligned (wave-uniform; a run-form window starts at any venue)
-  const bool aligned = ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(tab)) & 15u) == 0;
-  const int n_wide = aligned ? (n / (4 * kWave)) * (4 * kWave) : 0;
-  for (int p = wave; (p + 1) * 4 * kWave <= n_wide; p += kTileWaves)
-    __builtin_amdgcn_global_load_lds(src + p * 4 * kWave + 4 * lane, tab + p * 4 * kWave, 16, 0, 0);
-  for (int p = wave; n_wide + p * kWave < n; p += kTileWaves)
-    __builtin_amdgcn_global_load_lds(src + min(n_wide + p * kWave + lane, n - 1), tab + n_wide + p * kWave, 4, 0, 0);
-#else
   for (int p = wave; p * kWave < n; p += kTileWaves)
     __builtin_amdgcn_global_load_lds(src + min(p * kWave + lane, n - 1), tab + p * kWave, 4, 0, 0);
-#endif
-#endif
 }
 
 // All direct sets of the slice.  Work items are (set, venue group, plane) in order.  While item i is summed, the rows
@@ -1420,9 +1382,29 @@ __device__ __forceinline__ bool direct_next(const TileDArgs& D, int& t, int& v0,
   return t < D.n_direct;
 }
 
+// timing diagnostics (a -DGJ_DIAG_STAMPS build; tools/ab.py, tools/rank_share.py): lane 0 of every workgroup of
+// k_tile_agents writes the cycles since its start at marked points into trans_susc[slice base + k] (the epilogue then
+// leaves trans_susc alone).  GJ_STAMP(k) needs `D` and the workgroup's `gj_stamp` in scope.
+#ifdef GJ_DIAG_STAMPS
+constexpr bool kAgentStamps = true;
+struct AgentStamp {
+  uint64_t t0;
+  __device__ AgentStamp() : t0(__builtin_amdgcn_s_memtime()) {}
+};
+#define GJ_STAMP(k)                                                                                                \
+  do {                                                                                                             \
+    if (threadIdx.x == 0 && D.trans_susc)                                                                           \
+      D.trans_susc[(int64_t)blockIdx.x * D.slice_agents + (k)] = (float)(__builtin_amdgcn_s_memtime() - gj_stamp.t0); \
+  } while (0)
+#else
+constexpr bool kAgentStamps = false;
+struct AgentStamp {};
+#define GJ_STAMP(k) do { } while (0)
+#endif
+
 __device__ __forceinline__ void direct_sets(const TileDArgs& D, float (&acc)[kQuadsPerLane][4], uint32_t qmask,
                                             float* lds, int64_t base, int n_local, int tid, DirectBatch& cur,
-                                            uint64_t diag_t0 = 0) {
+                                            const AgentStamp& gj_stamp) {
   auto wtab_of = [&](int t) { return lds + (t & 1) * kClassWeightFloats; };
   auto tab_of = [&](const TDirect& T) {
     return lds + 2 * kClassWeightFloats + (T.region ? D.table_floats + kWave : 0);
@@ -1439,10 +1421,7 @@ __device__ __forceinline__ void direct_sets(const TileDArgs& D, float (&acc)[kQu
     const TDirect& T = D.direct[t];
     const int nv = group_nv(T, v0);
     if (plane == 0) publish_staged();           // this group's values have landed (vmcnt(0) + barrier) - and its rows
-#ifdef GJ_DIAG_STAMPS
-    if (threadIdx.x == 0 && D.trans_susc && t < 4)
-      D.trans_susc[(int64_t)blockIdx.x * D.slice_agents + 8 + 2 * t] = (float)(__builtin_amdgcn_s_memtime() - diag_t0);
-#endif
+    if (t < 4) GJ_STAMP(8 + 2 * t);
     int tn = t, vn = v0, pn = plane;
     more = direct_next(D, tn, vn, pn);
     const bool new_group = more && pn == 0;
@@ -1452,15 +1431,8 @@ __device__ __forceinline__ void direct_sets(const TileDArgs& D, float (&acc)[kQu
       direct_stage(D, D.direct[tn], wtab_of(tn), tab_of(D.direct[tn]), group_lo(D.direct[tn], vn), group_nv(D.direct[tn], vn), tid);
     DirectBatch nxt;
     if (more) direct_load(D, D.direct[tn], base, n_local, tid, pn, nxt);     // in flight while this item is summed
-#ifndef GJ_DIAG_NO_DIRECT_ADD
     direct_add(D, T, acc, qmask, wtab_of(t), tab_of(T), v0, nv, n_local, tid, cur);
-#else
-    if (cur.w[0][0] == 0x12345678u && cur.cls[0] == 77u) acc[0][0] = 1.0f;     // keep the loads alive
-#endif
-#ifdef GJ_DIAG_STAMPS
-    if (threadIdx.x == 0 && D.trans_susc && t < 4)
-      D.trans_susc[(int64_t)blockIdx.x * D.slice_agents + 9 + 2 * t] = (float)(__builtin_amdgcn_s_memtime() - diag_t0);
-#endif
+    if (t < 4) GJ_STAMP(9 + 2 * t);
     if (new_group && !overlap) {                // same region: only once every wave is done reading this group
       __syncthreads();
       direct_stage(D, D.direct[tn], wtab_of(tn), tab_of(D.direct[tn]), group_lo(D.direct[tn], vn), group_nv(D.direct[tn], vn), tid);
@@ -1503,36 +1475,44 @@ __device__ __forceinline__ void store_quad(float* p, int64_t a0, int n_ok, bool 
   }
 }
 
-// GJ_DIAG_STAMPS (timing diagnostics, tools/ab.py): lane 0 of every workgroup writes the cycles since its start at
-// marked points into trans_susc[slice base + k] (the epilogue then leaves trans_susc alone)
-#ifdef GJ_DIAG_STAMPS
-#define GJ_STAMP(k)                                                                                         \
-  do {                                                                                                      \
-    if (threadIdx.x == 0 && D.trans_susc)                                                                    \
-      D.trans_susc[(int64_t)blockIdx.x * D.slice_agents + (k)] = (float)(__builtin_amdgcn_s_memtime() - gj_t0); \
-  } while (0)
-#else
-#define GJ_STAMP(k) do { } while (0)
-#endif
-
-__global__ __launch_bounds__(kTileThreads) void k_tile_agents(const TileDArgs D) {
-  extern __shared__ __align__(16) fx_t lds_acc[];
-#ifdef GJ_DIAG_STAMPS
-  const uint64_t gj_t0 = __builtin_amdgcn_s_memtime();
-#endif
-  const int tid = threadIdx.x;
-  const int wave = __builtin_amdgcn_readfirstlane(tid / kWave), lane = tid % kWave;
-  const int s = blockIdx.x;
-  const int64_t base = (int64_t)s * D.slice_agents;
-  const int n_local = (int)min((int64_t)D.slice_agents, D.n_agents - base);
-  uint32_t* lds_flags = reinterpret_cast<uint32_t*>(lds_acc + D.slice_agents);   // two bits per agent (fx_flag): POS words, NEG words
-  const int fwords = D.slice_agents / 32;
+// ---- the phases of k_tile_agents, in order.  What they hand on: the slice's fixed-point sums and flags in LDS
+// (zero -> gather -> registers), then a lane's sums `acc` in registers (-> direct sets -> outputs / epilogue), ts in
+// LDS (agents_ts_to_lds -> agents_epilogue) and the lane's `infected` bits (-> agents_tail).
+__device__ __forceinline__ void agents_zero(fx_t* lds_acc, uint32_t* lds_flags, int fwords, int n_local, int tid) {
   for (int i = tid; i < n_local; i += kTileThreads) lds_acc[i] = 0;
   for (int i = tid; i < 2 * fwords; i += kTileThreads) lds_flags[i] = 0u;
-  DirectBatch first;                       // rows of the first direct item: their round trip hides behind the tiled sets
-  if (D.n_direct > 0) direct_load(D, D.direct[0], base, n_local, tid, 0, first);
-  __syncthreads();
-  // ts = susc * (q * sum over masked sets + sum over raw sets): masked sets first, scale by q, raw sets last
+}
+
+// the quarantined agents' sums over the masked sets become 0
+__device__ __forceinline__ void agents_quarantine(const TileDArgs& D, fx_t* lds_acc, uint32_t* lds_flags, int fwords,
+                                                  int64_t base, int n_local, int tid) {
+  // (a lane's stage loads are issued ten at a time: one per iteration made this a chain of 20 memory round trips)
+  constexpr int kStageBatch = 10;
+  for (int i0 = tid; i0 < n_local; i0 += kStageBatch * kTileThreads) {
+    float stg[kStageBatch];
+#pragma unroll
+    for (int u = 0; u < kStageBatch; ++u) stg[u] = D.stage[base + min(i0 + u * kTileThreads, n_local - 1)];
+#pragma unroll
+    for (int u = 0; u < kStageBatch; ++u) {
+      const int i = i0 + u * kTileThreads;
+      if (i < n_local && !(stg[u] < D.q_thr)) {
+        lds_acc[i] = 0;
+        // a sum that merely saturated is finite in the reference: its quarantine factor of 0 makes it 0 (NaN stays NaN)
+        const uint32_t bit = 1u << (i & 31);
+        const bool pos = lds_flags[i >> 5] & bit, neg = lds_flags[fwords + (i >> 5)] & bit;
+        if (pos != neg) {
+          atomicAnd(&lds_flags[i >> 5], ~bit);
+          atomicAnd(&lds_flags[fwords + (i >> 5)], ~bit);
+        }
+      }
+    }
+  }
+}
+
+// ts = susc * (q * sum over masked sets + sum over raw sets): masked sets first, scale by q, raw sets last
+__device__ __forceinline__ void agents_gather(const TileDArgs& D, fx_t* lds_acc, uint32_t* lds_flags, int fwords, int s,
+                                              int64_t base, int n_local, int tid) {
+  const int wave = __builtin_amdgcn_readfirstlane(tid / kWave), lane = tid % kWave;
   for (int pass = 0; pass < 2; ++pass) {
     for (int t = 0; t < D.n_sets; ++t) {
       const TSetA& T = D.sets[t];
@@ -1545,43 +1525,24 @@ __global__ __launch_bounds__(kTileThreads) void k_tile_agents(const TileDArgs D)
         gather_set<false>(T, lds_acc, lds_flags, fwords, s, wave, lane);
       }
     }
-    __syncthreads();
+    __syncthreads();                            // the pass's adds have landed
     if (pass == 0 && D.has_q) {
-      // (a lane's stage loads are issued ten at a time: one per iteration made this a chain of 20 memory round trips)
-      constexpr int kStageBatch = 10;
-      for (int i0 = tid; i0 < n_local; i0 += kStageBatch * kTileThreads) {
-        float stg[kStageBatch];
-#pragma unroll
-        for (int u = 0; u < kStageBatch; ++u) stg[u] = D.stage[base + min(i0 + u * kTileThreads, n_local - 1)];
-#pragma unroll
-        for (int u = 0; u < kStageBatch; ++u) {
-          const int i = i0 + u * kTileThreads;
-          if (i < n_local && !(stg[u] < D.q_thr)) {
-            lds_acc[i] = 0;
-            // a sum that merely saturated is finite in the reference: its quarantine factor of 0 makes it 0 (NaN stays NaN)
-            const uint32_t bit = 1u << (i & 31);
-            const bool pos = lds_flags[i >> 5] & bit, neg = lds_flags[fwords + (i >> 5)] & bit;
-            if (pos != neg) {
-              atomicAnd(&lds_flags[i >> 5], ~bit);
-              atomicAnd(&lds_flags[fwords + (i >> 5)], ~bit);
-            }
-          }
-        }
-      }
-      __syncthreads();
+      agents_quarantine(D, lds_acc, lds_flags, fwords, base, n_local, tid);
+      __syncthreads();                          // ... and the zeros, before the raw sets add
     }
   }
-  GJ_STAMP(1);
-  // ---- per-agent tail.  Each lane owns QUADS of consecutive agents, 4 * (tid + m * 1024) + 0..3 (m < 5): their sums
-  // leave LDS for registers, so that the whole LDS is free for the direct sets' venue tables, and the epilogue moves
-  // 16 bytes per lane and array.
-  constexpr int kQ = kQuadsPerLane;
-  float acc[kQ][4];
+}
+
+// Each lane owns QUADS of consecutive agents, 4 * (tid + m * 1024) + 0..3 (m < 5): their sums leave LDS for registers,
+// so that the whole LDS is free for the direct sets' venue tables, and the epilogue moves 16 bytes per lane and array.
+__device__ __forceinline__ void agents_sums_to_registers(const fx_t* lds_acc, const uint32_t* lds_flags, int fwords,
+                                                         int slice_agents, int n_local, int tid,
+                                                         float (&acc)[kQuadsPerLane][4]) {
 #pragma unroll
-  for (int m = 0; m < kQ; ++m) {
+  for (int m = 0; m < kQuadsPerLane; ++m) {
     const int i0 = 4 * (tid + m * kTileThreads);
     // (the quad's four "not summable" bits sit in one word: i0 is a multiple of 4)
-    const int iq = min(i0, D.slice_agents - 4);           // unconditional, clamped LDS reads (the whole quad is in LDS)
+    const int iq = min(i0, slice_agents - 4);             // unconditional, clamped LDS reads (the whole quad is in LDS)
     const uint32_t pos = (lds_flags[iq >> 5] >> (iq & 31)) & 0xFu, neg = (lds_flags[fwords + (iq >> 5)] >> (iq & 31)) & 0xFu;
     fx_t raw[4];
 #pragma unroll
@@ -1592,77 +1553,82 @@ __global__ __launch_bounds__(kTileThreads) void k_tile_agents(const TileDArgs D)
       acc[m][j] = (i0 < n_local) ? (((pos | neg) >> j) & 1u ? fx_special((pos >> j) & 1u, (neg >> j) & 1u, v) : v) : 0.0f;
     }
   }
-  if (D.n_direct > 0) {
-    uint32_t qmask = 0u;                                  // bit 4m + j: the agent is quarantined
-    if (D.has_q) {
-      float stg[kQ][4];
-#pragma unroll
-      for (int m = 0; m < kQ; ++m) {
-        const int i0 = 4 * (tid + m * kTileThreads);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) stg[m][j] = (i0 + j < n_local) ? D.stage[base + i0 + j] : -INFINITY;
-      }
-#pragma unroll
-      for (int m = 0; m < kQ; ++m)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) qmask |= (stg[m][j] < D.q_thr) ? 0u : (1u << (4 * m + j));
-    }
-    GJ_STAMP(2);
-#ifndef GJ_DIAG_NO_DIRECT_SETS       // timing diagnostics only (tools/ab.py): what the direct sets cost in phase D
-#ifdef GJ_DIAG_STAMPS
-    direct_sets(D, acc, qmask, reinterpret_cast<float*>(lds_acc), base, n_local, tid, first, gj_t0);
-#else
-    direct_sets(D, acc, qmask, reinterpret_cast<float*>(lds_acc), base, n_local, tid, first);
-#endif
-#endif
-    GJ_STAMP(3);
-  }
-  const bool vec = D.io_vec4 != 0;
-  if (D.agent_sums) {    // the forward's sums, kept for a backward pass
+}
+
+// bit 4m + j: agent 4 * (tid + m * 1024) + j is quarantined (takes nothing from the masked direct sets)
+__device__ __forceinline__ uint32_t agents_quarantine_mask(const TileDArgs& D, int64_t base, int n_local, int tid) {
+  constexpr int kQ = kQuadsPerLane;
+  uint32_t qmask = 0u;
+  if (D.has_q) {
+    float stg[kQ][4];
 #pragma unroll
     for (int m = 0; m < kQ; ++m) {
+      const int i0 = 4 * (tid + m * kTileThreads);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) stg[m][j] = (i0 + j < n_local) ? D.stage[base + i0 + j] : -INFINITY;
+    }
+#pragma unroll
+    for (int m = 0; m < kQ; ++m)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) qmask |= (stg[m][j] < D.q_thr) ? 0u : (1u << (4 * m + j));
+  }
+  return qmask;
+}
+
+// The optional outputs that are the sums themselves.  true: the split form - the sums went to acc_scratch and a7-a9
+// are left to k_tile_epilogue.
+__device__ __forceinline__ bool agents_outputs(const TileDArgs& D, const float (&acc)[kQuadsPerLane][4], int64_t base,
+                                               int n_local, int tid, bool vec) {
+  if (D.agent_sums) {    // the forward's sums, kept for a backward pass
+#pragma unroll
+    for (int m = 0; m < kQuadsPerLane; ++m) {
       const int i0 = 4 * (tid + m * kTileThreads);
       if (i0 < n_local) store_quad<true>(D.agent_sums, base + i0, n_local - i0, vec, acc[m]);
     }
   }
-  if (D.acc_scratch) {   // split form: hand the per-agent sums to k_tile_epilogue (runs at full occupancy)
+  if (!D.acc_scratch) return false;
+  // split form: hand the per-agent sums to k_tile_epilogue (runs at full occupancy)
 #pragma unroll
-    for (int m = 0; m < kQ; ++m) {
-      const int i0 = 4 * (tid + m * kTileThreads);
-      if (i0 < n_local) store_quad(D.acc_scratch, base + i0, n_local - i0, vec, acc[m]);
-    }
-    return;
+  for (int m = 0; m < kQuadsPerLane; ++m) {
+    const int i0 = 4 * (tid + m * kTileThreads);
+    if (i0 < n_local) store_quad(D.acc_scratch, base + i0, n_local - i0, vec, acc[m]);
   }
-  // Epilogue a7-a9.  ALL of a lane's susceptibility loads are issued together (one memory round trip, not one per
-  // quad); ts = susceptibility * sum goes to LDS (a lane reads back only what it wrote), so that the final loop is
-  // rolled.  In it a quad's infection thresholds are drawn (Philox: the epilogue's arithmetic, independent of the
-  // data) between its stores - measured: as a phase of its own in front of the loop the same arithmetic costs 40 %
-  // more, there is nothing in flight for it to hide behind.
-  const float now = D.clock ? D.clock->now : D.now;
-  const uint64_t step = D.clock ? D.clock->step : D.step;
+  return true;
+}
+
+// Epilogue a7-a9, first half.  ALL of a lane's susceptibility loads are issued together (one memory round trip, not one
+// per quad); ts = susceptibility * sum goes to LDS (a lane reads back only what it wrote), so that the final loop is
+// rolled.
+__device__ __forceinline__ void agents_ts_to_lds(const TileDArgs& D, const float (&acc)[kQuadsPerLane][4], float4* ts4,
+                                                 int64_t base, int n_local, int tid, bool vec) {
+  constexpr int kQ = kQuadsPerLane;
+  float sq[kQ][4];
+#pragma unroll
+  for (int m = 0; m < kQ; ++m) {
+    int i0 = 4 * (tid + m * kTileThreads);
+    asm volatile("" : "+v"(i0));          // (computed here, not carried through the direct sets as five 64-bit addresses)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) sq[m][j] = 0.0f;
+    if (i0 < n_local) load_quad(D.susceptibility, base + i0, n_local - i0, vec, sq[m]);
+  }
+  __syncthreads();          // every lane has its sums in registers, the last venue table has been read by every wave
+#pragma unroll
+  for (int m = 0; m < kQ; ++m) {
+    const int q = tid + m * kTileThreads;
+    if (4 * q < n_local)
+      ts4[q] = make_float4(sq[m][0] * acc[m][0], sq[m][1] * acc[m][1], sq[m][2] * acc[m][2], sq[m][3] * acc[m][3]);
+  }
+}
+
+// Epilogue a7-a9, second half: the rolled loop over a lane's quads.  In it a quad's infection thresholds are drawn
+// (Philox: the epilogue's arithmetic, independent of the data) between its stores - measured: as a phase of its own in
+// front of the loop the same arithmetic costs 40 % more, there is nothing in flight for it to hide behind.
+// Returns bit 4m + j: agent 4 * (tid + m * 1024) + j was infected in this step and a9 is still to be applied to it.
+__device__ __forceinline__ uint32_t agents_epilogue(const TileDArgs& D, const float4* ts4, int64_t base, int n_local,
+                                                    int tid, bool vec, const StepClock& clock) {
   const bool own_noise = D.sample && !D.exp_noise;
   const int mis = (int)((D.agent_offset + base) & 3);       // (wave-uniform: base is a multiple of 64)
-  float4* ts4 = reinterpret_cast<float4*>(lds_acc);
-  {
-    float sq[kQ][4];
-#pragma unroll
-    for (int m = 0; m < kQ; ++m) {
-      int i0 = 4 * (tid + m * kTileThreads);
-      asm volatile("" : "+v"(i0));          // (computed here, not carried through the direct sets as five 64-bit addresses)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) sq[m][j] = 0.0f;
-      if (i0 < n_local) load_quad(D.susceptibility, base + i0, n_local - i0, vec, sq[m]);
-    }
-    __syncthreads();          // every lane has its sums in registers, the last venue table has been read by every wave
-#pragma unroll
-    for (int m = 0; m < kQ; ++m) {
-      const int q = tid + m * kTileThreads;
-      if (4 * q < n_local)
-        ts4[q] = make_float4(sq[m][0] * acc[m][0], sq[m][1] * acc[m][1], sq[m][2] * acc[m][2], sq[m][3] * acc[m][3]);
-    }
-  }
-  GJ_STAMP(4);
-  uint32_t infected = 0u;                       // bit 4m + j: agent 4 * (tid + m * 1024) + j was infected in this step
+  uint32_t infected = 0u;
   int m_run = 0;
   for (int q = tid; 4 * q < n_local; q += kTileThreads, ++m_run) {
     const int i0 = 4 * q;
@@ -1673,9 +1639,7 @@ __global__ __launch_bounds__(kTileThreads) void k_tile_agents(const TileDArgs D)
     float p[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) p[j] = not_infected_prob(ts[j], D.dt);
-#ifndef GJ_DIAG_STAMPS
-    if (D.trans_susc) store_quad<true>(D.trans_susc, a0, n_ok, vec, ts);
-#endif
+    if (!kAgentStamps && D.trans_susc) store_quad<true>(D.trans_susc, a0, n_ok, vec, ts);
     if (D.not_infected_probs) store_quad<true>(D.not_infected_probs, a0, n_ok, vec, p);
     if (!D.sample) continue;
     float nw[4], th[4] = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -1684,8 +1648,8 @@ __global__ __launch_bounds__(kTileThreads) void k_tile_agents(const TileDArgs D)
       // block, any other quad two (wave-uniform: base is a multiple of 64)
       const uint64_t g0 = (uint64_t)(D.agent_offset + a0);
       uint32_t r0[4], r1[4] = {0u, 0u, 0u, 0u};
-      philox4x32_10(g0 >> 2, step, D.seed, r0);
-      if (mis) philox4x32_10((g0 >> 2) + 1, step, D.seed, r1);
+      philox4x32_10(g0 >> 2, clock.step, D.seed, r0);
+      if (mis) philox4x32_10((g0 >> 2) + 1, clock.step, D.seed, r1);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int w = mis + j;                       // word of the pair of blocks
@@ -1694,16 +1658,12 @@ __global__ __launch_bounds__(kTileThreads) void k_tile_agents(const TileDArgs D)
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      if (own_noise) {
-        nw[j] = own_new_infected(p[j], th[j]);
-      } else {
-        float e0 = 1.0f, e1 = 1.0f;
-        if (j < n_ok) {
-          e0 = D.exp_noise[a0 + j];
-          e1 = D.exp_noise[D.n_agents + a0 + j];
-        }
-        nw[j] = gumbel_new_infected(p[j], e0, e1);
+      float e0 = 1.0f, e1 = 1.0f;
+      if (!own_noise && j < n_ok) {
+        e0 = D.exp_noise[a0 + j];
+        e1 = D.exp_noise[D.n_agents + a0 + j];
       }
+      nw[j] = new_infected_of(!own_noise, p[j], e0, e1, th[j]);
       if (j < n_ok && nw[j] != 0.0f) infected |= 1u << (4 * m_run + j);
     }
     if (D.new_infected) store_quad<true>(D.new_infected, a0, n_ok, vec, nw);
@@ -1714,23 +1674,25 @@ __global__ __launch_bounds__(kTileThreads) void k_tile_agents(const TileDArgs D)
         infected &= ~(1u << (4 * m_run + j));
         const int64_t a = a0 + j;
         float sc = D.susceptibility[a], inf = D.is_infected[a], t_inf = D.infection_time[a];
-        infect(nw[j], now, sc, inf, t_inf);
+        infect(nw[j], clock.now, sc, inf, t_inf);
         D.susceptibility[a] = sc;
         D.is_infected[a] = inf;
         D.infection_time[a] = t_inf;
       }
     }
   }
-  // a9 for the agents infected in this step (new_infected == 1), all of a lane's at once: one memory round trip for
-  // the whole slice instead of one per quad that holds a new case (a wave covers 256 agents per iteration: at one
-  // new case per thousand agents a quarter of the iterations would wait on these loads)
-  GJ_STAMP(6);
-#ifndef GJ_TAIL_BATCHED
-  // Each lane takes its new cases one after the other: one memory round trip per case of the wave's busiest lane (a wave
-  // of 1 280 agents has a handful of new cases per step, two in one lane are rare), three loads issued together, ~30
-  // instructions.  (The batched form below - every (quad, agent) slot of the lane loaded straight-line, idle slots
-  // reading the slice's first agent - pays one round trip too, but 60 loads, 60 predicated stores and their address
-  // selects per lane whether there is a case or not: 8 % of the launch.)
+  return infected;
+}
+
+// a9 for the agents infected in this step (new_infected == 1), after the loop: not one memory round trip per quad that
+// holds a new case (a wave covers 256 agents per iteration: at one new case per thousand agents a quarter of the
+// iterations would wait on these loads).
+// Each lane takes its new cases one after the other: one memory round trip per case of the wave's busiest lane (a wave
+// of 1 280 agents has a handful of new cases per step, two in one lane are rare), three loads issued together, ~30
+// instructions.  (Measured and rejected, the batched form - every (quad, agent) slot of the lane loaded straight-line,
+// idle slots reading the slice's first agent - pays one round trip too, but 60 loads, 60 predicated stores and their
+// address selects per lane whether there is a case or not: 8 % of the launch.)
+__device__ __forceinline__ void agents_tail(const TileDArgs& D, uint32_t infected, int64_t base, int tid, float now) {
   if (__builtin_amdgcn_ballot_w64(infected != 0u) != 0ull) {
     uint32_t todo = infected;
     while (todo) {
@@ -1744,37 +1706,40 @@ __global__ __launch_bounds__(kTileThreads) void k_tile_agents(const TileDArgs D)
       D.infection_time[a] = tinf;
     }
   }
-#else
-  if (__builtin_amdgcn_ballot_w64(infected != 0u) != 0ull) {
-    // straight-line loads: a lane without a case at (m, j) reads the slice's first agent instead (one line for the
-    // whole wave) - a load under its own branch would be waited for on its own
-    float sc[kQ][4], inf[kQ][4], tinf[kQ][4];
-#pragma unroll
-    for (int m = 0; m < kQ; ++m) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const bool hit = (infected >> (4 * m + j)) & 1u;
-        const int64_t a = hit ? base + 4 * (tid + m * kTileThreads) + j : base;
-        sc[m][j] = D.susceptibility[a];
-        inf[m][j] = D.is_infected[a];
-        tinf[m][j] = D.infection_time[a];
-      }
-    }
-#pragma unroll
-    for (int m = 0; m < kQ; ++m) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int64_t a = base + 4 * (tid + m * kTileThreads) + j;
-        infect(1.0f, now, sc[m][j], inf[m][j], tinf[m][j]);
-        if ((infected >> (4 * m + j)) & 1u) {
-          D.susceptibility[a] = sc[m][j];
-          D.is_infected[a] = inf[m][j];
-          D.infection_time[a] = tinf[m][j];
-        }
-      }
-    }
+}
+
+__global__ __launch_bounds__(kTileThreads) void k_tile_agents(const TileDArgs D) {
+  extern __shared__ __align__(16) fx_t lds_acc[];
+  [[maybe_unused]] const AgentStamp gj_stamp;
+  const int tid = threadIdx.x;
+  const int s = blockIdx.x;
+  const int64_t base = (int64_t)s * D.slice_agents;
+  const int n_local = (int)min((int64_t)D.slice_agents, D.n_agents - base);
+  uint32_t* lds_flags = reinterpret_cast<uint32_t*>(lds_acc + D.slice_agents);   // two bits per agent (fx_flag): POS words, NEG words
+  const int fwords = D.slice_agents / 32;
+  agents_zero(lds_acc, lds_flags, fwords, n_local, tid);
+  DirectBatch first;                       // rows of the first direct item: their round trip hides behind the tiled sets
+  if (D.n_direct > 0) direct_load(D, D.direct[0], base, n_local, tid, 0, first);
+  __syncthreads();                         // the sums and flags are zero
+  agents_gather(D, lds_acc, lds_flags, fwords, s, base, n_local, tid);
+  GJ_STAMP(1);
+  float acc[kQuadsPerLane][4];
+  agents_sums_to_registers(lds_acc, lds_flags, fwords, D.slice_agents, n_local, tid, acc);
+  if (D.n_direct > 0) {
+    const uint32_t qmask = agents_quarantine_mask(D, base, n_local, tid);
+    GJ_STAMP(2);
+    direct_sets(D, acc, qmask, reinterpret_cast<float*>(lds_acc), base, n_local, tid, first, gj_stamp);
+    GJ_STAMP(3);
   }
-#endif
+  const bool vec = D.io_vec4 != 0;
+  if (agents_outputs(D, acc, base, n_local, tid, vec)) return;
+  const StepClock clock = step_clock(D);
+  float4* ts4 = reinterpret_cast<float4*>(lds_acc);
+  agents_ts_to_lds(D, acc, ts4, base, n_local, tid, vec);
+  GJ_STAMP(4);
+  const uint32_t infected = agents_epilogue(D, ts4, base, n_local, tid, vec, clock);
+  GJ_STAMP(6);
+  agents_tail(D, infected, base, tid, clock.now);
   GJ_STAMP(5);
 }
 

@@ -1081,7 +1081,6 @@ static int tiled_agents(const gj_plan* plan, const gj_agent_state* st, const gj_
     TDirect& X = D.direct[D.n_direct++];
     X.ell = run ? S.run_pv_win : S.ell;
     X.cum = E.cum;
-    X.K = 2;
     X.planes = run ? 1 : S.ell_k / 2;
     X.plane_stride = owned_slices * (int64_t)T->slice_agents * 2;
     X.V = run ? S.run_max_window : (int32_t)E.n_venues;      // (run form: the table is one slice's window of cum)
@@ -1124,7 +1123,6 @@ static int tiled_agents(const gj_plan* plan, const gj_agent_state* st, const gj_
       const int64_t cap = X.region ? cap1 : cap0;
       X.group_venues = sz <= cap ? X.V : (int32_t)(cap / X.stride);
       if (X.group_venues < 1 || (X.win_lo && sz > cap)) return GJ_E_PLAN;   // a window is staged whole
-      X._pad = 0;
       prev_region = X.region;
     }
     D.table_floats = (int32_t)cap0;

@@ -15,7 +15,8 @@ refusal, values beyond the fixed-point windows with either sign, and the public 
 Layout forms that run with transpose = 1 here (asserted on the plans' own fields in
 test_every_layout_form_runs_transposed and in the medium-world tests): workspace form of phases C + D (ell_k == 0),
 direct form (ell_k > 0) with one and with several venue groups, pass 1 in the direct form (presum), narrow, wide and
-explicit-slot descriptors, multi_slots rows, the run form, the split epilogue, several venue blocks per set."""
+explicit-slot descriptors, multi_slots rows, the run form, the split epilogue, several venue blocks per set; and, in
+test_chunks_without_slot_rows_walk_the_tile_tables, narrow and wide descriptors without the rows (the table walk)."""
 import math
 from types import SimpleNamespace
 
@@ -24,6 +25,7 @@ import pytest
 import torch
 
 import gj_testlib as L
+from grad_june_amd import tiling as TL
 from test_gpu_golden_parity import LAYOUT_IDS, LAYOUTS, engine_for
 from test_gpu_random_worlds import random_layout, random_world
 from test_transposed_reference import june769_case, qmask_of, signed_vector
@@ -227,6 +229,8 @@ def forms_of(host, split_epilogue=False):
         f.add("explicit" if t.slot_idx is not None and t.n_edges > 0 else ("wide" if t.desc_wide else "narrow"))
         if t.multi_slots is not None and len(t.multi_slots):
             f.add("multi_slots")
+        if TL.walk_share(t) > 0:
+            f.add("walk")
         if t.runs is not None:
             f.add("runs")
         if t.presum:
@@ -250,6 +254,56 @@ def test_every_layout_form_runs_transposed(device):
             assert e.plan.tiled_c.direct_table_floats == layout[1]["direct_table_floats"]
     assert seen >= {"direct", "workspace", "narrow", "wide", "explicit", "multi_slots", "runs", "presum", "blocks>1",
                     "split_epilogue"}, seen
+
+
+# Geometries of the reference world in which most household and company chunks span more tiles than their descriptor
+# expresses (tiling.walk_share: narrow 75 % / 91 %, wide 67 % / 73 %).  desc_explicit=False keeps the wide one on
+# descriptors (by itself it would switch to explicit slots).
+WALK_GEOMETRIES = [dict(sv_max=64, eb_target=512, slices="small", desc_wide=False, direct=False),
+                   dict(sv_max=16, eb_target=64, slices="small", desc_wide=True, desc_explicit=False, direct=False)]
+
+
+def test_chunks_without_slot_rows_walk_the_tile_tables(device, monkeypatch):
+    """A plan whose descriptors mark "multi" chunks and whose gj_tiled_set.multi_slots is NULL (valid input by
+    include/gradjune_hip.h; what build_tiled(multi_rows=False) gives): the lanes of such a chunk walk the tile tables in
+    phases A and D - narrow descriptors (chunk_slot_slow) and wide ones (chunk_slot_walk).  Next to it the same geometry
+    with the rows of explicit slots - for the wide descriptors the only layout that has rows at all.  Both resolve the
+    same slots and the sums are integer: per-element parity for each, forward and transposed, quarantine off and on, and
+    cum and the per-agent result bit for bit the same."""
+    import functools
+
+    real = TL.build_tiled
+    for geometry in WALK_GEOMETRIES:
+        engines = {}
+        for rows in (True, False):
+            with monkeypatch.context() as m:
+                if not rows:
+                    m.setattr(TL, "build_tiled", functools.partial(real, multi_rows=False))
+                engines[rows] = build(case_769(0, False), ("tiled", geometry), device)
+        tiled = {rows: {s.name: s.tiled for s in e.plan.host.sets} for rows, e in engines.items()}
+        for name in ("household", "company"):
+            walk, with_rows = tiled[False][name], tiled[True][name]
+            assert walk.multi_slots is None and TL.walk_share(walk) > 0.5, (geometry, name, TL.walk_share(walk))
+            assert with_rows.multi_slots is not None and len(with_rows.multi_slots) > 0, (geometry, name)
+            for t in (walk, with_rows):
+                assert t.slot_idx is None and bool(t.desc_wide) == geometry["desc_wide"], (geometry, name)
+        assert "walk" in forms_of(engines[False].plan.host) and "walk" not in forms_of(engines[True].plan.host)
+        for quarantine in (False, True):
+            case = case_769(0, quarantine)
+            x = signed_vector(case["world"]["n_agents"], 3)
+            for transpose in (0, 1):
+                what = f"{geometry} quarantine {quarantine} transpose {transpose}"
+                ref, got = reference(case, "x", x, bool(transpose)), {}
+                for rows, engine in engines.items():
+                    if transpose:
+                        check_parity(engine, case, "x", x, device, f"{what} rows {rows}")
+                    got[rows] = cum, out = run_passes(engine, case, x, device, transpose=transpose)
+                    for n in case["active"]:          # (check_parity's checks, for either direction)
+                        within(cum[n], ref["cum"][n], ref["cum_bound"][n], f"{what} rows {rows} cum/{n}")
+                    within(out, ref["out"], ref["out_bound"], f"{what} rows {rows} per agent")
+                for n in case["active"]:
+                    assert torch.equal(got[True][0][n], got[False][0][n]), (what, n)
+                assert torch.equal(got[True][1], got[False][1]), what
 
 
 # ---- 3. the adjoint identity ----------------------------------------------------------------------------------------------
