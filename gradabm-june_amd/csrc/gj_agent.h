@@ -676,4 +676,203 @@ __global__ __launch_bounds__(kThreads) void k_adjoint_group_stats(const GroupAdj
   }
 }
 
+// f2 by symptom stage (gj_stage_stats): a histogram of the agents over (group, stage) - the occupancy - and of those
+// whose stage differs from the previous step's - the entries - as 64-bit counts.  Most agents sit in one or two stages,
+// so one atomic per agent on the same address is the form to avoid.  kStageOne (one group): a lane counts in private
+// 8-bit fields - stage s is byte s % 8 of the low (s < 8) or high word - which the host's grid keeps from overflowing
+// (at most kStageLaneLoads loads of four agents per lane); the fields are added over the wave at the end.  kStageLds /
+// kStageGlobal (labels): a lane carries one open run keyed on the bin g * n_stages + s, closed by the whole wave as in
+// k_group_stats; the adds go to this workgroup's histogram of 32-bit counters in LDS, or to `out` as global atomics.
+// kStageOne and kStageLds end by adding the histogram's non-zero counters to `out`, one 64-bit atomic each.
+constexpr int kStageLdsBins = GJ_STAGE_LDS_BINS;       // 2 * 4 B * 8192 = 64 KiB of LDS per workgroup, as k_group_stats
+constexpr int kStageLdsThreads = GJ_STAGE_LDS_THREADS, kStageLdsBlocks = GJ_STAGE_LDS_BLOCKS;
+constexpr int kStageGlobalBlocks = GJ_STAGE_GLOBAL_BLOCKS;
+constexpr int kStageLaneLoads = GJ_STAGE_LANE_LOADS;   // 63 loads * 4 agents = 252 < 256: an 8-bit field holds them
+constexpr int kStageAdjLdsBins = GJ_STAGE_ADJ_LDS_BINS;   // the adjoint stages 2 * 4 B * 2048 = 16 KiB, as k_adjoint_group_stats
+constexpr uint32_t kStageBadLabel = GJ_STAGE_ERR_LABEL, kStageBadStage = GJ_STAGE_ERR_STAGE;
+static_assert(GJ_STAGE_GLOBAL_THREADS == kThreads && kStageLaneLoads * 4 < 256 && GJ_MAX_STAGES <= 16, "gj_stage_stats");
+enum { kStageOne = 0, kStageLds = 1, kStageGlobal = 2 };
+
+// The bin g * n_stages + s of one agent, or -1 for an agent that is skipped: a label outside [0, G) (never an index)
+// or a stage that is not an integer value in [0, S) (false for NaN).  ONE definition, for the histogram and its adjoint.
+__device__ __forceinline__ int stage_bin(int g, float stage, int G, int S, uint32_t& err) {
+  const bool label = (uint32_t)g < (uint32_t)G;
+  const bool value = stage >= 0.0f && stage < (float)S && stage == truncf(stage);
+  if (!label) err |= kStageBadLabel;
+  else if (!value) err |= kStageBadStage;
+  return (label && value) ? g * S + (int)stage : -1;
+}
+
+struct StageArgs {
+  int64_t n;
+  const int32_t* group;       // [n] or NULL (every agent in group 0)
+  const float* stage;
+  const float* prev;          // [n] or NULL (no entries)
+  int32_t n_groups, n_stages;
+  int32_t vec4;               // every array given is 16-byte aligned
+  unsigned long long* out;    // [2][n_groups][n_stages]
+  uint32_t* err;
+};
+
+template <int MODE>
+__global__ __launch_bounds__(MODE == kStageGlobal ? kThreads : kStageLdsThreads) void k_stage_stats(const StageArgs A) {
+  extern __shared__ uint32_t stage_hist[];     // kStageOne, kStageLds: [2 * bins]
+  const int G = A.n_groups, S = A.n_stages, bins = G * S;      // (bins <= INT32_MAX; the second plane is indexed in 64 bits)
+  if (MODE != kStageGlobal) {
+    for (int i = threadIdx.x; i < 2 * bins; i += blockDim.x) stage_hist[i] = 0;
+    __syncthreads();
+  }
+  const int lane = threadIdx.x % kWave;
+  uint64_t occ_lo = 0, occ_hi = 0, ent_lo = 0, ent_hi = 0;     // kStageOne: this lane's counts, 8 bits per stage
+  int run = -1;                                                // otherwise: the bin of this lane's open run
+  uint32_t ro = 0, re = 0;                                     // and its counts: occupancy, entries
+  uint32_t err = 0;
+  auto add = [&](int b, uint32_t o, uint32_t e) {
+    if (MODE == kStageGlobal) {
+      if (o) atomicAdd(&A.out[b], (unsigned long long)o);
+      if (e) atomicAdd(&A.out[(int64_t)bins + b], (unsigned long long)e);
+    } else {
+      if (o) atomicAdd(&stage_hist[b], o);
+      if (e) atomicAdd(&stage_hist[bins + b], e);
+    }
+  };
+  // wave-convergent: closes the run of every lane with `closing` set (k_group_stats' close_runs, on bins)
+  auto close_runs = [&](bool closing) {
+    closing = closing && run >= 0;
+#pragma unroll 1
+    for (int round = 0; round < 2; ++round) {
+      const unsigned long long m = __ballot(closing);
+      if (m == 0) return;
+      const int leader = __ffsll((long long)m) - 1;
+      const int bin = __shfl(run, leader, kWave);
+      const bool mine = closing && run == bin;
+      const uint32_t o = wave_sum<uint32_t>(mine ? ro : 0u), e = wave_sum<uint32_t>(mine ? re : 0u);
+      if (lane == leader) add(bin, o, e);
+      if (mine) closing = false, run = -1, ro = 0, re = 0;
+    }
+    if (closing) add(run, ro, re), run = -1, ro = 0, re = 0;
+  };
+  // one agent per lane (`on` = this lane has one); wave-convergent except in kStageOne
+  auto take = [&](bool on, int g, float stage, float prev) {
+    const int b = on ? stage_bin(g, stage, G, S, err) : -1;
+    const bool entered = A.prev != nullptr && prev != stage;
+    if (MODE == kStageOne) {                                   // (b = the stage, < 16)
+      const uint64_t one = b >= 0 ? 1ull << ((b & 7) * 8) : 0ull;
+      const uint64_t lo = b < 8 ? one : 0ull, hi = one ^ lo, e = entered ? ~0ull : 0ull;
+      occ_lo += lo, occ_hi += hi, ent_lo += lo & e, ent_hi += hi & e;
+      return;
+    }
+    const bool differs = b >= 0 && b != run;
+    if (__any(differs && run >= 0)) close_runs(differs);
+    if (b < 0) return;
+    run = b;
+    ro += 1u;
+    re += entered ? 1u : 0u;
+  };
+  // this workgroup's share, in units of four agents (vec4) or of one
+  const int64_t units = A.vec4 ? (A.n >> 2) : A.n;
+  const int64_t per = (units + gridDim.x - 1) / gridDim.x;
+  const int64_t u0 = (int64_t)blockIdx.x * per, u1 = (u0 + per < units) ? u0 + per : units;
+  for (int64_t base = u0; base < u1; base += blockDim.x) {     // (the same trip count for every lane of a wave)
+    const int64_t i = base + threadIdx.x;
+    const bool on = i < u1;
+    if (A.vec4) {
+      int4 g = make_int4(0, 0, 0, 0);
+      float4 s = make_float4(0.f, 0.f, 0.f, 0.f), p = s;
+      if (on) {
+        if (A.group) g = reinterpret_cast<const int4*>(A.group)[i];
+        s = reinterpret_cast<const float4*>(A.stage)[i];
+        if (A.prev) p = reinterpret_cast<const float4*>(A.prev)[i];
+      }
+      take(on, g.x, s.x, p.x);
+      take(on, g.y, s.y, p.y);
+      take(on, g.z, s.z, p.z);
+      take(on, g.w, s.w, p.w);
+    } else {
+      take(on, (on && A.group) ? A.group[i] : 0, on ? A.stage[i] : 0.f, (on && A.prev) ? A.prev[i] : 0.f);
+    }
+  }
+  if (A.vec4 && blockIdx.x == gridDim.x - 1 && threadIdx.x < kWave) {     // the n % 4 agents behind the last float4
+    const int64_t a = (units << 2) + threadIdx.x;
+    const bool on = a < A.n;
+    take(on, (on && A.group) ? A.group[a] : 0, on ? A.stage[a] : 0.f, (on && A.prev) ? A.prev[a] : 0.f);
+  }
+  if (MODE == kStageOne) {
+#pragma unroll
+    for (int s = 0; s < GJ_MAX_STAGES; ++s) {
+      if (s >= S) continue;                                    // (S is uniform: whole waves skip)
+      const int sh = (s & 7) * 8;
+      const uint32_t o = wave_sum<uint32_t>((uint32_t)((s < 8 ? occ_lo : occ_hi) >> sh) & 0xFFu);
+      const uint32_t e = wave_sum<uint32_t>((uint32_t)((s < 8 ? ent_lo : ent_hi) >> sh) & 0xFFu);
+      if (lane == 0) add(s, o, e);
+    }
+  } else {
+    close_runs(true);
+  }
+  if (err) atomicOr(A.err, err);
+  if (MODE != kStageGlobal) {
+    __syncthreads();
+    for (int i = threadIdx.x; i < 2 * bins; i += blockDim.x) {
+      const uint32_t v = stage_hist[i];
+      if (v) atomicAdd(&A.out[i], (unsigned long long)v);
+    }
+  }
+}
+
+// adjoint of gj_stage_stats: a gather through (label, stage)
+struct StageAdjArgs {
+  int64_t n;
+  const int32_t* group;
+  const float* stage;
+  const float* prev;
+  const float* g_occ;
+  const float* g_ent;
+  float* grad_stage;
+  int32_t n_groups, n_stages;
+  int32_t vec4;
+};
+
+template <bool LDS>
+__global__ __launch_bounds__(kThreads) void k_adjoint_stage_stats(const StageAdjArgs A) {
+  extern __shared__ float stage_staged[];     // LDS: g_occ [bins], g_ent [bins]
+  const int G = A.n_groups, S = A.n_stages, bins = G * S;
+  const float* go = A.g_occ;
+  const float* ge = A.g_ent;
+  if (LDS) {
+    for (int i = threadIdx.x; i < bins; i += blockDim.x) {
+      stage_staged[i] = go ? go[i] : 0.0f;
+      stage_staged[bins + i] = ge ? ge[i] : 0.0f;
+    }
+    __syncthreads();
+    go = stage_staged;
+    ge = stage_staged + bins;
+  }
+  // autograd of (stage == s) * stage / s, for the occupancy and (masked by the constant prev != stage) for the entries
+  auto grad = [&](int g, float stage, float prev) {
+    uint32_t unused = 0;
+    const int b = stage_bin(g, stage, G, S, unused);
+    if (b < 0 || stage == 0.0f) return 0.0f;
+    float v = go ? go[b] / stage : 0.0f;
+    if (A.prev && ge && prev != stage) v += ge[b] / stage;
+    return v;
+  };
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  int64_t first_scalar = 0;
+  if (A.vec4) {
+    const int64_t n4 = A.n >> 2;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+      const int4 g = A.group ? reinterpret_cast<const int4*>(A.group)[i] : make_int4(0, 0, 0, 0);
+      const float4 s = reinterpret_cast<const float4*>(A.stage)[i];
+      const float4 p = A.prev ? reinterpret_cast<const float4*>(A.prev)[i] : s;
+      reinterpret_cast<float4*>(A.grad_stage)[i] =
+          make_float4(grad(g.x, s.x, p.x), grad(g.y, s.y, p.y), grad(g.z, s.z, p.z), grad(g.w, s.w, p.w));
+    }
+    first_scalar = n4 << 2;
+  }
+  for (int64_t a = first_scalar + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; a < A.n; a += stride) {
+    const float s = A.stage[a];
+    A.grad_stage[a] = grad(A.group ? A.group[a] : 0, s, A.prev ? A.prev[a] : s);
+  }
+}
+
 }  // namespace gj

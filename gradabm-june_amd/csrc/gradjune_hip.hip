@@ -1558,6 +1558,69 @@ int gj_adjoint_group_stats(int64_t n, const int32_t* group, int32_t n_groups, co
   return gj::launch(gj::k_adjoint_group_stats<false>, blocks, gj::kThreads, 0, (hipStream_t)stream, S);
 }
 
+// the size checks gj_stage_stats and its adjoint share
+static int check_stage_sizes(int64_t n, const int32_t* group, int32_t n_groups, int32_t n_stages) {
+  if (n < 0 || n > GJ_STAGE_MAX_AGENTS || n_groups < 1 || n_groups > GJ_MAX_GROUPS) return GJ_E_RANGE;
+  if (n_stages < 1 || n_stages > GJ_MAX_STAGES || (int64_t)n_groups * n_stages > INT32_MAX) return GJ_E_RANGE;
+  if (!group && n_groups != 1) return GJ_E_RANGE;
+  return GJ_OK;
+}
+
+int gj_stage_stats(int64_t n, const int32_t* group, int32_t n_groups, int32_t n_stages, const float* current_stage,
+                   const float* prev_stage, int64_t* out, uint32_t* err, void* stream) {
+  if (const int rc = check_stage_sizes(n, group, n_groups, n_stages)) return rc;
+  if (!current_stage || !out || !err) return GJ_E_NULL;
+  if (n == 0) return GJ_OK;
+  gj::StageArgs S;
+  S.n = n;
+  S.group = group;
+  S.stage = current_stage;
+  S.prev = prev_stage;
+  S.n_groups = n_groups;
+  S.n_stages = n_stages;
+  S.vec4 = gj::aligned16(group, current_stage, prev_stage);
+  S.out = (unsigned long long*)out;
+  S.err = err;
+  const int64_t bins = (int64_t)n_groups * n_stages;
+  const int64_t units = S.vec4 ? (n >> 2) + 1 : n;
+  const size_t lds = (size_t)bins * 2 * sizeof(uint32_t);
+  if (n_groups == 1) {      // regime (i); no lane takes more than kStageLaneLoads loads
+    const int64_t lane_bound = gj::grid_for(units, 0, gj::kStageLdsThreads * gj::kStageLaneLoads);
+    const int64_t blocks = std::max(gj::grid_for(units, gj::kStageLdsBlocks, gj::kStageLdsThreads), lane_bound);
+    return gj::launch(gj::k_stage_stats<gj::kStageOne>, blocks, gj::kStageLdsThreads, lds, (hipStream_t)stream, S);
+  }
+  if (bins <= gj::kStageLdsBins)      // regime (ii)
+    return gj::launch(gj::k_stage_stats<gj::kStageLds>, gj::grid_for(units, gj::kStageLdsBlocks, gj::kStageLdsThreads),
+                      gj::kStageLdsThreads, lds, (hipStream_t)stream, S);
+  return gj::launch(gj::k_stage_stats<gj::kStageGlobal>, gj::grid_for(units, gj::kStageGlobalBlocks), gj::kThreads, 0,
+                    (hipStream_t)stream, S);      // regime (iii)
+}
+
+int gj_adjoint_stage_stats(int64_t n, const int32_t* group, int32_t n_groups, int32_t n_stages,
+                           const float* current_stage, const float* prev_stage, const float* g_occupancy,
+                           const float* g_entries, float* grad_stage, void* stream) {
+  if (const int rc = check_stage_sizes(n, group, n_groups, n_stages)) return rc;
+  if (!current_stage || !grad_stage) return GJ_E_NULL;
+  if (n == 0) return GJ_OK;
+  gj::StageAdjArgs S;
+  S.n = n;
+  S.group = group;
+  S.stage = current_stage;
+  S.prev = prev_stage;
+  S.g_occ = g_occupancy;
+  S.g_ent = g_entries;
+  S.grad_stage = grad_stage;
+  S.n_groups = n_groups;
+  S.n_stages = n_stages;
+  S.vec4 = gj::aligned16(group, current_stage, prev_stage, grad_stage);
+  const int64_t bins = (int64_t)n_groups * n_stages;
+  const int64_t blocks = gj::grid_for(gj::vec4_lanes(n, S.vec4), 2048);
+  if (bins <= gj::kStageAdjLdsBins)
+    return gj::launch(gj::k_adjoint_stage_stats<true>, blocks, gj::kThreads, (size_t)bins * 2 * sizeof(float),
+                      (hipStream_t)stream, S);
+  return gj::launch(gj::k_adjoint_stage_stats<false>, blocks, gj::kThreads, 0, (hipStream_t)stream, S);
+}
+
 int gj_step(const gj_plan* plan, const gj_agent_state* state, const gj_step_params* params, const gj_step_io* io,
             void* stream) {
   int rc = gj::check_plan(plan);

@@ -20,6 +20,13 @@ GJ_STREAM_EDGES = 2048
 GJ_MAX_GROUPS = 1 << 28
 GJ_GROUP_ERR_LABEL, GJ_GROUP_ERR_VALUE = 1, 2
 GJ_SEED_CHUNK = 1024
+# gj_stage_stats: error bits, the regime boundaries and the launch shapes (include/gradjune_hip.h)
+GJ_STAGE_ERR_LABEL, GJ_STAGE_ERR_STAGE = 1, 2
+GJ_STAGE_LDS_BINS, GJ_STAGE_ADJ_LDS_BINS = 8192, 2048
+GJ_STAGE_LDS_THREADS, GJ_STAGE_LDS_BLOCKS = 1024, 512
+GJ_STAGE_GLOBAL_THREADS, GJ_STAGE_GLOBAL_BLOCKS = 256, 2048
+GJ_STAGE_LANE_LOADS = 63
+GJ_STAGE_MAX_AGENTS = 1 << 40
 
 MASK_RAW, MASK_Q, MASK_QL, MASK_QL_AGE75 = 0, 1, 2, 3
 
@@ -240,6 +247,8 @@ SYMBOLS = {
     "gj_step_stats": (C.c_int, [C.c_int64, _vp, _vp, _vp, C.c_int32, C.POINTER(C.c_int32), C.c_int32, _vp, _vp]),
     "gj_group_stats": (C.c_int, [C.c_int64, _vp, C.c_int32, _vp, _vp, C.c_int32, _vp, _vp, _vp]),
     "gj_adjoint_group_stats": (C.c_int, [C.c_int64, _vp, C.c_int32, _vp, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
+    "gj_stage_stats": (C.c_int, [C.c_int64, _vp, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
+    "gj_adjoint_stage_stats": (C.c_int, [C.c_int64, _vp, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gj_step": (C.c_int, [C.POINTER(Plan), C.POINTER(AgentState), C.POINTER(StepParams), C.POINTER(StepIO), _vp]),
     "gj_step_phase": (
         C.c_int,

@@ -591,3 +591,30 @@ class GroupSeriesRow(torch.autograd.Function):
         want_inf, want_stage = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
         grads = stats.gather(stage, ctx.dead, _f32(g_cases, dev), _f32(g_deaths, dev), want_inf, want_stage)
         return (None, *_to_devices(grads, ctx.devices))
+
+
+class StageSeriesRow(torch.autograd.Function):
+    """One row of the symptom-stage series as an autograd node: current_stage -> (occupancy [G, S], entries [G, S]),
+    the float32 values of the counts of ``gj_stage_stats``, differentiable in the reference's form
+    ``sum (stage == s) * stage / s`` (column 0, ``recovered``, is a plain count).  ``env``: ``{"stats":
+    groups.StageStats, "prev": the previous row's stage, a detached constant, or None}``.  Forward = ``gj_stage_stats``
+    on a zeroed row; backward = ``gj_adjoint_stage_stats``, a gather through (label, stage)."""
+
+    @staticmethod
+    def forward(ctx, env, current_stage):
+        stats = env["stats"]
+        dev = stats.device
+        stage, prev = _f32(current_stage, dev), _f32(env.get("prev"), dev)
+        row = torch.zeros(2, stats.n_groups, stats.n_stages, dtype=torch.int64, device=dev)
+        stats.add(stage, prev, row)
+        ctx.stats, ctx.prev, ctx.device = stats, prev, current_stage.device
+        ctx.save_for_backward(stage)
+        row = row.to(torch.float32)
+        return row[0].clone(), row[1].clone()
+
+    @staticmethod
+    def backward(ctx, g_occupancy, g_entries):
+        (stage,) = ctx.saved_tensors
+        dev = ctx.stats.device
+        grad = ctx.stats.gather(stage, ctx.prev, _f32(g_occupancy, dev), _f32(g_entries, dev))
+        return None, grad.to(ctx.device)

@@ -173,7 +173,8 @@ class DistributedRunner(Runner):
         runner = cls(model=model, data=local, timer=Timer.from_parameters(params),
                      log_fraction_initial_cases=log_fraction,
                      save_path=params["save_path"], parameters=params,
-                     age_bins=params.get("age_bins_to_save", (0, 18, 65, 100)), seed_group=seed_group)
+                     age_bins=params.get("age_bins_to_save", (0, 18, 65, 100)), seed_group=seed_group,
+                     stages=params.get("stages_to_save"))
         runner.agent_offset = model.agent_range[0]
         runner.n_agents_total = n_total
         runner.group, runner.collectives = group, collectives
@@ -197,8 +198,9 @@ class DistributedRunner(Runner):
         if not self.collectives or not dist.is_initialized() or dist.get_world_size(self.group) == 1:
             return
         # (the series by agent group too: the labels were encoded on the whole world before the partition cut it, so the
-        # columns are the same on every rank)
-        for series in [self._series, *getattr(self, "_group_series", {}).values()]:
+        # columns are the same on every rank; the symptom-stage counts are int64 and go the same way)
+        for series in [self._series, *getattr(self, "_group_series", {}).values(),
+                       *getattr(self, "_stage_series", {}).values()]:
             if dist.get_backend(self.group) == "gloo":            # tests: staged through the host
                 host = series[:n_rows].cpu()
                 dist.all_reduce(host, group=self.group)

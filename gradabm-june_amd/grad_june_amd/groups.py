@@ -20,6 +20,8 @@ from . import _native as N
 
 #: result keys of Runner.forward() that a group name must not shadow
 _RESERVED = re.compile(r"age(_\d+)?")
+#: stage names whose series <st>_per_timestep / <st>_by_<name> would shadow a result key of Runner.forward()
+_STAGE_SHADOWS = ("cases", "daily_cases", "deaths")
 
 
 class GroupLabelError(RuntimeError):
@@ -145,6 +147,92 @@ class GroupStats:
             if err & N.GJ_GROUP_ERR_VALUE:
                 why.append("an is_infected that is not finite or beyond 2^18 (it was counted as 0)")
             raise GroupLabelError(f"{what}: " + " and ".join(why))
+
+
+class StageLabelError(RuntimeError):
+    """gj_stage_stats met a label outside [0, n_groups) or a stage that is no integer in [0, n_stages)."""
+
+
+def stages_to_save(spec, stages) -> List[str]:
+    """The YAML key ``stages_to_save`` / the Runner's ``stages=``: a list of names of ``symptoms.stages``, or ``all``.
+    Returns the names in the order given (``all``: the model's order).  An unknown name, and a name whose result keys
+    ``<st>_per_timestep`` / ``new_<st>_per_timestep`` / ``<st>_by_<name>`` would shadow a key the Runner already
+    reports, raise ``ValueError``."""
+    stages = [str(s) for s in stages]
+    if spec is None or (isinstance(spec, (list, tuple)) and not spec):
+        return []
+    if isinstance(spec, str):
+        spec = stages if spec == "all" else [spec]
+    names = [str(s) for s in spec]
+    for st in names:
+        if st not in stages:
+            raise ValueError(f"stages_to_save: '{st}' is no symptom stage (known: {stages})")
+        if st in _STAGE_SHADOWS or "new_" + st in names:
+            raise ValueError(f"stages_to_save: the series of stage '{st}' would shadow the result key '{st}_per_timestep'")
+    if len(set(names)) != len(names):
+        raise ValueError(f"stages_to_save: a stage is given twice ({names})")
+    return names
+
+
+class StageStats:
+    """``gj_stage_stats`` / ``gj_adjoint_stage_stats`` for one labelling of the agents, or for none (``labels`` None:
+    the national call, one group): the labels, the shape of the histogram and the sticky error word."""
+
+    def __init__(self, labels, n_groups: int, n_stages: int, device=None):
+        if n_groups < 1 or n_groups > N.GJ_MAX_GROUPS:
+            raise ValueError(f"n_groups = {n_groups}: expected 1 .. {N.GJ_MAX_GROUPS}")
+        if n_stages < 1 or n_stages > N.GJ_MAX_STAGES or n_groups * n_stages > 2 ** 31 - 1:
+            raise ValueError(f"n_stages = {n_stages}: expected 1 .. {N.GJ_MAX_STAGES}, n_groups * n_stages < 2^31")
+        if labels is None and n_groups != 1:
+            raise ValueError("no labels: one group")
+        dev = torch.device(device) if device is not None else labels.device
+        self.labels = None if labels is None else labels.detach().to(device=dev, dtype=torch.int32).contiguous()
+        self.n_groups, self.n_stages, self.device = int(n_groups), int(n_stages), dev
+        self.err = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    def _agents(self, *per_agent) -> int:
+        n = per_agent[0].numel()
+        for t in per_agent:
+            if t is not None and (t.numel() != n or t.dtype != torch.float32 or not t.is_contiguous()):
+                raise ValueError("per-agent arguments: contiguous float32 tensors of one length")
+        if self.labels is not None and self.labels.numel() != n:
+            raise ValueError(f"{n} stages for {self.labels.numel()} labels")
+        return n
+
+    def add(self, current_stage: torch.Tensor, prev_stage, out: torch.Tensor) -> None:
+        """out[0] += occupancy [G, S]; out[1] += entries [G, S] where ``prev_stage`` (or None) differs (int64, device)."""
+        n = self._agents(current_stage, prev_stage)
+        if out.dtype != torch.int64 or out.numel() != 2 * self.n_groups * self.n_stages or not out.is_contiguous():
+            raise ValueError("out: a contiguous int64 tensor of 2 * n_groups * n_stages elements")
+        N.check(N.load().gj_stage_stats(n, N.ptr(self.labels), self.n_groups, self.n_stages, N.ptr(current_stage),
+                                        N.ptr(prev_stage), N.ptr(out), N.ptr(self.err), N.current_stream()),
+                "gj_stage_stats")
+
+    def gather(self, current_stage, prev_stage, g_occupancy, g_entries) -> torch.Tensor:
+        """The adjoint: grad_stage [n] for the cotangents [G, S] (fp32, or None = zeros) of the two planes."""
+        n = self._agents(current_stage, prev_stage)
+        for g in (g_occupancy, g_entries):
+            if g is not None and (g.dtype != torch.float32 or g.numel() != self.n_groups * self.n_stages
+                                  or not g.is_contiguous()):
+                raise ValueError("cotangents: contiguous float32 tensors of n_groups * n_stages elements")
+        grad = torch.empty(n, dtype=torch.float32, device=self.device)
+        N.check(N.load().gj_adjoint_stage_stats(n, N.ptr(self.labels), self.n_groups, self.n_stages,
+                                                N.ptr(current_stage), N.ptr(prev_stage), N.ptr(g_occupancy),
+                                                N.ptr(g_entries), N.ptr(grad), N.current_stream()),
+                "gj_adjoint_stage_stats")
+        return grad
+
+    def check(self, what: str = "gj_stage_stats") -> None:
+        """Raise if a launch since the last check met a bad label or stage (one device read)."""
+        err = int(self.err.item()) & 0xFFFFFFFF
+        if err:
+            self.err.zero_()
+            why = []
+            if err & N.GJ_STAGE_ERR_LABEL:
+                why.append(f"a label outside [0, {self.n_groups}) (its agent was skipped)")
+            if err & N.GJ_STAGE_ERR_STAGE:
+                why.append(f"a stage that is no integer in [0, {self.n_stages}) (its agent was skipped)")
+            raise StageLabelError(f"{what}: " + " and ".join(why))
 
 
 class SeedPlan:

@@ -50,7 +50,7 @@ def world_from_npz(path) -> HeteroData:
 
 class Runner(torch.nn.Module):
     def __init__(self, model, data, timer, log_fraction_initial_cases, save_path, parameters,
-                 age_bins=(0, 18, 65, 100), groups=None, seed_group=None):
+                 age_bins=(0, 18, 65, 100), groups=None, seed_group=None, stages=None):
         super().__init__()
         self.model = model
         self.data = data
@@ -79,6 +79,13 @@ class Runner(torch.nn.Module):
             raise ValueError(f"seed_group '{seed_group}': no such labelling (present: {sorted(self.group_keys)})")
         self.seed_group = seed_group
         self._seed_plan = None
+        # symptom-stage series (not in the reference): ``stages`` = names of ``symptoms.stages`` or "all" (the YAML key
+        # ``stages_to_save``): the occupancy of each stage and the entries into it, nationally and by every labelling
+        from .groups import stages_to_save
+
+        self.stage_names = [str(s) for s in model.symptoms_updater.symptoms_sampler.stages] if stages else []
+        self.stages_saved = stages_to_save(stages, self.stage_names)
+        self._stage_stats = None
         self.restore_initial_data()
 
     @classmethod
@@ -103,6 +110,7 @@ class Runner(torch.nn.Module):
             parameters=params,
             age_bins=params.get("age_bins_to_save", (0, 18, 65, 100)),
             seed_group=seed_group,
+            stages=params.get("stages_to_save"),
         )
 
     @staticmethod
@@ -277,6 +285,36 @@ class Runner(torch.nn.Module):
         for name, stats in self._groups().items():
             stats.add(inf, stage, dead, self._group_series[name][row])
 
+    # per-step symptom-stage series: one gj_stage_stats pass for the nation and one per labelling ------------------
+    def _stages(self):
+        """{None or labelling name: groups.StageStats} (empty without ``stages_to_save``: nothing is allocated or launched)."""
+        if self._stage_stats is None:
+            self._stage_stats = {}
+            if self.stages_saved:
+                from .groups import StageStats
+
+                dev, S = require_hip(self.device), len(self.stage_names)
+                self._stage_stats[None] = StageStats(None, 1, S, device=dev)
+                for name, st in self._groups().items():
+                    self._stage_stats[name] = StageStats(st.labels, st.n_groups, S, device=dev)
+        return self._stage_stats
+
+    def _record_stages(self, data, row, diff_rows=None):
+        stage = data["agent"].symptoms["current_stage"]
+        if diff_rows is not None:                 # differentiable run: the rows stay on the autograd graph
+            from .autograd import StageSeriesRow
+
+            for key, stats in self._stages().items():
+                diff_rows[key].append(torch.stack(StageSeriesRow.apply({"stats": stats, "prev": self._stage_prev}, stage)))
+            # the next row's previous stage: a stage on the graph is a fresh tensor of its step (SymptomsStep) that
+            # nothing updates in place - it is kept as it is; one that is updated in place is copied
+            self._stage_prev = stage.detach() if stage.requires_grad else stage.detach().to(torch.float32, copy=True)
+            return
+        cur = stage.detach().to(torch.float32).contiguous()
+        for key, stats in self._stages().items():
+            stats.add(cur, self._stage_prev, self._stage_series[key][row])
+        self._stage_prev.copy_(cur)
+
     # time loop --------------------------------------------------------------------------------------
     def forward(self):
         timer, model, data = self.timer, self.model, self.data
@@ -305,12 +343,23 @@ class Runner(torch.nn.Module):
         self._group_series = {name: torch.zeros(n_rows, 2 * st.n_groups, dtype=torch.float64,
                                                 device=require_hip(self.device)) for name, st in groups.items()}
         group_diff_rows = {name: [] for name in groups} if differentiable else None
+        stages = self._stages()
+        # (a differentiable run keeps its rows on the graph instead: no int64 series then)
+        self._stage_series = {} if differentiable else {
+            key: torch.zeros(n_rows, 2, st.n_groups, st.n_stages, dtype=torch.int64, device=st.device)
+            for key, st in stages.items()}
+        stage_diff_rows = {key: [] for key in stages} if differentiable else None
+        if stages:      # row 0 counts its entries against the restored initial stage: the agents the seed moved
+            self._stage_prev = self.data_backup["symptoms"]["current_stage"].detach().to(
+                device=require_hip(self.device), dtype=torch.float32, copy=True).contiguous()
 
         def record(row, done=False):
             if not done:
                 self._record(data, row)
             if groups:
                 self._record_groups(data, row, group_diff_rows)
+            if stages:
+                self._record_stages(data, row, stage_diff_rows)
             if differentiable:
                 ag = data["agent"]
                 stage = ag.symptoms["current_stage"]
@@ -361,6 +410,18 @@ class Runner(torch.nn.Module):
             results[f"daily_cases_by_{name}"] = torch.diff(by_group[:, :G], dim=0,
                                                            prepend=torch.zeros(1, G, device=by_group.device))
             results[f"deaths_by_{name}"] = by_group[:, G:]
+        for key, st in stages.items():      # every stage was counted: the columns asked for are selected here
+            st.check("symptom-stage series" + (f" by {key}" if key else ""))
+            if differentiable:
+                counts = self._reduce_differentiable(torch.stack(stage_diff_rows[key]))
+            else:
+                counts = self._stage_series[key][: row + 1].to(torch.float32)      # [T, 2, G, S]
+            for name in self.stages_saved:
+                s = self.stage_names.index(name)
+                tail = "per_timestep" if key is None else f"by_{key}"
+                occupancy, entries = counts[:, 0, :, s], counts[:, 1, :, s]
+                results[f"{name}_{tail}"] = occupancy[:, 0] if key is None else occupancy
+                results[f"new_{name}_{tail}"] = entries[:, 0] if key is None else entries
         is_infected = data["agent"].is_infected
         if "original_index" in data["agent"]:
             out = torch.empty_like(is_infected)
@@ -388,8 +449,9 @@ class Runner(torch.nn.Module):
         for name, keys in self.group_keys.items():      # [T, G] series: long format, one file per labelling
             if f"cases_by_{name}" not in results:       # a labelling that is only seeded by has no series
                 continue
+            saved = [c for st in self.stages_saved for c in (st, "new_" + st)]
             cols = {c: results[f"{c}_by_{name}"].detach().cpu().numpy().reshape(-1)
-                    for c in ("cases", "daily_cases", "deaths")}
+                    for c in ("cases", "daily_cases", "deaths", *saved)}
             pd.DataFrame({"date": np.repeat(np.asarray(results["dates"], dtype=object), len(keys)),
                           name: np.tile(keys, len(results["dates"])), **cols}).to_csv(
                 self.save_path / f"results_by_{name}.csv", index=False)

@@ -430,6 +430,62 @@ int gj_adjoint_group_stats(int64_t n, const int32_t* group, int32_t n_groups, co
                            int32_t dead_stage, const float* g_cases, const float* g_deaths, float* grad_is_infected,
                            float* grad_stage, void* stream);
 
+/* ---- row f2 by symptom stage: occupancy of every stage and the entries into it, nationally or by agent group ------
+ * A pure addition to ABI 7.  What hospital data records - beds occupied, daily admissions - are the number of agents
+ * in `severe` / `critical` and the entries into them; the reference reduces only the last stage to a series
+ * (store_differentiable_deaths, runner.py:198-215).  For agent a with g = group[a] (0 when group is NULL) and
+ * s = (int)current_stage[a]:
+ *   out[0][g][s] += 1                                                      (occupancy)
+ *   out[1][g][s] += 1  if prev_stage is given and prev_stage[a] != current_stage[a]   (a entered s during this step)
+ * out: device int64 [2][n_groups][n_stages]; the call ADDS to it.  The counts are 64-bit integers: no order of the
+ * agents, no grid and no regime changes a bit, and there is neither a workspace nor a finish launch.
+ * Bad input never reaches a bin: an agent whose label is outside [0, n_groups) is skipped (the label is never used as
+ * an index) and sets GJ_STAGE_ERR_LABEL in *err; a current_stage that is not an integer value in [0, n_stages) - NaN,
+ * 2.5, -1, n_stages - is skipped and sets GJ_STAGE_ERR_STAGE.  *err (device uint32) is sticky until the caller clears it.
+ * group: device int32 [n], or NULL = every agent in group 0 (n_groups must be 1).  prev_stage: device fp32 [n] or
+ * NULL (plane 1 is then left alone).  n_groups * n_stages <= INT32_MAX; n <= GJ_STAGE_MAX_AGENTS.
+ * One pass, 8 B per agent (12 with labels), a workgroup reads a CONTIGUOUS share of the agents; four agents per lane
+ * and load when every array is 16-byte aligned.  Three regimes:
+ *  (i)   n_groups == 1 (the national call, where most agents share one or two bins): every lane counts in private
+ *        8-bit fields of four 64-bit registers, the lanes' counts are added by wave shuffles at the end and at most
+ *        2 * n_stages 64-bit atomics per workgroup reach memory.  The grid is sized so that a lane takes at most
+ *        GJ_STAGE_LANE_LOADS loads of four agents: a field cannot overflow.
+ *  (ii)  n_groups * n_stages <= GJ_STAGE_LDS_BINS: a lane carries one open run keyed on the bin g * n_stages + s; the
+ *        lanes of a wave that close the same bin fold their counts with shuffles and one adds to the workgroup's
+ *        histogram of 32-bit counters in LDS (2 * 4 B * 8192 = 64 KiB at most), whose non-zero counters are added to
+ *        `out` at the end, one 64-bit atomic each.
+ *  (iii) above that: the same runs, one global 64-bit atomic per folded run.
+ * (i) and (ii) launch at most GJ_STAGE_LDS_BLOCKS workgroups of GJ_STAGE_LDS_THREADS lanes ((i): more where the lane
+ * bound asks for it), (iii) at most GJ_STAGE_GLOBAL_BLOCKS of GJ_STAGE_GLOBAL_THREADS.
+ * Errors, returned before any device work: GJ_E_RANGE for n < 0 or > GJ_STAGE_MAX_AGENTS, n_groups outside
+ * 1..GJ_MAX_GROUPS, n_stages outside 1..GJ_MAX_STAGES, n_groups * n_stages > INT32_MAX, group == NULL with
+ * n_groups != 1; GJ_E_NULL for a NULL current_stage, out or err.                                                     */
+#define GJ_STAGE_ERR_LABEL 1u
+#define GJ_STAGE_ERR_STAGE 2u
+#define GJ_STAGE_LDS_BINS 8192
+#define GJ_STAGE_LDS_THREADS 1024
+#define GJ_STAGE_LDS_BLOCKS 512
+#define GJ_STAGE_GLOBAL_THREADS 256
+#define GJ_STAGE_GLOBAL_BLOCKS 2048
+#define GJ_STAGE_LANE_LOADS 63
+#define GJ_STAGE_MAX_AGENTS ((int64_t)1 << 40)
+int gj_stage_stats(int64_t n, const int32_t* group, int32_t n_groups, int32_t n_stages, const float* current_stage,
+                   const float* prev_stage, int64_t* out, uint32_t* err, void* stream);
+
+/* adjoint of gj_stage_stats.  The differentiable value of a count is the reference's own form for deaths
+ * (store_differentiable_deaths, and mask_stage * current_stage / i in sample_next_stage): sum (stage == s) * stage / s;
+ * the entry mask (prev != stage) is a constant.  With s = current_stage[a], g = group[a]:
+ *   grad_stage[a] = g_occupancy[g][s] / s + (prev_stage[a] != current_stage[a] ? g_entries[g][s] / s : 0)    for s >= 1
+ *   grad_stage[a] = 0                                              for s == 0, a bad label or a bad stage (as above)
+ * Column 0 (`recovered`) is therefore a plain count with zero gradient: the reference's form divides by the stage id.
+ * g_occupancy / g_entries: device fp32 [n_groups][n_stages], NULL = zeros.  grad_stage: device fp32 [n], written for
+ * every agent.  A gather; up to GJ_STAGE_ADJ_LDS_BINS bins the two tables are staged in LDS once per workgroup.
+ * Errors as for gj_stage_stats, with GJ_E_NULL for a NULL current_stage or grad_stage.                              */
+#define GJ_STAGE_ADJ_LDS_BINS 2048
+int gj_adjoint_stage_stats(int64_t n, const int32_t* group, int32_t n_groups, int32_t n_stages,
+                           const float* current_stage, const float* prev_stage, const float* g_occupancy,
+                           const float* g_entries, float* grad_stage, void* stream);
+
 /* ---- row f3: adjoint (backward) of one hot-path step, forward-only kernels reused ---------------
  * The aggregation ts = susc * sum_n w_n * (M_n^T diag(beta_n p_contact) M_n)(m_n * transmission) is
  * self-adjoint up to the exchange of the masks m_n <-> w_n, so its backward is the same four tiled
