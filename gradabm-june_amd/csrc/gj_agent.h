@@ -324,7 +324,8 @@ __device__ __forceinline__ float digamma(float x) {
 //   dT/d shape   = T * (ln u - psi(shape))           (torch: pow'(exponent) = pow * ln(base), masked to 0 at base == 0
 //                                                     with exponent >= 0; lgamma' = digamma)
 //   dT/d rate    = T * (shape / rate - d)
-//   dT/d shift   = T * (rate - (shape - 1) / d)      (= -dT/dt: the infection_time term shares it)
+//   dT/d shift   = T * (rate - (shape - 1) / d)      (= -dT/dt: the infection_time term shares it; d == 0 is taken apart
+//                                                     from the division, see below)
 // Each NULL output is neither computed nor written: a launch moves bytes only for the parameters that need a gradient.
 // is_infected == 0 gives 0 in every output.
 template <bool PARAMS>
@@ -344,7 +345,17 @@ __device__ __forceinline__ void adjoint_transmission_agent(
   float p_mx = 0.0f, p_shp = 0.0f, p_rt = 0.0f, dtdt = 0.0f;  // d trans / d parameter; d trans / d t = -dT/d shift
   if (inf != 0.0f) {
     const float T = base * inf;
-    dtdt = T * ((s - 1.0f) / h.d - r);
+    if (h.d != 0.0f) {
+      dtdt = T * ((s - 1.0f) / h.d - r);
+    } else {
+      // t == shift exactly (a constant integer shape and a shift that is a multiple of the step: once per infected
+      // agent): T * ((s - 1) / 0 - r) is T * (0 / 0) at shape 1 and 0 * inf at shape >= 2.  The derivative of the pow
+      // as torch takes it, y * pow(base, y - 1) with a zero exponent y contributing 0: -r T at shape 1,
+      // max_inf * sign / Gamma(2) * aux2 * is_infected * r at shape 2, 0 above; +-inf or NaN at a non-integer shape < 2.
+      const float y = s - 1.0f;
+      const float lead = (y == 0.0f) ? 0.0f : y * fast_pow(0.0f, y - 1.0f);
+      dtdt = mx[a] * h.sign * inv_gamma(s) * h.aux2 * inf * r * lead - r * T;
+    }
     if (PARAMS && grad_mx) p_mx = h.sign * h.aux * h.aux2 * inf;
     if (PARAMS && grad_shp) {
       const float u = h.d * r;

@@ -264,7 +264,15 @@ __device__ __forceinline__ float fast_pow(float x, float y) {
   }
   return __builtin_amdgcn_exp2f(y * __builtin_amdgcn_logf(x));      // v_exp_f32(y * v_log_f32(x))
 }
-__device__ __forceinline__ float fast_exp(float e) { return __builtin_amdgcn_exp2f(e * 1.44269504088896341f); }
+// v_exp_f32 flushes a subnormal RESULT to 0 where expf underflows gradually.  Alone that is an absolute error below
+// 2^-126; but next to a pow that has overflowed (shape 28, d * rate = 100: pow(100, 27) = inf, exp(-100) = 3.8e-44) it
+// turns the reference's inf * 3.8e-44 = inf into inf * 0 = NaN.  Below 2^-126 the result is therefore taken as
+// exp2(x + 32) * 2^-32 (the product is an ordinary multiply, which keeps subnormals); above, the multiply by 1 changes no bit.
+__device__ __forceinline__ float fast_exp(float e) {
+  const float x = e * 1.44269504088896341f;
+  const bool tiny = x < -126.0f;
+  return __builtin_amdgcn_exp2f(tiny ? x + 32.0f : x) * (tiny ? 2.3283064365386963e-10f : 1.0f);
+}
 
 // The head of the profile, shared by the update and its adjoints (which must give the update's bits):
 // transmission = max_infectiousness * sign * aux * aux2 * is_infected, with t the time since infection and d = t - shift.

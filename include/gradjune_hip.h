@@ -506,7 +506,11 @@ int gj_adjoint_stage_stats(int64_t n, const int32_t* group, int32_t n_groups, in
  *   with d = t - shift, u = d * rate:  d/d max_infectiousness = sign * aux * aux2 * is_infected,
  *   d/d shape = trans * (ln u - digamma(shape)), d/d rate = trans * (shape / rate - d),
  *   d/d shift = trans * (rate - (shape - 1) / d); 0 where is_infected == 0.  Each of the four outputs may be NULL:
- *   a NULL output is neither computed nor written.                                                    */
+ *   a NULL output is neither computed nor written.
+ *   d == 0 (t == shift exactly; both entry points): d trans/d t is not taken through the division but as torch's
+ *   autograd gives it, max_inf * sign / Gamma(shape) * aux2 * is_infected * rate * (shape - 1) * pow(0, shape - 2)
+ *   - rate * trans with a zero exponent contributing 0: -rate * trans at shape 1, max_inf * rate^2 * is_infected at
+ *   shape 2, 0 above - finite for every integer shape.                                                */
 int gj_adjoint_sample(int64_t n, const float* susceptibility0, const float* infection_time0, const float* acc,
                       const float* exp_noise, uint64_t seed, uint64_t step, int64_t agent_offset, float now,
                       float delta_time, const float* g_susc, const float* g_inf, const float* g_time,
