@@ -131,9 +131,12 @@ __device__ __forceinline__ float gumbel_new_infected(float p, float e0, float e1
   return 1.0f - ret0;
 }
 
-// a9: GradJune.infect_people (reference grad_june/model.py:103-110)
+// a9: GradJune.infect_people (reference grad_june/model.py:103-110).  torch.maximum passes a NaN through where fmaxf
+// would swallow it: a NaN new_infected (a NaN probability, an injected draw of 0) or a NaN susceptibility leaves the
+// susceptibility NaN like is_infected and infection_time, not 0.
 __device__ __forceinline__ void infect(float nw, float now, float& susc, float& inf, float& t_inf) {
-  susc = fmaxf(0.0f, susc - nw);
+  const float x = susc - nw;
+  susc = (x != x) ? x : fmaxf(0.0f, x);
   inf = inf + nw;
   t_inf = t_inf + nw * (now - t_inf);
 }

@@ -333,7 +333,11 @@ int gj_agent_gather(const gj_plan* plan, const gj_agent_state* state,
 /* a8 + a9 alone on a given probability vector: replaces IsInfectedSampler.forward +
  * infect_people for callers that hold `not_infected_probs` (e.g. infect_fraction_of_people,
  * grad_june/infection.py:31-42).  The three state pointers may ALL be NULL: then only
- * `new_infected` is produced (IsInfectedSampler.forward alone).                             */
+ * `new_infected` is produced (IsInfectedSampler.forward alone).
+ * new_infected is exactly 0 or 1 (a tie of the two softmax terms: 0), or NaN where torch gives NaN: a NaN
+ * probability or an injected draw of 0.  An agent with new_infected == 0 keeps its state bits.  The others get
+ * max(0, s - nu), i + nu, t + nu * (now - t) as separate fp32 operations; a NaN nu or a NaN susceptibility gives
+ * a NaN susceptibility (torch.maximum), like is_infected and infection_time, in the fused step too.           */
 int gj_sample_infect(int64_t n_agents, const float* not_infected_probs, const float* exp_noise,
                      uint64_t seed, uint64_t step, int64_t agent_offset, float now,
                      float* new_infected, float* susceptibility, float* is_infected,
@@ -497,6 +501,12 @@ int gj_adjoint_stage_stats(int64_t n, const int32_t* group, int32_t n_groups, in
  *   step's noise (or Philox key) and the gradients w.r.t. the step's outputs (NULL = zeros).
  *   Outputs: x_out = susc0 * ts_bar (input of the transposed passes), grad_susc_out (complete),
  *   grad_time_out = g_time * (1 - new_infected).
+ *   Per agent, with the rules of gj_adjoint_seed below: ts = susc0 * acc and the clamp's mask 1e-6f <= ts <= 100f are
+ *   taken in fp32 (ts_bar is 0 outside it and for a NaN ts); d nu / d p is 0 where it is not finite (p == 0 or 1
+ *   after rounding, a NaN softmax: torch's autograd gives NaN there); the subgradient of max(0, susc0 - nu) is 0.5
+ *   at the tie.  All in fp32: against fp64, ts_bar is good to about 2^-24 * (50 L + 10 (|ln p| + 2) / (1 - p)) relative,
+ *   L the sum of the four |ln| of p, 1 - p and the two draws, and is 0 where y0 * y1 underflows fp32
+ *   (tests/gj_sampler_ref.py: the bound, per agent; measured in tests/test_gpu_sampler_kernels.py).
  * gj_adjoint_transmission: through the transmission profile (transmission.py:39-51):
  *   grad_inf_out = g_inf + trans_bar * d trans/d is_infected;
  *   grad_time_inout += trans_bar * d trans/d infection_time.

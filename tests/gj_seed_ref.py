@@ -30,7 +30,8 @@ def library_draws(seed: int, step: int, agent_offset: int, n: int):
     return theta.astype(np.float64) * s, (np.float32(1.0) - theta).astype(np.float64) * s, theta
 
 
-def _softmax_terms(p, e0, e1, dtype):
+def softmax_terms(p, e0, e1, dtype):
+    """y0, y1 of the tau = 0.1 softmax in ``dtype``, op for op as csrc/gj_device.h:sampler_softmax"""
     p, e0, e1 = (np.asarray(v, dtype=dtype) for v in (p, e0, e1))
     tau = dtype(TAU)
     with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
@@ -46,7 +47,7 @@ def decisions(p, e0=None, e1=None, theta=None, dtype=np.float64):
     p < theta for the library's.  Returned as ``dtype``."""
     if theta is not None:
         return (np.asarray(p, dtype=np.float32) < np.asarray(theta, dtype=np.float32)).astype(dtype)
-    y0, y1 = _softmax_terms(p, e0, e1, np.float32)
+    y0, y1 = softmax_terms(p, e0, e1, np.float32)
     return (y1 > y0).astype(dtype)
 
 
@@ -56,6 +57,18 @@ def seed_forward(p_not_by_group, labels, susc0, inf0, time0, now, e0=None, e1=No
     nu = decisions(p, e0, e1, theta, dtype)
     s0, i0, t0 = (np.asarray(v, dtype=dtype) for v in (susc0, inf0, time0))
     return nu, np.maximum(dtype(0.0), s0 - nu), i0 + nu, t0 + nu * (dtype(now) - t0)
+
+
+def sampler_adjoint_terms(p, s0, t0, y0, y1, nu, now, gs, gi, gt, gn, dtype):
+    """(h, nu_bar, d nu / d p) of one agent's a8 + a9 adjoint, every argument an array of ``dtype`` (csrc/gj_device.h,
+    sample_adjoint): shared by the seed's adjoint below and by the sampler's (tests/gj_sampler_ref.py)."""
+    x = s0 - nu
+    h = np.where(x > 0, dtype(1.0), np.where(x == 0, dtype(0.5), dtype(0.0)))
+    nu_bar = gi + gt * (dtype(now) - t0) - gs * h + gn
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        dnu_dp = -(y0 * y1 / dtype(TAU)) * (dtype(1.0) / p + dtype(1.0) / (dtype(1.0) - p))
+        dnu_dp = np.where(np.abs(dnu_dp) < 3.0e38, dnu_dp, dtype(0.0))
+    return h, nu_bar, dnu_dp
 
 
 def seed_adjoint(p_not_by_group, labels, n_groups, susc0, time0, now, e0, e1, theta=None, g_susc=None, g_inf=None,
@@ -72,15 +85,10 @@ def seed_adjoint(p_not_by_group, labels, n_groups, susc0, time0, now, e0, e1, th
     gs, gi, gt, gn = (zeros if g is None else np.asarray(g, dtype=dtype) for g in (g_susc, g_inf, g_time, g_new))
     s0, t0 = np.asarray(susc0, dtype=dtype), np.asarray(time0, dtype=dtype)
     p = np.asarray(p_not_by_group, dtype=dtype)[lab]
-    y0, y1 = _softmax_terms(p, e0, e1, dtype)
+    y0, y1 = softmax_terms(p, e0, e1, dtype)
     nu = decisions(p, e0, e1, theta, dtype) if nu is None else np.asarray(nu, dtype=dtype)
     nu = np.where(valid, nu, dtype(0.0))
-    x = s0 - nu
-    h = np.where(x > 0, dtype(1.0), np.where(x == 0, dtype(0.5), dtype(0.0)))
-    nu_bar = gi + gt * (dtype(now) - t0) - gs * h + gn
-    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
-        dnu_dp = -(y0 * y1 / dtype(TAU)) * (dtype(1.0) / p + dtype(1.0) / (dtype(1.0) - p))
-    dnu_dp = np.where(np.abs(dnu_dp) < 3.0e38, dnu_dp, dtype(0.0))
+    h, nu_bar, dnu_dp = sampler_adjoint_terms(p, s0, t0, y0, y1, nu, now, gs, gi, gt, gn, dtype)
     c = np.where(valid, -(nu_bar * dnu_dp), dtype(0.0))
     c64 = c.astype(np.float64)
     return {"grad_fraction": np.bincount(lab, weights=c64, minlength=n_groups)[:n_groups],
