@@ -19,6 +19,7 @@
 #include "gj_device.h"
 #include "gj_tiled.h"
 #include "gj_agent.h"
+#include "gj_location.h"
 
 namespace gj {
 
@@ -1619,6 +1620,67 @@ int gj_adjoint_stage_stats(int64_t n, const int32_t* group, int32_t n_groups, in
     return gj::launch(gj::k_adjoint_stage_stats<true>, blocks, gj::kThreads, (size_t)bins * 2 * sizeof(float),
                       (hipStream_t)stream, S);
   return gj::launch(gj::k_adjoint_stage_stats<false>, blocks, gj::kThreads, 0, (hipStream_t)stream, S);
+}
+
+int gj_location_stats(const gj_plan* plan, const gj_step_params* params, const gj_location_rows* rows,
+                      const float* new_infected, const float* susceptibility0, const float* current_stage,
+                      const int32_t* group, int32_t n_groups, const int32_t* cols, int32_t n_cols,
+                      int32_t background_col, int64_t* out, uint32_t* err, void* stream) {
+  int rc = gj::check_plan(plan);
+  if (rc) return rc;
+  gj::Groups G;
+  rc = gj::group_networks(plan, params, &G);
+  if (rc) return rc;
+  if (!new_infected || !susceptibility0 || !out || !err) return GJ_E_NULL;
+  if ((plan->n_sets > 0 && !rows) || (params->n_nets > 0 && !cols)) return GJ_E_NULL;
+  if (params->has_quarantine && !current_stage) return GJ_E_NULL;
+  if (n_groups < 1 || n_groups > GJ_MAX_GROUPS || (!group && n_groups != 1)) return GJ_E_RANGE;
+  if (n_cols < 1 || n_cols > GJ_LOC_MAX_COLS || background_col < 0 || background_col >= n_cols) return GJ_E_RANGE;
+  for (int i = 0; i < params->n_nets; ++i)
+    if (cols[i] < 0 || cols[i] >= n_cols) return GJ_E_RANGE;
+  gj::LocArgs A = {};
+  for (int g = 0; g < G.n; ++g) {
+    const gj_edge_set& E = plan->sets[G.set[g]];
+    const gj_location_rows& R = rows[G.set[g]];
+    if (R.a_rowptr && !R.a_venue && E.n_edges > 0) return GJ_E_NULL;
+    const gj::NetGroup C = gj::classify_group(params, G, g);
+    gj::LocSet& S = A.sets[g];
+    S.rowptr = R.a_rowptr;
+    S.venue = R.a_venue;
+    S.cum = E.cum;
+    S.n_edges = (int32_t)E.n_edges;
+    S.n_venues = (int32_t)E.n_venues;
+    S.stride = E.cum_stride;
+    S.nk = C.nk;
+    S.first = G.first[g];
+    memcpy(S.mask, C.mask, sizeof(S.mask));
+    memcpy(S.table, C.table, sizeof(S.table));
+  }
+  if (plan->n_agents == 0) return GJ_OK;
+  A.n = plan->n_agents;
+  A.nu = new_infected;
+  A.s0 = susceptibility0;
+  A.stage = params->has_quarantine ? current_stage : nullptr;
+  A.group = group;
+  A.cls = plan->agent_class;
+  A.tables = plan->tables;
+  A.out = (unsigned long long*)out;
+  A.err = err;
+  A.n_groups = n_groups;
+  A.n_cols = n_cols;
+  A.n_nets = params->n_nets;
+  A.background = background_col;
+  A.n_sets = G.n;
+  A.has_q = params->has_quarantine ? 1 : 0;
+  A.day_type = params->day_type;
+  A.q_thr = params->q_threshold;
+  for (int i = 0; i < params->n_nets; ++i) A.cols[i] = cols[i];
+  const int64_t blocks = gj::grid_for(A.n, gj::kLocBlocks, gj::kLocLoads * gj::kWave);
+  const int64_t bins = (int64_t)n_groups * n_cols;
+  if (bins <= gj::kLocLdsBins)
+    return gj::launch(gj::k_location_stats<true>, blocks, gj::kThreads, (size_t)bins * sizeof(unsigned long long),
+                      (hipStream_t)stream, A);
+  return gj::launch(gj::k_location_stats<false>, blocks, gj::kThreads, 0, (hipStream_t)stream, A);
 }
 
 int gj_step(const gj_plan* plan, const gj_agent_state* state, const gj_step_params* params, const gj_step_io* io,

@@ -27,6 +27,10 @@ GJ_STAGE_LDS_THREADS, GJ_STAGE_LDS_BLOCKS = 1024, 512
 GJ_STAGE_GLOBAL_THREADS, GJ_STAGE_GLOBAL_BLOCKS = 256, 2048
 GJ_STAGE_LANE_LOADS = 63
 GJ_STAGE_MAX_AGENTS = 1 << 40
+# gj_location_stats: the fixed-point unit of one infection, error bits, limits and the launch shape
+GJ_LOC_UNIT = 1 << 30
+GJ_LOC_ERR_LABEL, GJ_LOC_ERR_VALUE, GJ_LOC_ERR_ROWS = 1, 2, 4
+GJ_LOC_MAX_COLS, GJ_LOC_LDS_BINS, GJ_LOC_BLOCKS = 64, 4096, 2048
 
 MASK_RAW, MASK_Q, MASK_QL, MASK_QL_AGE75 = 0, 1, 2, 3
 
@@ -191,6 +195,13 @@ class SymptomsParams(C.Structure):
     ]
 
 
+class LocationRows(C.Structure):
+    _fields_ = [
+        ("a_rowptr", _vp),
+        ("a_venue", _vp),
+    ]
+
+
 class SeedPlan(C.Structure):
     _fields_ = [
         ("n_sorted", C.c_int64),
@@ -249,6 +260,11 @@ SYMBOLS = {
     "gj_adjoint_group_stats": (C.c_int, [C.c_int64, _vp, C.c_int32, _vp, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
     "gj_stage_stats": (C.c_int, [C.c_int64, _vp, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
     "gj_adjoint_stage_stats": (C.c_int, [C.c_int64, _vp, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gj_location_stats": (
+        C.c_int,
+        [C.POINTER(Plan), C.POINTER(StepParams), C.POINTER(LocationRows), _vp, _vp, _vp, _vp, C.c_int32,
+         C.POINTER(C.c_int32), C.c_int32, C.c_int32, _vp, _vp, _vp],
+    ),
     "gj_step": (C.c_int, [C.POINTER(Plan), C.POINTER(AgentState), C.POINTER(StepParams), C.POINTER(StepIO), _vp]),
     "gj_step_phase": (
         C.c_int,

@@ -235,6 +235,95 @@ class StageStats:
             raise StageLabelError(f"{what}: " + " and ".join(why))
 
 
+class LocationError(RuntimeError):
+    """gj_location_stats met a label outside [0, n_groups), a new_infected that is neither 0 nor 1, a NaN or negative
+    term, or a row outside its edge set."""
+
+
+def locations_to_save(spec) -> bool:
+    """The YAML key ``locations_to_save`` / the Runner's ``locations=``: true or false (absent: false)."""
+    if spec is None:
+        return False
+    if isinstance(spec, (bool, np.bool_)):
+        return bool(spec)
+    raise ValueError(f"locations_to_save: expected true or false, not {spec!r}")
+
+
+def location_keys(networks) -> List[str]:
+    """Columns of the infection-location series: the network names in the order given (``infection_networks.networks``),
+    then ``background`` (an infection nobody transmitted: the reference's probability floor), then ``seed``."""
+    names = [str(n) for n in networks]
+    for reserved in ("background", "seed"):
+        if reserved in names:
+            raise ValueError(f"a network named '{reserved}' would shadow that column of the infection-location series")
+    return names + ["background", "seed"]
+
+
+class LocationStats:
+    """``gj_location_stats`` for one labelling of the agents, or for none (``labels`` None: the national call, one
+    group).  Owns the integer series ``out`` [rows, n_groups, len(columns)] - units of 1 / GJ_LOC_UNIT of an infection -
+    and the sticky error word."""
+
+    def __init__(self, labels, n_groups: int, columns, device=None, n_rows: int = 1):
+        if n_groups < 1 or n_groups > N.GJ_MAX_GROUPS:
+            raise ValueError(f"n_groups = {n_groups}: expected 1 .. {N.GJ_MAX_GROUPS}")
+        if labels is None and n_groups != 1:
+            raise ValueError("no labels: one group")
+        self.columns = [str(c) for c in columns]
+        if not 1 <= len(self.columns) <= N.GJ_LOC_MAX_COLS or len(set(self.columns)) != len(self.columns):
+            raise ValueError(f"columns: 1 .. {N.GJ_LOC_MAX_COLS} distinct names, not {self.columns}")
+        dev = torch.device(device) if device is not None else labels.device
+        self.labels = None if labels is None else labels.detach().to(device=dev, dtype=torch.int32).contiguous()
+        self.n_groups, self.n_cols, self.device = int(n_groups), len(self.columns), dev
+        self.err = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.reset(n_rows)
+
+    def reset(self, n_rows: int = 1) -> None:
+        self.out = torch.zeros(int(n_rows), self.n_groups, self.n_cols, dtype=torch.int64, device=self.device)
+
+    def add(self, plan, params, new_infected, susceptibility0, current_stage, active=(), background="background",
+            row: int = 0, edges=None) -> None:
+        """out[row] += the shares of the step ``params`` describes (a ``gj_step_params``, after its ``gj_step`` on
+        ``plan``: the plan's ``cum`` workspaces hold that step's sums).  ``active``: the column name of each of the
+        step's networks, in the order of ``params.nets``; ``edges``: see ``DevicePlan.location_rows``."""
+        n = plan.host.n_agents
+        for t in (new_infected, susceptibility0, current_stage):
+            if t is not None and (t.numel() != n or t.dtype != torch.float32 or not t.is_contiguous()
+                                  or t.device != self.device):
+                raise ValueError(f"per-agent arguments: contiguous float32[{n}] on {self.device}")
+        if self.labels is not None and self.labels.numel() != n:
+            raise ValueError(f"{n} agents for {self.labels.numel()} labels")
+        if len(active) != params.n_nets:
+            raise ValueError(f"{len(active)} columns for {params.n_nets} active networks")
+        import ctypes as C
+
+        cols = (C.c_int32 * max(1, len(active)))(*[self.columns.index(str(c)) for c in active])
+        N.check(N.load().gj_location_stats(
+            C.byref(plan.c), C.byref(params), plan.location_rows(edges), N.ptr(new_infected), N.ptr(susceptibility0),
+            N.ptr(current_stage), N.ptr(self.labels), self.n_groups, cols, self.n_cols,
+            self.columns.index(background), N.ptr(self.out[row]), N.ptr(self.err), N.current_stream()),
+            "gj_location_stats")
+
+    def values(self, n_rows=None) -> torch.Tensor:
+        """The series in infections: out / GJ_LOC_UNIT formed in fp64, then float32 [rows, n_groups, columns]."""
+        out = self.out if n_rows is None else self.out[:n_rows]
+        return (out.to(torch.float64) / float(N.GJ_LOC_UNIT)).to(torch.float32)
+
+    def check(self, what: str = "gj_location_stats") -> None:
+        """Raise if a launch since the last check met bad input (one device read)."""
+        err = int(self.err.item()) & 0xFFFFFFFF
+        if err:
+            self.err.zero_()
+            why = []
+            if err & N.GJ_LOC_ERR_LABEL:
+                why.append(f"a label outside [0, {self.n_groups}) (its agent was skipped)")
+            if err & N.GJ_LOC_ERR_VALUE:
+                why.append("a new_infected that is neither 0 nor 1 (skipped) or a NaN / negative term (counted as 0)")
+            if err & N.GJ_LOC_ERR_ROWS:
+                why.append("a row pointer or venue id outside its edge set (skipped)")
+            raise LocationError(f"{what}: " + " and ".join(why))
+
+
 class SeedPlan:
     """One labelling as ``gj_adjoint_seed`` wants it (include/gradjune_hip.h, gj_seed_plan): the agents with a label in
     [0, n_groups) sorted by label (stable), every group's segment cut into chunks of GJ_SEED_CHUNK agents.  Built once per

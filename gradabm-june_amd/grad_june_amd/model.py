@@ -32,6 +32,7 @@ class GradJune(torch.nn.Module):
         self.rng_seed = None        # Philox key; defaults to torch.initial_seed() at first use
         self.n_steps = 0            # Philox stream id: one stream per forward() call
         self.step_stats = None      # see forward()
+        self.location_stats = None  # see forward()
 
     @classmethod
     def from_file(cls, fpath=None):
@@ -77,6 +78,10 @@ class GradJune(torch.nn.Module):
         betas = self._betas(engine, active, timer)
         where = self._launch_env(engine, timer, active, betas, has_q, step)
         exp_noise = self._exp_noise(engine, exp_noise)
+        # infection-location series: what forward() launches gj_location_stats with after the step (s0 and stage are
+        # filled in by the path taken)
+        self._location_step = (None if getattr(self, "location_stats", None) is None else
+                               {"engine": engine, "params": where["params"], "active": [n.name for n in active]})
         if differentiable:
             return self._hot_path_differentiable(data, engine, where, active, betas, has_q, exp_noise, want_probs)
         return self._hot_path_in_place(data, engine, where, has_q, exp_noise, want_probs)
@@ -107,6 +112,8 @@ class GradJune(torch.nn.Module):
         n, device = engine.plan.host.n_agents, engine.plan.device
         new_infected = torch.empty(n, dtype=torch.float32, device=device)
         probs = torch.empty(n, dtype=torch.float32, device=device) if want_probs else None
+        if self._location_step is not None:      # the step overwrites the susceptibility: keep what it started from
+            self._location_step.update(s0=bufs.tensors["susceptibility"].clone(), stage=bufs.tensors["current_stage"])
         engine.step(bufs, where["params"],
                     engine.io(not_infected_probs=probs, new_infected=new_infected, exp_noise=exp_noise))
         return new_infected, probs
@@ -126,13 +133,40 @@ class GradJune(torch.nn.Module):
         env = dict(where, fixed=fixed, stage=stage, exp_noise=exp_noise, nets=list(active), betas=betas)
         state = [ag[k] if ag[k].dtype == torch.float32 else ag[k].to(torch.float32) for k in
                  ("susceptibility", "is_infected", "infection_time")]
+        if self._location_step is not None:      # the node returns new tensors: the incoming one stays as it is
+            self._location_step.update(s0=f(state[0]), stage=stage)
         susc, inf, time, new_infected = HotPathStep.apply(env, *state, *[n_.log_beta for n_ in active],
                                                           *profile_inputs(ip))
         ag.susceptibility, ag.is_infected, ag.infection_time = susc, inf, time
         return new_infected, None
 
+    @staticmethod
+    def location_edges(data, plan):
+        """What ``DevicePlan.location_rows`` builds the by-agent rows from - the world's COO edge lists, in the agent
+        order in use - or None once the plan holds them (built once, kept with the plan)."""
+        if getattr(plan, "_location_rows", None) is not None:
+            return None
+        return {s: data["attends_" + s].edge_index for s in plan.host.set_index if "attends_" + s in data}
+
+    def _record_locations(self, sink, data, new_infected):
+        """gj_location_stats on the step just run (the plan's ``cum`` workspaces still hold its sums), for every
+        ``groups.LocationStats`` of the sink: from detached tensors, so the series carry no gradient."""
+        step = self._location_step
+        plan = step["engine"].plan
+        nu = new_infected.detach().to(device=plan.device, dtype=torch.float32).contiguous()
+        edges = self.location_edges(data, plan)
+        for stats in sink["stats"]:
+            stats.add(plan, step["params"], nu, step["s0"], step["stage"], active=step["active"],
+                      background="background", row=sink["row"], edges=edges)
+
     def forward(self, data, timer, exp_noise=None):
         new_infected, _ = self.hot_path(data, timer, exp_noise=exp_noise)
+        # location_stats: set by the Runner for the duration of its time loop, like step_stats - the step's new
+        # infections are attributed to the networks BEFORE the symptoms update, while current_stage is still the stage
+        # the quarantine mask was formed from.  Without it nothing is cloned and nothing is launched
+        sink = getattr(self, "location_stats", None)
+        if sink is not None:
+            self._record_locations(sink, data, new_infected)
         # in grad mode new_infected stays on the graph: the symptoms update is then an autograd node too
         # (autograd.SymptomsStep), which is what makes the deaths series differentiable (runner.py:198-215)
         # step_stats: set by the Runner for the duration of its time loop - the per-step result reductions

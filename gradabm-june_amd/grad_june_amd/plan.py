@@ -650,6 +650,46 @@ class DevicePlan:
         stride = self.c.sets[i].cum_stride
         return self.cum[i][: self.host.sets[i].n_venues * stride].view(self.host.sets[i].n_venues, stride)
 
+    def location_rows(self, edges=None):
+        """The ``gj_location_rows`` array of ``gj_location_stats``: every set's edges as CSR by owned agent, built on
+        first use and kept with the plan (only the infection-location series asks for it).
+
+        A plan that holds the CSR arrays (layout "csr" / "both") reuses them.  Otherwise ``edges`` supplies the COO
+        lists, ``{set name: edge_index [2, E]}`` or ``{set name: (agent, venue)}`` in the agent order of this plan: a
+        stable sort by agent keeps the COO order inside a row (torch ops on the device, 4 B per edge).  A set that is
+        in neither gets no rows (it contributes nothing)."""
+        if getattr(self, "_location_rows", None) is not None:
+            return self._location_rows
+        dev, n = self.device, self.host.n_agents
+        rows = (N.LocationRows * N.GJ_MAX_SETS)()
+        keep = []
+        for i, s in enumerate(self.host.sets):
+            t = self.keep[i]
+            if t.get("a_rowptr") is not None:
+                rowptr, venue = t["a_rowptr"], t["a_venue"]
+            elif edges is not None and s.name in edges:
+                e = edges[s.name]
+                agent, venue = (e[0], e[1])
+                to = lambda a: (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))).to(dev)
+                agent, venue = to(agent).long(), to(venue)
+                if self.host.n_ext_agents > n:                       # halo agents' edges belong to another rank's rows
+                    own = agent < n
+                    agent, venue = agent[own], venue[own]
+                if agent.numel() and (int(agent.min()) < 0 or int(agent.max()) >= n or int(venue.min()) < 0
+                                      or int(venue.max()) >= s.n_venues):
+                    raise ValueError(f"edge set {s.name}: an agent or venue index outside the plan")
+                order = torch.argsort(agent, stable=True)
+                venue = venue[order].to(torch.int32).contiguous()
+                zero = torch.zeros(1, dtype=torch.int64, device=dev)
+                rowptr = torch.cat((zero, torch.cumsum(torch.bincount(agent, minlength=n), 0))).to(torch.int32).contiguous()
+            else:
+                continue
+            keep.append((rowptr, venue))
+            rows[i].a_rowptr, rows[i].a_venue = rowptr.data_ptr(), venue.data_ptr()
+        self._location_rows_keep = keep
+        self._location_rows = rows
+        return rows
+
     def bytes_resident(self) -> int:
         n = 0
         for t in self.keep:

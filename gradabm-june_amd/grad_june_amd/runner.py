@@ -50,8 +50,9 @@ def world_from_npz(path) -> HeteroData:
 
 class Runner(torch.nn.Module):
     def __init__(self, model, data, timer, log_fraction_initial_cases, save_path, parameters,
-                 age_bins=(0, 18, 65, 100), groups=None, seed_group=None, stages=None):
+                 age_bins=(0, 18, 65, 100), groups=None, seed_group=None, stages=None, locations=None):
         super().__init__()
+        self._refuse_locations(locations)
         self.model = model
         self.data = data
         self.data_backup = self.backup_infection_data(data)
@@ -86,7 +87,24 @@ class Runner(torch.nn.Module):
         self.stage_names = [str(s) for s in model.symptoms_updater.symptoms_sampler.stages] if stages else []
         self.stages_saved = stages_to_save(stages, self.stage_names)
         self._stage_stats = None
+        # infection-location series (not in the reference): ``locations=True`` (the YAML key ``locations_to_save``):
+        # each step's new infections attributed to the networks they came through, nationally and by every labelling
+        from .groups import location_keys, locations_to_save
+
+        self.locations_saved = locations_to_save(locations)
+        self.location_keys = location_keys(model.infection_networks.networks) if self.locations_saved else []
+        self._location_stats = None
         self.restore_initial_data()
+
+    _supports_locations = True
+
+    @classmethod
+    def _refuse_locations(cls, spec):
+        from .groups import locations_to_save
+
+        if locations_to_save(spec) and not cls._supports_locations:
+            raise NotImplementedError("locations_to_save: the infection-location series is not available in a "
+                                      "partitioned run")
 
     @classmethod
     def from_file(cls, fpath=None):
@@ -111,6 +129,7 @@ class Runner(torch.nn.Module):
             age_bins=params.get("age_bins_to_save", (0, 18, 65, 100)),
             seed_group=seed_group,
             stages=params.get("stages_to_save"),
+            locations=params.get("locations_to_save"),
         )
 
     @staticmethod
@@ -226,6 +245,8 @@ class Runner(torch.nn.Module):
                 data=self.data, timer=self.timer, symptoms_updater=self.model.symptoms_updater,
                 fractions=fractions, labels=labels, device=self.device,
                 agent_offset=getattr(self, "agent_offset", 0), plan=plan, all_reduce=self._seed_all_reduce())
+        if self.locations_saved:      # row 0 of the infection-location series
+            self._seed_new_infected = new_infected.detach()
         self.model.symptoms_updater(data=self.data, timer=self.timer, new_infected=new_infected)
 
     # per-step result reductions: one fused pass (gj_step_stats) into a preallocated series ------------
@@ -315,6 +336,33 @@ class Runner(torch.nn.Module):
             stats.add(cur, self._stage_prev, self._stage_series[key][row])
         self._stage_prev.copy_(cur)
 
+    # per-step infection-location series: one gj_location_stats pass for the nation and one per labelling -----------
+    def _locations(self):
+        """{None or labelling name: groups.LocationStats} (empty without ``locations_to_save``: nothing is allocated,
+        cloned or launched)."""
+        if self._location_stats is None:
+            self._location_stats = {}
+            if self.locations_saved:
+                from .groups import LocationStats
+
+                dev = require_hip(self.device)
+                self._location_stats[None] = LocationStats(None, 1, self.location_keys, device=dev)
+                for name, st in self._groups().items():
+                    self._location_stats[name] = LocationStats(st.labels, st.n_groups, self.location_keys, device=dev)
+        return self._location_stats
+
+    def _record_seed_locations(self, locations):
+        """Row 0: the seeding step.  No network is active, so every seeded agent lands in the column ``seed``."""
+        dev = require_hip(self.device)
+        engine = self.model._engine(self.data, dev)
+        params = engine.params(now=self.timer.now, delta_time=self.timer.duration, day_type=0, active=[], betas={})
+        f = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
+        nu, s0 = f(self._seed_new_infected), f(self.data_backup["susceptibility"])
+        for stats in locations.values():
+            stats.add(engine.plan, params, nu, s0, None, active=(), background="seed", row=0,
+                      edges=self.model.location_edges(self.data, engine.plan))
+        self._seed_new_infected = None
+
     # time loop --------------------------------------------------------------------------------------
     def forward(self):
         timer, model, data = self.timer, self.model, self.data
@@ -353,6 +401,12 @@ class Runner(torch.nn.Module):
             self._stage_prev = self.data_backup["symptoms"]["current_stage"].detach().to(
                 device=require_hip(self.device), dtype=torch.float32, copy=True).contiguous()
 
+        locations = self._locations()
+        for st in locations.values():
+            st.reset(n_rows)
+        if locations:
+            self._record_seed_locations(locations)
+
         def record(row, done=False):
             if not done:
                 self._record(data, row)
@@ -379,10 +433,13 @@ class Runner(torch.nn.Module):
                 cls, edges, dead = self._stats_args(data)
                 sink = {"cls": cls, "edges": edges, "n_bins": n_bins, "dead": dead, "out": self._series[row]}
             model.step_stats = sink
+            if locations:
+                model.location_stats = {"stats": list(locations.values()), "row": row}
             try:
                 data = model(data, timer)
             finally:
                 model.step_stats = None
+                model.location_stats = None
             record(row, done=bool(sink and sink.get("done")))
             dates.append(timer.date)
         self._finalize_series(row + 1)
@@ -422,6 +479,13 @@ class Runner(torch.nn.Module):
                 occupancy, entries = counts[:, 0, :, s], counts[:, 1, :, s]
                 results[f"{name}_{tail}"] = occupancy[:, 0] if key is None else occupancy
                 results[f"new_{name}_{tail}"] = entries[:, 0] if key is None else entries
+        for key, st in locations.items():      # out / 2^30 in fp64, then float32 like the other series; no gradient
+            st.check("infection-location series" + (f" by {key}" if key else ""))
+            values = st.values(row + 1)
+            if key is None:
+                results["infections_by_location"] = values[:, 0, :]
+            else:
+                results[f"infections_by_location_by_{key}"] = values
         is_infected = data["agent"].is_infected
         if "original_index" in data["agent"]:
             out = torch.empty_like(is_infected)
@@ -455,6 +519,19 @@ class Runner(torch.nn.Module):
             pd.DataFrame({"date": np.repeat(np.asarray(results["dates"], dtype=object), len(keys)),
                           name: np.tile(keys, len(results["dates"])), **cols}).to_csv(
                 self.save_path / f"results_by_{name}.csv", index=False)
+        if "infections_by_location" in results:      # long format: date, location, infections
+            dates, L = np.asarray(results["dates"], dtype=object), len(self.location_keys)
+            pd.DataFrame({"date": np.repeat(dates, L), "location": np.tile(self.location_keys, len(dates)),
+                          "infections": results["infections_by_location"].detach().cpu().numpy().reshape(-1)}).to_csv(
+                self.save_path / "results_by_location.csv", index=False)
+            for name, keys in self.group_keys.items():
+                if f"infections_by_location_by_{name}" not in results:
+                    continue
+                G = len(keys)
+                pd.DataFrame({"date": np.repeat(dates, G * L), name: np.tile(np.repeat(np.asarray(keys), L), len(dates)),
+                              "location": np.tile(self.location_keys, len(dates) * G),
+                              "infections": results[f"infections_by_location_by_{name}"].detach().cpu().numpy().reshape(-1)}
+                             ).to_csv(self.save_path / f"results_by_location_by_{name}.csv", index=False)
         pd.DataFrame({"is_infected": is_infected.detach().cpu().numpy()}).to_csv(
             self.save_path / "results_is_infected.csv")
 

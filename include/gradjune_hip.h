@@ -490,6 +490,58 @@ int gj_adjoint_stage_stats(int64_t n, const int32_t* group, int32_t n_groups, in
                            const float* current_stage, const float* prev_stage, const float* g_occupancy,
                            const float* g_entries, float* grad_stage, void* stream);
 
+/* ---- row f2 by infection location: the step's new infections attributed to the networks they came through ---------
+ * A pure addition to ABI 7.  Run AFTER a step, with the step's own `params`, while plan->sets[s].cum still holds the
+ * step's per-venue sums cum_n[v] (column k of a set = its k-th network among the step's active networks, in the order
+ * of params->nets).  For an agent a with new_infected[a] == 1 and every active network n, in fp64:
+ *   t_n[a] = w_n[a] * susceptibility0[a] * sum over the edges (a, v) of n's edge set of cum_n[v]
+ * w_n the receiving-side recipe of gj_mask_kind: 1 (RAW), q[a] (Q), q[a] * L_n[day_type][class[a]] (QL), that times
+ * (age > 75) (QL_AGE75); q[a] = !has_quarantine || current_stage[a] < q_threshold.  This is what the reference's
+ * InfectionNetwork.forward returns per network (infection_networks/base.py:61-84); T = sum_n t_n (in the order of
+ * nets) is the pre-clamp trans_susc.  T finite and > 0: network n gets the share t_n / T of the infection.  Otherwise
+ * the whole infection goes to `background_col`: the reference's probability floor (clamp(ts, 1e-6, ...), base.py:136)
+ * infects agents nobody transmitted to.  A term that is NaN or negative counts as 0 and sets GJ_LOC_ERR_VALUE.
+ * Shares are 64-bit integers in units of 1 / GJ_LOC_UNIT of an infection: c_n = floor(t_n / T * GJ_LOC_UNIT), the
+ * remainder GJ_LOC_UNIT - sum c_n goes to the network with the largest t_n (lowest index on a tie), so every infection
+ * adds exactly GJ_LOC_UNIT and out[g][.] sums to GJ_LOC_UNIT * (new infections of group g); no order of the agents, no
+ * grid and no regime changes a bit.
+ *   out[group[a]][cols[n]] += c_n          out: device int64 [n_groups][n_cols]; the call ADDS to it.
+ * rows[s] (s < plan->n_sets): the set's edges as CSR by OWNED agent - a_rowptr device int32 [n_agents + 1], a_venue
+ * device int32 [n_edges], venue ids in the set's own numbering - supplied by the caller because gj_edge_set's CSR arrays
+ * are NULL on the tiled layout (a CSR plan may pass those).  a_rowptr == NULL: the set contributes nothing.
+ * cols: HOST int32 [params->n_nets], the output column of active network i; several networks may share a column.
+ * group: device int32 [n_agents] or NULL (n_groups must be 1).  current_stage: NULL iff !has_quarantine.
+ * n_nets == 0 is valid: every infection goes to background_col (the seeding step).  n_agents == 0 launches nothing.
+ * Bad input never reaches a bin: a label outside [0, n_groups) is skipped (never an index) and sets GJ_LOC_ERR_LABEL; a
+ * new_infected that is neither 0 nor 1 is skipped and sets GJ_LOC_ERR_VALUE; a row pointer or venue id outside the set
+ * is skipped and sets GJ_LOC_ERR_ROWS.  *err (device uint32) is sticky until the caller clears it.
+ * One launch.  A lane reads new_infected for its agents (4 B per agent, coalesced, a workgroup takes a contiguous
+ * share); a wave ballots 256 agents and hands the flagged ones to its four groups of 16 lanes, four agents at a time:
+ * a group walks its agent's rows set by set with its lanes striding over the edges (8 B of row pointers per set, 4 B
+ * per edge, the set's nk floats of cum per edge, at cache-line granularity), reduces in fp64 over the group - lane i
+ * holds t_i - and adds the shares: into an LDS histogram when n_groups * n_cols <= GJ_LOC_LDS_BINS, flushed with one
+ * 64-bit atomic per non-zero bin, else with global 64-bit atomics.  At most GJ_LOC_BLOCKS workgroups of 256.
+ * Errors, returned before any device work: GJ_E_NULL for a NULL plan, params, rows (n_sets > 0), new_infected,
+ * susceptibility0, out, err, cols (n_nets > 0), a NULL current_stage with has_quarantine, a_rowptr without a_venue;
+ * GJ_E_RANGE for n_nets outside 0..GJ_MAX_NETS, n_groups outside 1..GJ_MAX_GROUPS, group == NULL with n_groups != 1,
+ * n_cols outside 1..GJ_LOC_MAX_COLS, cols[i] or background_col outside [0, n_cols); and what gj_step returns for a
+ * bad plan or bad networks.                                                                                          */
+#define GJ_LOC_UNIT ((int64_t)1 << 30)
+#define GJ_LOC_ERR_LABEL 1u
+#define GJ_LOC_ERR_VALUE 2u
+#define GJ_LOC_ERR_ROWS 4u
+#define GJ_LOC_MAX_COLS 64
+#define GJ_LOC_LDS_BINS 4096
+#define GJ_LOC_BLOCKS 2048
+typedef struct gj_location_rows {
+  const int32_t* a_rowptr;  /* device [n_agents+1] or NULL: no rows, the set contributes nothing */
+  const int32_t* a_venue;   /* device [n_edges]                                                   */
+} gj_location_rows;
+int gj_location_stats(const gj_plan* plan, const gj_step_params* params, const gj_location_rows* rows /* [plan->n_sets] */,
+                      const float* new_infected, const float* susceptibility0, const float* current_stage,
+                      const int32_t* group, int32_t n_groups, const int32_t* cols /* host [n_nets] */, int32_t n_cols,
+                      int32_t background_col, int64_t* out, uint32_t* err, void* stream);
+
 /* ---- row f3: adjoint (backward) of one hot-path step, forward-only kernels reused ---------------
  * The aggregation ts = susc * sum_n w_n * (M_n^T diag(beta_n p_contact) M_n)(m_n * transmission) is
  * self-adjoint up to the exchange of the masks m_n <-> w_n, so its backward is the same four tiled
