@@ -287,6 +287,169 @@ __global__ __launch_bounds__(kThreads) void k_adjoint_seed_finish(const SeedSumA
   if (lane == 0) S.out[g] = acc;
 }
 
+// Vaccination (include/gradjune_hip.h, gj_vaccinate / gj_adjoint_vaccinate): streaming, per agent.  A campaign's uniform
+// of an agent is infection_uniform(seed, stream, global id) - word (id & 3) of the block (id >> 2, stream) - so a lane
+// that holds the four agents of an aligned quad of global ids computes ONE block (vaccine_uniforms4); a lane that holds
+// one agent calls infection_uniform itself.  The per-age tables arrive by value and are staged in LDS, where a lane's
+// age indexes them (300 floats; from the kernel arguments a per-lane index would go through scratch).
+// ONE definition of the rule, shared by the update and its adjoint (which must take the update's decision).
+__device__ __forceinline__ bool vaccine_newly(float u, float lo, float hi) { return lo <= u && u < hi; }
+
+constexpr int kVaccineAges = 100, kVaccineTable = 3 * kVaccineAges;
+static_assert(sizeof(gj_vaccinate_tables) == kVaccineTable * sizeof(float), "gj_vaccinate_tables: three packed tables");
+
+// tab = thr_lo | thr_hi | factor; ends with a barrier
+__device__ __forceinline__ void vaccine_stage_tables(const gj_vaccinate_tables& T, float* tab) {
+  const float* src = reinterpret_cast<const float*>(&T);
+  for (int i = threadIdx.x; i < kVaccineTable; i += blockDim.x) tab[i] = src[i];
+  __syncthreads();
+}
+// one agent's decision and the factor its susceptibility is multiplied by (1 where it is not newly vaccinated)
+__device__ __forceinline__ bool vaccine_agent(const float* tab, int cls, float u, float& factor) {
+  const int age = cls % kVaccineAges;
+  const bool nw = vaccine_newly(u, tab[age], tab[kVaccineAges + age]);
+  factor = nw ? tab[2 * kVaccineAges + age] : 1.0f;
+  return nw;
+}
+// the uniforms of the global ids g0 .. g0 + 3, g0 a multiple of 4: infection_uniform's, from one block
+__device__ __forceinline__ void vaccine_uniforms4(uint64_t seed, uint64_t stream, int64_t g0, float (&u)[4]) {
+  uint32_t r[4];
+  philox4x32_10((uint64_t)g0 >> 2, stream, seed, r);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) u[j] = u01(r[j]);
+}
+
+struct VaccinateArgs {
+  gj_vaccinate_tables T;
+  int64_t n;
+  const uint8_t* cls;
+  uint64_t seed, stream;
+  int64_t agent_offset;
+  float* susc;
+  float* newly;                // [n] or NULL
+  unsigned long long* count;   // [1] or NULL
+  int32_t vec4;                // agent_offset % 4 == 0 and susc, newly 16-byte, cls 4-byte aligned
+};
+
+// Workgroups of 1024 lanes, at most 512 of them (the shape of k_group_stats' LDS form: the same waves per CU as 2048
+// workgroups of 256), because every workgroup with a count ends in one atomic on ONE address, and those serialise: with
+// 2048 workgroups the launch that moves 1 % of 10 M agents took 34 us, of which the atomics were 20.
+constexpr int kVaccineThreads = 1024, kVaccineBlocks = 512;
+
+__global__ __launch_bounds__(kVaccineThreads) void k_vaccinate(const VaccinateArgs S) {
+  __shared__ float tab[kVaccineTable];
+  __shared__ uint32_t part[kVaccineThreads / kWave];
+  vaccine_stage_tables(S.T, tab);
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  uint32_t cnt = 0;            // (a lane meets n / (lanes of the grid) agents: far below 2^32)
+  int64_t first_scalar = 0;
+  if (S.vec4) {
+    const int64_t n4 = S.n >> 2;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+      // both loads issued before the Philox rounds
+      const uint32_t cl = reinterpret_cast<const uint32_t*>(S.cls)[i];
+      float4 s = reinterpret_cast<const float4*>(S.susc)[i];
+      float u[4], f0, f1, f2, f3;
+      vaccine_uniforms4(S.seed, S.stream, S.agent_offset + 4 * i, u);
+      const bool n0 = vaccine_agent(tab, (int)(cl & 0xFF), u[0], f0);
+      const bool n1 = vaccine_agent(tab, (int)((cl >> 8) & 0xFF), u[1], f1);
+      const bool n2 = vaccine_agent(tab, (int)((cl >> 16) & 0xFF), u[2], f2);
+      const bool n3 = vaccine_agent(tab, (int)(cl >> 24), u[3], f3);
+      if (n0 || n1 || n2 || n3) {      // most steps move few agents: the array is read, not rewritten
+        if (n0) s.x *= f0;
+        if (n1) s.y *= f1;
+        if (n2) s.z *= f2;
+        if (n3) s.w *= f3;
+        reinterpret_cast<float4*>(S.susc)[i] = s;
+      }
+      if (S.newly)
+        reinterpret_cast<float4*>(S.newly)[i] =
+            make_float4(n0 ? 1.0f : 0.0f, n1 ? 1.0f : 0.0f, n2 ? 1.0f : 0.0f, n3 ? 1.0f : 0.0f);
+      cnt += (uint32_t)n0 + (uint32_t)n1 + (uint32_t)n2 + (uint32_t)n3;
+    }
+    first_scalar = n4 << 2;
+  }
+  for (int64_t a = first_scalar + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; a < S.n; a += stride) {
+    float f;
+    const bool nw = vaccine_agent(tab, (int)S.cls[a], infection_uniform(S.seed, S.stream, S.agent_offset + a), f);
+    if (nw) S.susc[a] = S.susc[a] * f;
+    if (S.newly) S.newly[a] = nw ? 1.0f : 0.0f;
+    cnt += (uint32_t)nw;
+  }
+  // the workgroup's count: a wave sum, the waves' sums through LDS, one integer atomic where it is not zero
+  cnt = wave_sum(cnt);
+  if (threadIdx.x % kWave == 0) part[threadIdx.x / kWave] = cnt;
+  __syncthreads();
+  if (threadIdx.x == 0 && S.count) {
+    unsigned long long v = 0;
+    for (int w = 0; w < kVaccineThreads / kWave; ++w) v += part[w];
+    if (v) atomicAdd(S.count, v);
+  }
+}
+
+// The adjoint's per-agent launch: g_in and the term of d loss / d efficacy[band] into the workspace that the seed's two
+// summing kernels (k_adjoint_seed_chunks, k_adjoint_seed_finish) then reduce in the order of the band's gj_seed_plan.
+struct VaccinateAdjArgs {
+  gj_vaccinate_tables T;
+  int64_t n;
+  const uint8_t* cls;
+  uint64_t seed, stream;
+  int64_t agent_offset;
+  const float* susc0;
+  const float* g_out;          // [n] or NULL (zeros)
+  const int32_t* band;         // [n]
+  int32_t n_bands;
+  int32_t vec4;                // agent_offset % 4 == 0 and every array given 16-byte (cls: 4-byte) aligned
+  double* contrib;             // [n]
+  float* g_in;                 // [n] or NULL
+};
+
+// susceptibility' = susceptibility0 * factor, factor = 1 - efficacy[band] where newly: d / d efficacy = -susceptibility0.
+// The product of two fp32 values is exact in fp64.  A label outside [0, n_bands) is no band: no term, never an index.
+__device__ __forceinline__ void vaccine_adjoint_agent(const float* tab, int cls, float u, float s0, float g, int32_t band,
+                                                      int32_t n_bands, double& c, float& gi) {
+  float f;
+  const bool nw = vaccine_agent(tab, cls, u, f);
+  gi = g * f;
+  c = (nw && (uint32_t)band < (uint32_t)n_bands) ? -((double)g * (double)s0) : 0.0;
+}
+
+__global__ __launch_bounds__(kThreads) void k_adjoint_vaccinate_agents(const VaccinateAdjArgs S) {
+  __shared__ float tab[kVaccineTable];
+  vaccine_stage_tables(S.T, tab);
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  int64_t first_scalar = 0;
+  if (S.vec4) {
+    const int64_t n4 = S.n >> 2;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+      const uint32_t cl = reinterpret_cast<const uint32_t*>(S.cls)[i];
+      const float4 s = reinterpret_cast<const float4*>(S.susc0)[i];
+      const float4 g = S.g_out ? reinterpret_cast<const float4*>(S.g_out)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+      const int4 b = reinterpret_cast<const int4*>(S.band)[i];
+      float u[4];
+      vaccine_uniforms4(S.seed, S.stream, S.agent_offset + 4 * i, u);
+      double c0, c1, c2, c3;
+      float4 gi;
+      vaccine_adjoint_agent(tab, (int)(cl & 0xFF), u[0], s.x, g.x, b.x, S.n_bands, c0, gi.x);
+      vaccine_adjoint_agent(tab, (int)((cl >> 8) & 0xFF), u[1], s.y, g.y, b.y, S.n_bands, c1, gi.y);
+      vaccine_adjoint_agent(tab, (int)((cl >> 16) & 0xFF), u[2], s.z, g.z, b.z, S.n_bands, c2, gi.z);
+      vaccine_adjoint_agent(tab, (int)(cl >> 24), u[3], s.w, g.w, b.w, S.n_bands, c3, gi.w);
+      reinterpret_cast<double2*>(S.contrib)[2 * i] = make_double2(c0, c1);
+      reinterpret_cast<double2*>(S.contrib)[2 * i + 1] = make_double2(c2, c3);
+      if (S.g_in) reinterpret_cast<float4*>(S.g_in)[i] = gi;
+    }
+    first_scalar = n4 << 2;
+  }
+  for (int64_t a = first_scalar + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; a < S.n; a += stride) {
+    double c;
+    float gi;
+    vaccine_adjoint_agent(tab, (int)S.cls[a], infection_uniform(S.seed, S.stream, S.agent_offset + a), S.susc0[a],
+                          S.g_out ? S.g_out[a] : 0.0f, S.band[a], S.n_bands, c, gi);
+    S.contrib[a] = c;
+    if (S.g_in) S.g_in[a] = gi;
+  }
+}
+
 // psi(x) = d lgamma / dx (torch.digamma, the derivative torch's autograd gives lgamma), for the adjoint of the profile's
 // 1 / Gamma(shape).  x < 0: reflection psi(x) = psi(1 - x) - pi / tan(pi x), NaN at the poles; x == 0: -inf (torch:
 // copysign(inf, -x)).  x > 0: the recurrence psi(x) = psi(x + 1) - 1/x up to x >= 6, then the asymptotic series to

@@ -1304,23 +1304,17 @@ int gj_adjoint_sample(int64_t n, const float* susceptibility0, const float* infe
                     g_new, x_out, grad_susc_out, grad_time_out);
 }
 
-int gj_adjoint_seed(int64_t n, const float* p_not_by_group, const int32_t* group, int32_t n_groups,
-                    const gj_seed_plan* plan, const float* susceptibility0, const float* infection_time0,
-                    const float* exp_noise, uint64_t seed, uint64_t step, int64_t agent_offset, float now,
-                    const float* g_susc, const float* g_inf, const float* g_time, const float* g_new,
-                    double* contrib_workspace, double* partial_workspace, double* grad_fraction, float* grad_susc_out,
-                    float* grad_time_out, void* stream) {
-  if (n < 0 || n_groups < 1 || n_groups > GJ_MAX_GROUPS) return GJ_E_RANGE;
-  if (!group && n_groups != 1) return GJ_E_RANGE;
-  if (!grad_fraction) return GJ_E_NULL;
-  gj::SeedSumArgs R;
+namespace gj {
+// The fp64 sums of gj_adjoint_seed and gj_adjoint_vaccinate: their arguments from the labelling's gj_seed_plan (checked
+// here; `plan` NULL: no labels, one group of all n agents, cut into chunks in index order) and their two launches.
+static int seed_sum_args(const gj_seed_plan* plan, int64_t n, int32_t n_groups, double* contrib, double* partial,
+                         double* out, SeedSumArgs& R) {
   R.n = n;
   R.n_groups = n_groups;
-  R.contrib = contrib_workspace;
-  R.partial = partial_workspace;
-  R.out = grad_fraction;
-  if (group) {
-    if (!plan) return GJ_E_NULL;
+  R.contrib = contrib;
+  R.partial = partial;
+  R.out = out;
+  if (plan) {
     if (plan->n_sorted < 0 || plan->n_sorted > n || plan->n_chunks < 0 ||
         plan->n_chunks > plan->n_sorted / GJ_SEED_CHUNK + n_groups)
       return GJ_E_RANGE;
@@ -1340,13 +1334,38 @@ int gj_adjoint_seed(int64_t n, const float* p_not_by_group, const int32_t* group
     R.chunk_first = nullptr;
     R.chunk_group = nullptr;
   }
-  constexpr int kWaves = gj::kThreads / gj::kWave;
+  if (grid_for(R.n_chunks, 0, kThreads / kWave) > 0x7fffffff) return GJ_E_RANGE;
+  if (n > 0 && !contrib) return GJ_E_NULL;
+  if (R.n_chunks > 0 && !partial) return GJ_E_NULL;
+  return GJ_OK;
+}
+static int seed_sum_launch(const SeedSumArgs& R, hipStream_t stream) {
+  constexpr int kWaves = kThreads / kWave;      // one wave per chunk, then one per group
+  if (R.n_chunks > 0) {
+    const int rc = launch(k_adjoint_seed_chunks, grid_for(R.n_chunks, 0, kWaves), kThreads, 0, stream, R);
+    if (rc) return rc;
+  }
+  return launch(k_adjoint_seed_finish, grid_for(R.n_groups, 0, kWaves), kThreads, 0, stream, R);
+}
+}  // namespace gj
+
+int gj_adjoint_seed(int64_t n, const float* p_not_by_group, const int32_t* group, int32_t n_groups,
+                    const gj_seed_plan* plan, const float* susceptibility0, const float* infection_time0,
+                    const float* exp_noise, uint64_t seed, uint64_t step, int64_t agent_offset, float now,
+                    const float* g_susc, const float* g_inf, const float* g_time, const float* g_new,
+                    double* contrib_workspace, double* partial_workspace, double* grad_fraction, float* grad_susc_out,
+                    float* grad_time_out, void* stream) {
+  if (n < 0 || n_groups < 1 || n_groups > GJ_MAX_GROUPS) return GJ_E_RANGE;
+  if (!group && n_groups != 1) return GJ_E_RANGE;
+  if (!grad_fraction) return GJ_E_NULL;
+  if (group && !plan) return GJ_E_NULL;
+  gj::SeedSumArgs R;
+  if (const int rc = gj::seed_sum_args(group ? plan : nullptr, n, n_groups, contrib_workspace, partial_workspace,
+                                       grad_fraction, R))
+    return rc;
   const int64_t agent_blocks = gj::grid_for(n);
-  const int64_t chunk_blocks = gj::grid_for(R.n_chunks, 0, kWaves);      // one wave per chunk, per group
-  const int64_t group_blocks = gj::grid_for(n_groups, 0, kWaves);
-  if (agent_blocks > 0x7fffffff || chunk_blocks > 0x7fffffff) return GJ_E_RANGE;
-  if (n > 0 && (!p_not_by_group || !susceptibility0 || !infection_time0 || !contrib_workspace)) return GJ_E_NULL;
-  if (R.n_chunks > 0 && !partial_workspace) return GJ_E_NULL;
+  if (agent_blocks > 0x7fffffff) return GJ_E_RANGE;
+  if (n > 0 && (!p_not_by_group || !susceptibility0 || !infection_time0)) return GJ_E_NULL;
   if (n > 0) {
     gj::SeedAdjArgs A;
     A.n = n;
@@ -1370,11 +1389,62 @@ int gj_adjoint_seed(int64_t n, const float* p_not_by_group, const int32_t* group
     const int rc = gj::launch(gj::k_adjoint_seed_agents, agent_blocks, gj::kThreads, 0, (hipStream_t)stream, A);
     if (rc) return rc;
   }
-  if (R.n_chunks > 0) {
-    const int rc = gj::launch(gj::k_adjoint_seed_chunks, chunk_blocks, gj::kThreads, 0, (hipStream_t)stream, R);
+  return gj::seed_sum_launch(R, (hipStream_t)stream);
+}
+
+// vaccination: the tables are copied into the launch's arguments (the caller's struct may change after the call returns)
+int gj_vaccinate(int64_t n, const uint8_t* agent_class, const gj_vaccinate_tables* tables, uint64_t seed,
+                 uint64_t stream, int64_t agent_offset, float* susceptibility, float* newly_out, int64_t* count_out,
+                 void* hip_stream) {
+  if (n < 0 || agent_offset < 0) return GJ_E_RANGE;
+  if (n == 0) return GJ_OK;
+  if (!agent_class || !tables || !susceptibility) return GJ_E_NULL;
+  gj::VaccinateArgs A;
+  A.T = *tables;
+  A.n = n;
+  A.cls = agent_class;
+  A.seed = seed;
+  A.stream = stream;
+  A.agent_offset = agent_offset;
+  A.susc = susceptibility;
+  A.newly = newly_out;
+  A.count = reinterpret_cast<unsigned long long*>(count_out);
+  A.vec4 = (agent_offset % 4 == 0 && gj::aligned16(susceptibility, newly_out) && (uintptr_t)agent_class % 4 == 0) ? 1 : 0;
+  return gj::launch(gj::k_vaccinate, gj::grid_for(gj::vec4_lanes(n, A.vec4), gj::kVaccineBlocks, gj::kVaccineThreads),
+                    gj::kVaccineThreads, 0, (hipStream_t)hip_stream, A);
+}
+
+int gj_adjoint_vaccinate(int64_t n, const uint8_t* agent_class, const gj_vaccinate_tables* tables, uint64_t seed,
+                         uint64_t stream, int64_t agent_offset, const float* susceptibility0, const float* g_out,
+                         const int32_t* band, int32_t n_bands, const gj_seed_plan* plan, double* contrib_workspace,
+                         double* partial_workspace, double* grad_efficacy, float* g_in, void* hip_stream) {
+  if (n < 0 || agent_offset < 0 || n_bands < 1 || n_bands > GJ_MAX_GROUPS) return GJ_E_RANGE;
+  if (!grad_efficacy || !plan) return GJ_E_NULL;
+  gj::SeedSumArgs R;
+  if (const int rc = gj::seed_sum_args(plan, n, n_bands, contrib_workspace, partial_workspace, grad_efficacy, R))
+    return rc;
+  if (n > 0) {
+    if (!agent_class || !tables || !susceptibility0 || !band) return GJ_E_NULL;
+    gj::VaccinateAdjArgs A;
+    A.T = *tables;
+    A.n = n;
+    A.cls = agent_class;
+    A.seed = seed;
+    A.stream = stream;
+    A.agent_offset = agent_offset;
+    A.susc0 = susceptibility0;
+    A.g_out = g_out;
+    A.band = band;
+    A.n_bands = n_bands;
+    A.vec4 = (agent_offset % 4 == 0 && gj::aligned16(susceptibility0, g_out, g_in) && gj::aligned16(band) &&
+              gj::aligned16(contrib_workspace) && (uintptr_t)agent_class % 4 == 0) ? 1 : 0;
+    A.contrib = contrib_workspace;
+    A.g_in = g_in;
+    const int rc = gj::launch(gj::k_adjoint_vaccinate_agents, gj::grid_for(gj::vec4_lanes(n, A.vec4), 2048),
+                              gj::kThreads, 0, (hipStream_t)hip_stream, A);
     if (rc) return rc;
   }
-  return gj::launch(gj::k_adjoint_seed_finish, group_blocks, gj::kThreads, 0, (hipStream_t)stream, R);
+  return gj::seed_sum_launch(R, (hipStream_t)hip_stream);
 }
 
 int gj_adjoint_transmission(int64_t n, const gj_agent_state* st, float now, const float* trans_bar,

@@ -213,6 +213,14 @@ class SeedPlan(C.Structure):
     ]
 
 
+class VaccinateTables(C.Structure):
+    _fields_ = [
+        ("thr_lo", C.c_float * 100),
+        ("thr_hi", C.c_float * 100),
+        ("factor", C.c_float * 100),
+    ]
+
+
 #: every symbol include/gradjune_hip.h declares: (restype, argtypes)
 SYMBOLS = {
     "gj_version": (C.c_int, []),
@@ -241,6 +249,15 @@ SYMBOLS = {
         C.c_int,
         [C.c_int64, _vp, _vp, C.c_int32, C.POINTER(SeedPlan), _vp, _vp, _vp, C.c_uint64, C.c_uint64, C.c_int64,
          C.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    ),
+    "gj_vaccinate": (
+        C.c_int,
+        [C.c_int64, _vp, C.POINTER(VaccinateTables), C.c_uint64, C.c_uint64, C.c_int64, _vp, _vp, _vp, _vp],
+    ),
+    "gj_adjoint_vaccinate": (
+        C.c_int,
+        [C.c_int64, _vp, C.POINTER(VaccinateTables), C.c_uint64, C.c_uint64, C.c_int64, _vp, _vp, _vp, C.c_int32,
+         C.POINTER(SeedPlan), _vp, _vp, _vp, _vp, _vp],
     ),
     "gj_adjoint_beta_partial": (
         C.c_int,

@@ -523,6 +523,49 @@ class SeedByGroup(torch.autograd.Function):
                 *_to_devices((grad_s, grad_i, grad_t), ctx.devices))
 
 
+class VaccinationStep(torch.autograd.Function):
+    """One launch of a vaccination campaign as an autograd node (``policies.VaccinationPolicies.apply``): (efficacy [B],
+    susceptibility) -> susceptibility'.  Forward = ``gj_vaccinate`` on a fresh tensor; backward =
+    ``gj_adjoint_vaccinate``, which sums d loss / d efficacy per band in fp64 in the order of the bands' ``SeedPlan``.
+    ``env``: the launch's decision inputs (agent classes, per-age tables, seed, stream, agent_offset), the optional
+    outputs ``newly`` / ``count``, ``band`` (int32 per agent) with its ``plan`` and - on a rank of a partitioned world -
+    ``all_reduce``, the sum over the ranks that makes every rank's gradient the whole world's (as ``SeedByGroup``)."""
+
+    @staticmethod
+    def forward(ctx, env, efficacy, susc):
+        dev = env["cls"].device
+        susc0 = _f32(susc, dev)
+        out = susc0.clone()
+        N.check(N.load().gj_vaccinate(out.numel(), N.ptr(env["cls"]), env["tables"], env["seed"], env["stream"],
+                                      env["agent_offset"], N.ptr(out), N.ptr(env["newly"]), N.ptr(env["count"]),
+                                      N.current_stream()), "gj_vaccinate")
+        ctx.env = {k: env[k] for k in ("cls", "tables", "seed", "stream", "agent_offset", "band", "plan", "all_reduce")}
+        ctx.like = (efficacy.device, efficacy.dtype, efficacy.shape)
+        ctx.susc_device = susc.device
+        ctx.save_for_backward(susc0)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        env = ctx.env
+        (susc0,) = ctx.saved_tensors
+        plan, dev, n = env["plan"], susc0.device, susc0.numel()
+        g_out = _f32(g_out, dev)
+        contrib = torch.empty(max(1, n), dtype=torch.float64, device=dev)
+        partial = torch.empty(max(1, plan.n_chunks), dtype=torch.float64, device=dev)
+        grad = torch.empty(plan.n_groups, dtype=torch.float64, device=dev)
+        g_in = torch.empty(n, dtype=torch.float32, device=dev) if ctx.needs_input_grad[2] else None
+        N.check(N.load().gj_adjoint_vaccinate(n, N.ptr(env["cls"]), env["tables"], env["seed"], env["stream"],
+                                              env["agent_offset"], N.ptr(susc0), N.ptr(g_out), N.ptr(env["band"]),
+                                              plan.n_groups, C.byref(plan.c), N.ptr(contrib), N.ptr(partial),
+                                              N.ptr(grad), N.ptr(g_in), N.current_stream()), "gj_adjoint_vaccinate")
+        if env.get("all_reduce") is not None:
+            grad = env["all_reduce"](grad)                     # fp64: the world's gradient on every rank
+        like_dev, like_dtype, like_shape = ctx.like
+        grad_eff = grad.to(device=like_dev, dtype=like_dtype).reshape(like_shape) if ctx.needs_input_grad[1] else None
+        return None, grad_eff, (None if g_in is None else g_in.to(ctx.susc_device))
+
+
 class SymptomsStep(torch.autograd.Function):
     """(new_infected, current_stage, next_stage, time_to_next_stage) -> the three updated arrays, with the
     reference's gradient paths (symptoms.py:98,105-124,231-236): a loss on the stages - the deaths series of

@@ -94,7 +94,12 @@ class DistributedGradJune(GradJune):
         data["agent"].transmission = hp.state["transmission"][: hp.rw.n_local]
         return out
 
-    # what GradJune.hot_path does differently on a rank -----------------------------------------------------------
+    # what GradJune.forward / hot_path do differently on a rank ---------------------------------------------------
+    def _vaccination_env(self):
+        """The campaigns' uniforms are keyed by the GLOBAL agent id, so the ranks decide as one GPU does; d loss / d
+        efficacy is a sum over agents: the ranks' [B] partial sums are added over the forward's process group."""
+        return self._hp.a0, self._hp.all_reduce_sum
+
     def _engine(self, data, device):
         return self._hp.engine
 
@@ -202,8 +207,11 @@ class DistributedRunner(Runner):
             return
         # (the series by agent group too: the labels were encoded on the whole world before the partition cut it, so the
         # columns are the same on every rank; the symptom-stage counts are int64 and go the same way)
+        # (the vaccination doses too: every rank counted its own agents' - int64 by campaign, fp64 by group)
+        vaccine = getattr(self, "_vaccine_series", None)
         for series in [self._series, *getattr(self, "_group_series", {}).values(),
-                       *getattr(self, "_stage_series", {}).values()]:
+                       *getattr(self, "_stage_series", {}).values(), *([vaccine] if vaccine is not None else []),
+                       *getattr(self, "_vaccine_group_series", {}).values()]:
             if dist.get_backend(self.group) == "gloo":            # tests: staged through the host
                 host = series[:n_rows].cpu()
                 dist.all_reduce(host, group=self.group)

@@ -285,6 +285,8 @@ class InfectionNetworks(torch.nn.Module):
         return [self.networks[a] for a in order]
 
     def forward(self, data, timer, policies):
-        """Per-agent probability of NOT being infected in this step (reference base.py:118-141)."""
+        """Per-agent probability of NOT being infected in this step (reference base.py:118-141).  Reads the
+        susceptibility as it is: this stand-alone call does not vaccinate (``Policies.vaccinate`` is ``GradJune.forward``'s
+        first act); call it yourself first if ``policies`` holds a ``Vaccination``."""
         return _run_networks(self.active_networks(timer, policies), data, timer, policies, self.device,
                              want="probs", all_networks=list(self.networks.values()))

@@ -159,7 +159,22 @@ class GradJune(torch.nn.Module):
             stats.add(plan, step["params"], nu, step["s0"], step["stage"], active=step["active"],
                       background="background", row=sink["row"], edges=edges)
 
+    def _vaccination_env(self):
+        """(global id of local agent 0, sum over the ranks of the efficacy's gradient or None): a rank of a partitioned
+        world overrides it (distributed_api.DistributedGradJune)."""
+        return 0, None
+
     def forward(self, data, timer, exp_noise=None):
+        # vaccination first: it moves the susceptibility the step starts from, and hot_path decides whether the step is
+        # differentiable from susceptibility.requires_grad before it applies the other policies.  The first call of a
+        # Runner's time loop comes after next(timer): agents a campaign already covers at the initial date are
+        # vaccinated in that first step, after the seeding.  Without a Vaccination policy nothing is launched
+        campaigns = getattr(self.policies, "vaccination_policies", None)
+        if campaigns is not None and len(campaigns.policies):
+            if self.rng_seed is None:
+                self.rng_seed = torch.initial_seed() & 0xFFFFFFFFFFFFFFFF
+            agent_offset, all_reduce = self._vaccination_env()
+            self.policies.vaccinate(data, timer, seed=self.rng_seed, agent_offset=agent_offset, all_reduce=all_reduce)
         new_infected, _ = self.hot_path(data, timer, exp_noise=exp_noise)
         # location_stats: set by the Runner for the duration of its time loop, like step_stats - the step's new
         # infections are attributed to the networks BEFORE the symptoms update, while current_stage is still the stage

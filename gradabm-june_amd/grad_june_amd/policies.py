@@ -7,6 +7,9 @@ arguments, YAML schema and ``apply`` signatures.  What reaches the kernels per s
                          the product over active policies is ``stage < min(thresholds)``, so the
                          kernels take one threshold (+inf when no policy is active)
   * CloseVenue        -> networks dropped from the step's list     (close_venue_policies.py:11-22)
+Not in the reference:
+  * Vaccination       -> ``susceptibility[a] *= 1 - efficacy[band]`` for the agents a campaign's age-banded rollout
+                         reaches in the step (``gj_vaccinate``); differentiable in the efficacy
 """
 from __future__ import annotations
 
@@ -131,13 +134,192 @@ class CloseVenuePolicies(PolicyCollection):
         return edge_types
 
 
+# ---- vaccination (not in the reference) --------------------------------------------------------
+#: Philox stream of campaign c: bit 61 set, c below (bits 62 and 63 and the 1 << 40 counter are the steps' and symptoms')
+VACCINE_STREAM = 1 << 61
+N_AGES = 100
+
+
+def _plain_number(v, what):
+    """A YAML number or a tensor without a gradient as a Python double; one that requires a gradient is refused."""
+    if isinstance(v, torch.Tensor):
+        if v.requires_grad:
+            raise NotImplementedError(f"{what}: gradients w.r.t. the vaccination coverage are not implemented "
+                                      "(pass plain numbers; the efficacy is the differentiable input)")
+        return float(v.detach())
+    return float(v)
+
+
+def _age_band(key):
+    lo, hi = (int(x) for x in str(key).split("-"))
+    if not 0 <= lo < hi:
+        raise ValueError(f"age band '{key}': expected 'lo-hi' with 0 <= lo < hi")
+    return lo, hi
+
+
+class Vaccination(Policy):
+    """One campaign: between ``start_date`` and ``end_date`` the share ``coverage[age] * ramp(date)`` of every age is
+    vaccinated, and an agent's vaccination multiplies its susceptibility by ``1 - efficacy[band of its age]``, once and
+    for good (the effect persists after ``end_date``).
+
+    ``coverage``: a number (every age) or ``{"lo-hi": fraction}`` (``parse_age_probabilities``: lo <= age < hi, gaps 0);
+    kept as 100 Python doubles; not differentiable.  ``efficacy``: a number (one band, every age) or ``{"lo-hi":
+    value}``: ``self.efficacy`` is a float32 tensor [B], one value per band in file order, and ``band_of_age`` maps an
+    age to its band (-1: none, efficacy 0).  ``self.efficacy`` may be replaced by an ``nn.Parameter`` of the same shape:
+    a loss on the results then leaves ``d loss / d efficacy`` in its ``.grad``.
+
+    Who is vaccinated when is decided without per-agent state: campaign ``c`` (its index in ``VaccinationPolicies``)
+    gives agent ``a`` one uniform ``u`` for the whole run, and the campaign has reached the agent by ``date`` iff
+    ``u < coverage[age] * ramp(date)``.  ``applied`` is the ramp applied so far in this run (``reset`` zeroes it)."""
+
+    spec = "vaccination"
+
+    def __init__(self, start_date, end_date, coverage, efficacy, device="cpu"):
+        super().__init__(start_date, end_date, device)
+        if self.end_date < self.start_date:
+            raise ValueError(f"vaccination: end_date {self.end_date:%Y-%m-%d} before start_date {self.start_date:%Y-%m-%d}")
+        from .utils import parse_age_probabilities
+
+        if isinstance(coverage, dict):
+            for key in coverage:
+                _age_band(key)
+            self.coverage = [float(v) for v in parse_age_probabilities(
+                {str(k): _plain_number(v, f"coverage['{k}']") for k, v in coverage.items()})]
+        else:
+            self.coverage = [_plain_number(coverage, "coverage")] * N_AGES
+        if isinstance(efficacy, dict):
+            bands = [_age_band(k) for k in efficacy]
+            by_lo = sorted(bands)
+            for (_, hi), (lo, _) in zip(by_lo, by_lo[1:]):
+                if lo < hi:
+                    raise ValueError(f"vaccination: overlapping efficacy bands ({sorted(map(str, efficacy))})")
+            values = list(efficacy.values())
+            self.band_of_age = [int(b) for b in parse_age_probabilities(
+                {str(k): i for i, k in enumerate(efficacy)}, fill_value=-1)]
+        else:
+            values, self.band_of_age = [efficacy], [0] * N_AGES
+        if any(isinstance(v, torch.Tensor) and v.requires_grad for v in values):
+            self.efficacy = torch.stack([torch.as_tensor(v, dtype=torch.float32).reshape(()) for v in values])
+        else:
+            self.efficacy = torch.tensor([float(v) for v in values], dtype=torch.float32)
+        self.applied = 0.0
+        self._bands = None
+
+    def reset(self):
+        self.applied = 0.0
+
+    def ramp(self, date) -> float:
+        """clamp((date - start) / (end - start), 0, 1) in Python doubles; 1 from ``end_date`` on (also when the window
+        is empty: everybody the campaign covers is vaccinated at once)."""
+        if date >= self.end_date:
+            return 1.0
+        if date <= self.start_date:
+            return 0.0
+        return ((date - self.start_date).total_seconds() / (self.end_date - self.start_date).total_seconds())
+
+    def tables(self, lo: float, hi: float):
+        """The launch's per-age tables (``gj_vaccinate_tables``), each value rounded once: thresholds fp32(fp64(coverage)
+        * ramp) for the ramps ``lo`` and ``hi``, factors fp32(1 - fp64(efficacy of the age's band)), 1 without a band."""
+        from . import _native as N
+
+        eff = [float(v) for v in self.efficacy.detach().to(torch.float32).cpu().tolist()]
+        if len(eff) != max(self.band_of_age) + 1:
+            raise ValueError(f"vaccination: efficacy of shape {tuple(self.efficacy.shape)}, expected "
+                             f"[{max(self.band_of_age) + 1}] (one value per band)")
+        t = N.VaccinateTables()
+        for age in range(N_AGES):
+            t.thr_lo[age] = self.coverage[age] * lo          # (ctypes rounds the double to fp32: once)
+            t.thr_hi[age] = self.coverage[age] * hi
+            b = self.band_of_age[age]
+            t.factor[age] = 1.0 - eff[b] if b >= 0 else 1.0
+        return t
+
+    def bands(self, ages: torch.Tensor):
+        """(int32 band per agent on the agents' device, its ``groups.SeedPlan``): what the adjoint sums through; built
+        once per world."""
+        if self._bands is None or self._bands[0].numel() != ages.numel() or self._bands[0].device != ages.device:
+            from .groups import SeedPlan
+
+            table = torch.tensor(self.band_of_age, dtype=torch.int32, device=ages.device)
+            band = table[ages.long().clamp(0, N_AGES - 1)].contiguous()
+            self._bands = (band, SeedPlan(band, max(self.band_of_age) + 1, device=ages.device))
+        return self._bands
+
+
+class VaccinationPolicies(PolicyCollection):
+    """The campaigns, in list order: a campaign's index is its Philox stream.  ``apply`` launches ``gj_vaccinate`` once
+    for every campaign whose ramp rose since it was last applied (``lo`` = the ramp applied, ``hi`` = the ramp now); with
+    none rising nothing is launched and nothing is allocated.  ``doses``: device int64 [C], the doses given so far in
+    this run by campaign (None before the first launch); ``on_newly``: set by the Runner for its time loop - called with
+    every launch's 0 / 1 mask of the newly vaccinated (without it the mask is not written)."""
+
+    def __init__(self, policies):
+        super().__init__(policies)
+        self.doses = None
+        self.on_newly = None
+        self._cls = None
+
+    def reset(self):
+        for policy in self.policies:
+            policy.reset()
+        if self.doses is not None:
+            self.doses.zero_()
+
+    def requires_grad(self) -> bool:
+        return any(isinstance(p.efficacy, torch.Tensor) and p.efficacy.requires_grad for p in self.policies)
+
+    def _agent_class(self, ag, device):
+        n = ag["age"].numel()
+        if self._cls is None or self._cls.numel() != n or self._cls.device != device:
+            sex = ag["sex"] if "sex" in ag else torch.zeros_like(ag["age"])
+            self._cls = (sex.to(device).long() * 100 + ag["age"].to(device).long()).to(torch.uint8).contiguous()
+        return self._cls
+
+    def apply(self, data, timer, seed, agent_offset=0, all_reduce=None):
+        from . import _native as N
+        from .world import require_hip
+
+        for c, policy in enumerate(self.policies):
+            lo, hi = policy.applied, policy.ramp(timer.date)
+            if not hi > lo:
+                continue
+            policy.applied = hi
+            ag = data["agent"]
+            susc = ag["susceptibility"]
+            dev = require_hip(susc.device)
+            n = susc.numel()
+            cls = self._agent_class(ag, dev)
+            if self.doses is None or self.doses.device != dev:
+                self.doses = torch.zeros(len(self.policies), dtype=torch.int64, device=dev)
+            newly = torch.empty(n, dtype=torch.float32, device=dev) if self.on_newly is not None else None
+            env = {"cls": cls, "tables": policy.tables(lo, hi), "seed": int(seed) & 0xFFFFFFFFFFFFFFFF,
+                   "stream": VACCINE_STREAM | c, "agent_offset": int(agent_offset), "newly": newly,
+                   "count": self.doses[c:c + 1], "all_reduce": all_reduce}
+            eff = policy.efficacy
+            if torch.is_grad_enabled() and (eff.requires_grad or susc.requires_grad):
+                from .autograd import VaccinationStep
+
+                env["band"], env["plan"] = policy.bands(ag["age"].to(dev))
+                ag["susceptibility"] = VaccinationStep.apply(env, eff, susc)
+            else:
+                if susc.dtype != torch.float32 or not susc.is_contiguous() or susc.requires_grad:
+                    susc = ag["susceptibility"] = susc.detach().to(torch.float32).contiguous()
+                N.check(N.load().gj_vaccinate(n, N.ptr(cls), env["tables"], env["seed"], env["stream"],
+                                              env["agent_offset"], N.ptr(susc), N.ptr(newly), N.ptr(env["count"]),
+                                              N.current_stream()), "gj_vaccinate")
+            if newly is not None:
+                self.on_newly(c, newly)
+
+
 # ---- container ---------------------------------------------------------------------------------
 class Policies(torch.nn.Module):
-    def __init__(self, interaction_policies=None, quarantine_policies=None, close_venue_policies=None):
+    def __init__(self, interaction_policies=None, quarantine_policies=None, close_venue_policies=None,
+                 vaccination_policies=None):
         super().__init__()
         self.interaction_policies = interaction_policies
         self.quarantine_policies = quarantine_policies
         self.close_venue_policies = close_venue_policies
+        self.vaccination_policies = vaccination_policies
 
     @classmethod
     def from_policy_list(cls, policies):
@@ -150,6 +332,7 @@ class Policies(torch.nn.Module):
             interaction_policies=InteractionPolicies(of("interaction")),
             quarantine_policies=QuarantinePolicies(of("quarantine")),
             close_venue_policies=CloseVenuePolicies(of("close_venue")),
+            vaccination_policies=VaccinationPolicies(of("vaccination")),
         )
 
     @classmethod
@@ -189,3 +372,20 @@ class Policies(torch.nn.Module):
             self.quarantine_policies.apply(
                 timer=timer, symptom_stages=data["agent"]["symptoms"]["current_stage"]
             )
+
+    def reset(self):
+        """Forget what a run applied (the vaccination ramps and dose counts): ``Runner.forward`` calls it next to
+        ``timer.reset()``."""
+        if self.vaccination_policies is not None:
+            self.vaccination_policies.reset()
+
+    def vaccinate(self, data, timer, seed, agent_offset=0, all_reduce=None):
+        """Move ``data["agent"].susceptibility`` for every campaign whose ramp rose since it was last applied
+        (``VaccinationPolicies.apply``).  ``seed``: the run's Philox key; ``agent_offset``: the global id of local agent
+        0 and ``all_reduce``: the sum over the ranks of the efficacy's gradient, on a rank of a partitioned world.
+        ``GradJune.forward`` calls it BEFORE the hot path, which decides whether the step is differentiable from
+        ``susceptibility.requires_grad``.  Without a ``Vaccination`` policy: nothing."""
+        vp = self.vaccination_policies
+        if vp is None or len(vp.policies) == 0:
+            return
+        vp.apply(data, timer, seed, agent_offset=agent_offset, all_reduce=all_reduce)

@@ -363,10 +363,24 @@ class Runner(torch.nn.Module):
                       edges=self.model.location_edges(self.data, engine.plan))
         self._seed_new_infected = None
 
+    # vaccination series: the launches' own counts, and one gj_group_stats pass per labelling on a launch's mask ----------
+    def _campaigns(self):
+        """The model's ``policies.VaccinationPolicies``, or None without a ``Vaccination`` policy (nothing is recorded)."""
+        vp = getattr(self.model.policies, "vaccination_policies", None)
+        return vp if vp is not None and len(vp.policies) else None
+
+    def _record_newly(self, campaign, newly):
+        """``VaccinationPolicies.on_newly``: this launch's newly vaccinated, added by group to the current row (the
+        cases half of gj_group_stats' output; no stage equals the ``dead`` given, so the other half stays zero)."""
+        for name, stats in self._groups().items():
+            stats.add(newly, newly, 2, self._vaccine_group_series[name][self._vaccine_row])
+
     # time loop --------------------------------------------------------------------------------------
     def forward(self):
         timer, model, data = self.timer, self.model, self.data
         timer.reset()
+        if hasattr(model.policies, "reset"):      # what a run applied: the vaccination ramps and dose counts
+            model.policies.reset()
         self.restore_initial_data()
         self.set_initial_cases()
         n_bins = len(self.age_bins) - 1
@@ -379,13 +393,14 @@ class Runner(torch.nn.Module):
         else:
             n_rows = 4096
         self._series = torch.zeros(n_rows, 2 + n_bins, dtype=torch.float64, device=require_hip(self.device))
-        # differentiable run (a log_beta is an nn.Parameter, a profile tensor or the seed requires a gradient, grad mode on):
-        # the case series must stay on the autograd graph, so they are formed with tensor ops instead of the fused
-        # reduction kernel
+        # differentiable run (a log_beta is an nn.Parameter, a profile tensor, the seed or a vaccination efficacy requires
+        # a gradient, grad mode on): the case series must stay on the autograd graph, so they are formed with tensor ops
+        # instead of the fused reduction kernel
+        campaigns = self._campaigns()
         differentiable = torch.is_grad_enabled() and (any(
             isinstance(n.log_beta, torch.Tensor) and n.log_beta.requires_grad
             for n in model.infection_networks.networks.values()) or profile_requires_grad(data)
-            or self._seed_requires_grad())
+            or self._seed_requires_grad() or (campaigns is not None and campaigns.requires_grad()))
         diff_rows = []
         groups = self._groups()
         self._group_series = {name: torch.zeros(n_rows, 2 * st.n_groups, dtype=torch.float64,
@@ -406,6 +421,18 @@ class Runner(torch.nn.Module):
             st.reset(n_rows)
         if locations:
             self._record_seed_locations(locations)
+        # vaccination series (not in the reference), whenever the model has a Vaccination policy: the doses given so far,
+        # by campaign (the launches' own counts) and by every labelling (gj_group_stats on a launch's mask of the newly
+        # vaccinated).  Integer counts, so a by-group row sums to the national row exactly; row 0 is zero; no gradient
+        self._vaccine_series, self._vaccine_group_series = None, {}
+        if campaigns is not None:
+            if "campaign" in groups:
+                raise ValueError("a labelling named 'campaign' would shadow the result key vaccine_doses_by_campaign")
+            self._vaccine_series = torch.zeros(n_rows, len(campaigns.policies), dtype=torch.int64,
+                                               device=require_hip(self.device))
+            self._vaccine_group_series = {name: torch.zeros(n_rows, 2 * st.n_groups, dtype=torch.float64,
+                                                            device=require_hip(self.device))
+                                          for name, st in groups.items()}
 
         def record(row, done=False):
             if not done:
@@ -435,11 +462,20 @@ class Runner(torch.nn.Module):
             model.step_stats = sink
             if locations:
                 model.location_stats = {"stats": list(locations.values()), "row": row}
+            if campaigns is not None:      # cumulative: a row starts from the one before it
+                for series in self._vaccine_group_series.values():
+                    series[row].copy_(series[row - 1])
+                self._vaccine_row = row
+                campaigns.on_newly = self._record_newly if groups else None
             try:
                 data = model(data, timer)
             finally:
                 model.step_stats = None
                 model.location_stats = None
+                if campaigns is not None:
+                    campaigns.on_newly = None
+            if campaigns is not None and campaigns.doses is not None:
+                self._vaccine_series[row].copy_(campaigns.doses)
             record(row, done=bool(sink and sink.get("done")))
             dates.append(timer.date)
         self._finalize_series(row + 1)
@@ -486,6 +522,12 @@ class Runner(torch.nn.Module):
                 results["infections_by_location"] = values[:, 0, :]
             else:
                 results[f"infections_by_location_by_{key}"] = values
+        if campaigns is not None:      # counts as float64: exact (float32 holds integers up to 2^24 only)
+            by_campaign = self._vaccine_series[: row + 1].to(torch.float64)
+            results["vaccine_doses_per_timestep"] = by_campaign.sum(1)
+            results["vaccine_doses_by_campaign"] = by_campaign
+            for name, st in groups.items():
+                results[f"vaccine_doses_by_{name}"] = self._vaccine_group_series[name][: row + 1, : st.n_groups].clone()
         is_infected = data["agent"].is_infected
         if "original_index" in data["agent"]:
             out = torch.empty_like(is_infected)
@@ -509,11 +551,17 @@ class Runner(torch.nn.Module):
         for key, series in results.items():
             if key != "dates" and series.dim() == 1:
                 df[key] = series.detach().cpu().numpy()
+        if "vaccine_doses_by_campaign" in results:      # [T, C]: one column per campaign, in the policies' order
+            by_campaign = results["vaccine_doses_by_campaign"].detach().cpu().numpy()
+            for c in range(by_campaign.shape[1]):
+                df[f"vaccine_doses_campaign_{c}"] = by_campaign[:, c]
         df.to_csv(self.save_path / "results.csv")
         for name, keys in self.group_keys.items():      # [T, G] series: long format, one file per labelling
             if f"cases_by_{name}" not in results:       # a labelling that is only seeded by has no series
                 continue
             saved = [c for st in self.stages_saved for c in (st, "new_" + st)]
+            if f"vaccine_doses_by_{name}" in results:
+                saved.append("vaccine_doses")
             cols = {c: results[f"{c}_by_{name}"].detach().cpu().numpy().reshape(-1)
                     for c in ("cases", "daily_cases", "deaths", *saved)}
             pd.DataFrame({"date": np.repeat(np.asarray(results["dates"], dtype=object), len(keys)),

@@ -626,6 +626,51 @@ int gj_adjoint_seed(int64_t n, const float* p_not_by_group, const int32_t* group
                     double* contrib_workspace, double* partial_workspace, double* grad_fraction, float* grad_susc_out,
                     float* grad_time_out, void* stream);
 
+/* ---- vaccination: an age-banded rollout that lowers susceptibility, differentiable in the efficacy ----------------
+ * A pure addition to ABI 7 (not in the reference, whose policies never touch the susceptibility).  One campaign gives
+ * every agent ONE uniform for the whole run, u = infection_uniform(seed, stream, agent_offset + a) - the forward
+ * sampler's device function: word (id & 3) of the Philox block (id >> 2, stream), so a partitioned run decides as one
+ * GPU does; the caller keeps `stream` apart from the step streams (policies.py: bit 61 set, the campaign's index
+ * below).  A launch moves the agents of one slice of the rollout,
+ *   newly = thr_lo[age] <= u && u < thr_hi[age]                 (age = agent_class % 100)
+ *   susceptibility[a] *= factor[age]   where newly              (an fp32 multiply, in place; stored only where a lane's
+ *                                                                 agents changed)
+ * The three per-age tables are formed by the host, each value rounded once: a threshold is fp32(fp64(coverage[age]) *
+ * ramp) and a factor fp32(1 - fp64(efficacy of the age's band)).  The kernel only compares and multiplies, so a numpy
+ * restatement gives its bits (tests/gj_vaccination_ref.py).  Thresholds that rise from launch to launch make the
+ * rollout monotone without per-agent state: the slices [lo, hi) of a run tile [0, final).  A NaN threshold moves
+ * nobody.
+ * newly_out:  device fp32 [n], 0 / 1, or NULL.   count_out: device int64 [1], the launch ADDS its number of newly
+ * vaccinated agents (an integer atomic: exact in any order), or NULL.
+ * Where agent_offset is a multiple of 4 and the arrays are 16-byte (agent_class: 4-byte) aligned, a lane takes four
+ * consecutive agents, which share one Philox block; otherwise one agent per lane.  Both forms give the same bits.   */
+typedef struct gj_vaccinate_tables {
+  float thr_lo[100];           /* per age: the rollout reached u < thr_lo before this launch                    */
+  float thr_hi[100];           /* ... and reaches u < thr_hi with it                                            */
+  float factor[100];           /* per age: 1 - efficacy (1 for an age in no band)                               */
+} gj_vaccinate_tables;
+int gj_vaccinate(int64_t n, const uint8_t* agent_class, const gj_vaccinate_tables* tables /* host */, uint64_t seed,
+                 uint64_t stream, int64_t agent_offset, float* susceptibility, float* newly_out, int64_t* count_out,
+                 void* hip_stream);
+
+/* gj_adjoint_vaccinate: adjoint of gj_vaccinate w.r.t. the incoming susceptibility and the efficacy of each band.
+ * The decision inputs are the forward's and `newly` is the forward's rule (one shared device function);
+ * susceptibility0: the PRE-update values; g_out: the cotangent of the updated susceptibility (device fp32 [n], NULL =
+ * zeros); band: device int32 [n], each agent's efficacy band, or a label outside [0, n_bands) for none.
+ *   g_in[a]          = g_out[a] * (newly ? factor[age] : 1)                                   (fp32; g_in may be NULL)
+ *   grad_efficacy[b] = sum over agents with band[a] == b and newly of -g_out[a] * susceptibility0[a]
+ *                                                                              (device double [n_bands]; d factor = -d efficacy)
+ * The terms are formed in fp64 from the fp32 inputs (the products are exact) and summed without atomics in the order
+ * `plan` fixes - a gj_seed_plan built on `band` (groups.SeedPlan), read exactly as gj_adjoint_seed reads it, through
+ * the same two kernels - so two launches on the same inputs give the same bits.  An agent with no band contributes
+ * nothing and its label is never used as an index.  contrib_workspace: device double [n]; partial_workspace: device
+ * double [plan->n_chunks].                                                                                          */
+int gj_adjoint_vaccinate(int64_t n, const uint8_t* agent_class, const gj_vaccinate_tables* tables /* host */,
+                         uint64_t seed, uint64_t stream, int64_t agent_offset, const float* susceptibility0,
+                         const float* g_out, const int32_t* band, int32_t n_bands, const gj_seed_plan* plan,
+                         double* contrib_workspace, double* partial_workspace, double* grad_efficacy, float* g_in,
+                         void* hip_stream);
+
 /* d loss / d log_beta of the networks on ONE edge set, from the forward's and the transposed passes' per-venue sums:
  *   col0 + k :  ln(10) * scale * sum_v [p_contact[v] > 0]  cum_fwd[v][k] * cum_bwd[v][k] / (beta[k] * p_contact[v]) * weight[v]
  * (reference: autograd through base.py:36-42,78-83; `weights` - fp64 [n_venues] or NULL = 1 - is a rank's share of
