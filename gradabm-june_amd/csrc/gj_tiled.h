@@ -57,6 +57,25 @@ __device__ __forceinline__ fx_t to_fx(float x) {      // |x| <= fx_max<BITS>() (
   const double d = __builtin_fma((double)x, scale, magic);
   return (fx_t)(__double_as_longlong(d) - 0x4338000000000000LL);
 }
+// The same conversion with its two constants handed in by the caller (FxConsts::make, once per loop nest): the scale in
+// a scalar register pair, the magic number in a vector register pair, so that a term costs ONE v_fma_f64.  With the
+// constants written out as above hipcc rebuilds them in front of every term (a destructive v_fmac_f64 behind two
+// v_mov_b32) - two of the ten vector instructions per slot and network of multi_sums, which is bound by their issue.
+template <int BITS>
+struct FxConsts {
+  double scale, magic;
+  static __device__ __forceinline__ FxConsts make() {
+    FxConsts c = {(double)(1ull << BITS), 6755399441055744.0};
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+s"(c.scale));
+    asm volatile("" : "+v"(c.magic));
+#endif
+    return c;
+  }
+  __device__ __forceinline__ fx_t to_fx(float x) const {      // == gj::to_fx<BITS>(x), bit for bit
+    return (fx_t)(__double_as_longlong(__builtin_fma((double)x, scale, magic)) - 0x4338000000000000LL);
+  }
+};
 template <int BITS>
 __device__ __forceinline__ float from_fx(fx_t v) {
   return (float)((double)(long long)v * (1.0 / (double)(1ull << BITS)));
@@ -554,7 +573,8 @@ struct TSetB {
   int32_t direct;                          // pass 2 runs in phase D's direct form: phase C has nothing to do
   uint32_t term_limit;                     // bit pattern of the largest |term| a venue sum takes (<= 16384): chosen per set
                                            // so that the largest venue's sum cannot leave the 64 bits (fill_set_b)
-  int32_t _pad_b;
+  int32_t multinet;                        // phase B sums every network of a group in one pass (multi_sums): a leisure set with
+                                           // several active networks; its pass-1 weights are class-major (tiled_venues)
   // run form (gj_tiled_set.run_*): the primary edge of the agents [blk_r0[j], blk_r0[j+1]) - value x[a], venue pv_blk[a]
   const uint16_t* pv_blk;
   const int32_t* blk_r0;
@@ -584,14 +604,22 @@ __device__ __forceinline__ ClassWeights class_weights(const float* tables, int t
 }
 // [nk][200] weights of a set's networks (TSet: TSetB, TPSet or TDirect) for the transmitting and / or the receiving side
 // (template arguments: which are wanted) - THE place where `transpose` exchanges the two (backward pass).
+// by_class > 0: the transmitting side is written class-major instead, [200][by_class] with by_class >= nk a multiple of
+// 4 (class_pad) and zeros behind the networks - every network's weight of one class in one or two 16-byte LDS reads.
+__host__ __device__ __forceinline__ constexpr int class_pad(int nk) { return nk <= 4 ? 4 : 8; }
+static_assert(GJ_MAX_NETS_PER_SET <= 8, "class_pad: a class's weights are one or two float4");
 template <bool TRANSMITTING, bool RECEIVING, typename TSet>
 __device__ __forceinline__ void fill_class_weights(float* transmitting, float* receiving, const TSet& T, const float* tables,
-                                                   int day_type, int transpose, int tid) {
+                                                   int day_type, int transpose, int tid, int by_class = 0) {
   for (int i = tid; i < T.nk * 200; i += kTileThreads) {
     const int k = i / 200, c = i % 200;
     const ClassWeights w = class_weights(tables, T.table[k], T.age75[k], day_type, c);
-    if (TRANSMITTING) transmitting[i] = transpose ? w.lw : w.l;
+    if (TRANSMITTING) transmitting[by_class ? c * by_class + k : i] = transpose ? w.lw : w.l;
     if (RECEIVING) receiving[i] = transpose ? w.l : w.lw;
+  }
+  if (TRANSMITTING && by_class > T.nk) {
+    const int n_pad = by_class - T.nk;
+    for (int i = tid; i < n_pad * 200; i += kTileThreads) transmitting[(i / n_pad) * by_class + T.nk + i % n_pad] = 0.0f;
   }
 }
 
@@ -672,14 +700,17 @@ struct VenueItem {
   int g0, g1;               // its groups of 8 slots
   fx_t* sums;               // [nk][nv] fixed-point sums (phase B), then 64 scratch sums, one per lane of a wave
   float* cumf;              // cum of (k, lv) at float index 2 * (k * nv + lv): the low half of its sum's slot (phase C)
-  float* tabs;              // leisure: [nk][200] pass-1 weights, then [nk][200] pass-2 weights
+  int wpad;                 // 0, or the networks per class of the class-major pass-1 weights (T.multinet: class_pad(nk))
+  float* tabs;              // leisure: [nk][200] (or [200][wpad]) pass-1 weights, 16-byte aligned, then tabs2
+  float* tabs2;             // leisure: [nk][200] pass-2 weights
   uint32_t* vflags;         // two bits per sum (fx_flag)
   int vwords;
   int dummy;                // the lane's scratch sum: what does not count is added there
   __device__ __forceinline__ VenueItem(const TSetB& T_, int j, float* lds, int tid_)
       : T(T_), tid(tid_), nk(T_.nk), v0(T_.blk_v0[j]), nv(T_.blk_v0[j + 1] - v0), g0(T_.blk_e0[j] >> 3),
-        g1(T_.blk_e0[j + 1] >> 3), sums(reinterpret_cast<fx_t*>(lds)), cumf(lds), tabs(lds + 2 * ((size_t)nk * nv + 64)),
-        vflags(reinterpret_cast<uint32_t*>(tabs + (T_.leisure ? 2 * nk * 200 : 0))), vwords((nk * nv + 64 + 31) / 32),
+        g1(T_.blk_e0[j + 1] >> 3), sums(reinterpret_cast<fx_t*>(lds)), cumf(lds), wpad(T_.multinet ? class_pad(nk) : 0),
+        tabs(lds + 2 * (((size_t)nk * nv + 64 + 1) & ~(size_t)1)), tabs2(tabs + (T_.leisure ? (wpad ? wpad : nk) * 200 : 0)),
+        vflags(reinterpret_cast<uint32_t*>(tabs2 + (T_.leisure ? nk * 200 : 0))), vwords((nk * nv + 64 + 31) / 32),
         dummy(nk * nv + (tid_ & 63)) {}
   __device__ __forceinline__ const uint4* lv8() const { return reinterpret_cast<const uint4*>(T.e_lv); }
   __device__ __forceinline__ const uint2* cls8() const { return reinterpret_cast<const uint2*>(T.e_cls); }
@@ -735,6 +766,96 @@ __device__ __forceinline__ bool one_venue_sum(const VenueItem& W, const Group8& 
   return true;
 }
 
+// Phase B, one group of a set that carries several networks (T.multinet), every network in one pass.  What does not
+// depend on the network is done once: the eight local venues, the run structure (first / take: lane masks, held in
+// scalar registers), the range check, and the class weights - `tabs` is class-major ([200][wpad]), so one 16-byte LDS read
+// per slot brings the weights of four networks where run_sums after Group8::weighted reads 4 bytes per slot and network.
+// Per network there remain the products, the fixed-point conversions, the integer run merge - and an LDS atomic ONLY
+// where a run ends: the same integers to the same sums as run_sums adds, without its adds to the scratch sum (with runs
+// of ~10 slots, four atomics in five).  Such an item is bound by the LDS pipe, not by instruction issue, which is what
+// the branch per slot costs.
+// The range check is conservative and made once for all networks: rounding is monotonic, so no |w x| of the group
+// exceeds fl(max |x| * wmax), wmax the largest |weight| of the whole table (NaN if it holds one).  A group that fails
+// it - it holds a NaN, an infinity or a term near the window - goes through multi_group_slow, element by element as in
+// venue_group_slow: integer adds are exact, so a term inside the window adds the same to its sum on either path.
+__device__ __noinline__ void multi_group_slow(fx_t* sums, uint32_t* vflags, int words, uint32_t limit, int nv, int k0, int k1,
+                                              const float* tabs, int wpad, uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3,
+                                              uint32_t c0, uint32_t c1, float x0, float x1, float x2, float x3, float x4,
+                                              float x5, float x6, float x7) {
+  const Group8 G(make_uint4(w0, w1, w2, w3), make_uint2(c0, c1), make_float4(x0, x1, x2, x3), make_float4(x4, x5, x6, x7));
+  for (int k = k0; k < k1; ++k) {
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      if (G.lv(q) == 0xFFFF) continue;
+      const float x = tabs[G.cls(q) * wpad + k] * G.x(q);
+      if (abs_bits(x) <= limit) {
+        atomicAdd(&sums[k * nv + G.lv(q)], to_fx<kFxVenue>(x));
+      } else {
+        fx_flag(vflags, words, k * nv + G.lv(q), x);
+      }
+    }
+  }
+}
+// the largest |weight| of a class-major table as a float (a NaN if the table holds one), wave-uniform
+__device__ __forceinline__ float max_class_weight(const float* tabs, int n, int tid) {
+  uint32_t m = 0u;
+  for (int i = tid & (kWave - 1); i < n; i += kWave) m = max(m, abs_bits(tabs[i]));
+#pragma unroll
+  for (int off = kWave / 2; off > 0; off >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, off, kWave));
+  return __uint_as_float(__builtin_amdgcn_readfirstlane(m));
+}
+__device__ __forceinline__ void multi_sums(const VenueItem& W, const Group8& G, bool one_venue, const float* tabs, float wmax,
+                                           const FxConsts<kFxVenue> C, fx_t* sums, uint32_t* vflags) {
+  const uint32_t kLimit = W.T.term_limit;
+  const bool careful = !(abs_bits(__uint_as_float(max_abs_bits(G.v)) * wmax) <= kLimit);
+  // the wave-uniform run (one_venue_sum), decided by one ballot for all networks
+  const bool wave_run = one_venue && __builtin_amdgcn_ballot_w64(careful) == 0ull;
+  int lv[8];
+  bool first[8], take[8];
+#pragma unroll
+  for (int q = 0; q < 8; ++q) lv[q] = G.lv(q);
+#pragma unroll
+  for (int q = 0; q < 8; ++q) {
+    first[q] = (q == 0) || (lv[q] != lv[q - (q > 0)]);
+    take[q] = ((q == 7) || (lv[q + (q < 7)] != lv[q])) && lv[q] != 0xFFFF;
+  }
+  for (int k0 = 0; k0 < W.nk; k0 += 4) {
+    if (__builtin_expect(careful && !wave_run, 0)) {
+      multi_group_slow(sums, vflags, W.vwords, kLimit, W.nv, k0, min(k0 + 4, W.nk), tabs, W.wpad, G.w[0], G.w[1], G.w[2],
+                       G.w[3], G.c[0], G.c[1], G.x(0), G.x(1), G.x(2), G.x(3), G.x(4), G.x(5), G.x(6), G.x(7));
+      continue;
+    }
+    float4 w4[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) w4[q] = *reinterpret_cast<const float4*>(tabs + G.cls(q) * W.wpad + k0);
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) {
+      if (k0 + kk >= W.nk) break;      // (wave-uniform)
+      // (through a scalar register: as plain arithmetic hipcc strength-reduces the 8 x 4 sum addresses of a chunk into
+      // registers of their own across the k0 loop, and the launch spills)
+      const int base_k = __builtin_amdgcn_readfirstlane((k0 + kk) * W.nv);
+      float x[8];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) x[q] = (kk == 0 ? w4[q].x : kk == 1 ? w4[q].y : kk == 2 ? w4[q].z : w4[q].w) * G.x(q);
+      if (wave_run) {
+        fx_t s = 0;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) s += C.to_fx(x[q]);
+        s = wave_sum<fx_t>(s);
+        if ((W.tid & (kWave - 1)) == 0) atomicAdd(&sums[base_k + lv[0]], s);
+      } else {
+        fx_t s8 = 0;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+          const fx_t f = C.to_fx(x[q]);
+          s8 = first[q] ? f : s8 + f;
+          if (take[q]) atomicAdd(&sums[base_k + lv[q]], s8);
+        }
+      }
+    }
+  }
+}
+
 __device__ __forceinline__ void venue_zero(const VenueItem& W, fx_t* sums, uint32_t* vflags) {
   for (int i = W.tid; i < W.nk * W.nv + 64; i += kTileThreads) sums[i] = 0;
   for (int i = W.tid; i < 2 * W.vwords; i += kTileThreads) vflags[i] = 0u;
@@ -744,12 +865,16 @@ __device__ __forceinline__ void venue_zero(const VenueItem& W, fx_t* sums, uint3
 // registers and adds each run to the block's LDS sums; kVenueUnroll such groups are loaded before the first is used.
 __device__ __forceinline__ void venue_sums_tiled(const VenueItem& W, const float* weights, fx_t* sums, uint32_t* vflags) {
   const TSetB& T = W.T;
+  const float wmax = T.multinet ? max_class_weight(weights, 200 * W.wpad, W.tid) : 0.0f;
+  const FxConsts<kFxVenue> fxc = FxConsts<kFxVenue>::make();
   auto add_group = [&](const Group8& G) {
     // every lane of the wave, all of them active, holds eight slots of the same venue
     const bool mine = G.one_venue() && (G.lv(0) == __builtin_amdgcn_readfirstlane(G.lv(0)));
     const bool one_venue = __builtin_amdgcn_ballot_w64(mine) == ~0ull;
     if (!T.leisure) {
       if (!(one_venue && one_venue_sum(W, G, G.lv(0), sums))) run_sums(W, G, 0, sums, vflags);
+    } else if (T.multinet) {
+      multi_sums(W, G, one_venue, weights, wmax, fxc, sums, vflags);
     } else {
       for (int k = 0; k < W.nk; ++k) {
         const Group8 Gk = G.weighted(weights + k * 200);
@@ -921,7 +1046,7 @@ __global__ __launch_bounds__(kTileThreads, GJ_VENUE_WAVES_PER_SIMD) void k_tile_
   if (T.nk == 0) return;
   const VenueItem W(T, j, lds_s, threadIdx.x);
   // table set-up: pass-1 weights, then pass-2 weights (read behind the barriers below)
-  if (T.leisure) fill_class_weights<true, true>(W.tabs, W.tabs + W.nk * 200, T, B.tables, B.day_type, B.transpose, W.tid);
+  if (T.leisure) fill_class_weights<true, true>(W.tabs, W.tabs2, T, B.tables, B.day_type, B.transpose, W.tid, W.wpad);
   if (B.mode != 2) {
     venue_zero(W, W.sums, W.vflags);
     __syncthreads();                            // the sums are zero and the tables written before the first add
@@ -935,7 +1060,7 @@ __global__ __launch_bounds__(kTileThreads, GJ_VENUE_WAVES_PER_SIMD) void k_tile_
     venue_cum_read(W, W.cumf);
   }
   __syncthreads();                              // cumf is complete
-  venue_gather(W, W.tabs + W.nk * 200, W.cumf);
+  venue_gather(W, W.tabs2, W.cumf);
 }
 
 // ---- pass 1 in the "direct" form (sets with few venues whose edges all belong to owned agents) ----------------------

@@ -1018,8 +1018,14 @@ static int tiled_venues(const gj_plan* plan, const gj_agent_state* st, const gj_
       X.blk_r0 = S.run_blk_r0;
       X.n_x = plan->n_ext_agents;
     }
+    // Phase B of a set that carries several networks sums all of them in one pass per group of slots, with an LDS
+    // atomic only where a run of one venue ends (multi_sums; its pass-1 weights are class-major, padded to 4 or 8
+    // networks).  Decided here, per set and step, from the active networks alone: such an item is bound by the LDS
+    // pipe at any block or tile width.  A single-network set keeps run_sums - its items are bound by bytes.
+    X.multinet = X.leisure && X.nk >= 2;
     const size_t n_sums = (size_t)X.nk * S.max_block_venues + 64;               // + a scratch sum per lane of a wave
-    const size_t need = n_sums * sizeof(fx_t) + (X.leisure ? 2 * 200 * (size_t)X.nk : 0) * sizeof(float) +
+    const size_t weights = !X.leisure ? 0 : 200 * ((size_t)(X.multinet ? class_pad(X.nk) : X.nk) + (size_t)X.nk);
+    const size_t need = ((n_sums + 1) & ~(size_t)1) * sizeof(fx_t) + weights * sizeof(float) +   // (the weights 16-byte aligned)
                         2 * ((n_sums + 31) / 32 * 4);                                 // two flag bits per sum
     X.term_limit = venue_term_limit(S.max_venue_edges);
     if (X.nk && need > lds) lds = need;

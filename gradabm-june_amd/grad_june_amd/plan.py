@@ -35,6 +35,9 @@ from . import tiling as TL
 
 LONG_CHUNK = 8192        # edges per workgroup for venues above the stream capacity
 MAX_ROWS_PER_BLOCK = 2048
+WORK_NET_COST = 0.15     # work-list weight of a venue block: cost of a slot per further network of its set, relative to the
+                         # first (tools/venue_timeline.py on C3: a leisure block, three active networks, 51.4 us against
+                         # 40.0 for a school block of the same 131 072 slots)
 
 
 @dataclass
@@ -381,8 +384,14 @@ def compile_plan(n_agents: int, edge_sets: Dict[str, dict], age=None, sex=None,
                 n_presum += int(t.presum)
             blk_e0, blk_v0 = _host(t.blk_e0).astype(np.int64), _host(t.blk_v0).astype(np.int64)
             prim = np.diff(_host(t.runs.blk_r0).astype(np.int64)) if t.runs is not None else np.zeros(t.n_blocks, np.int64)
+            # The weight of a work item is its cost: its slots, heavier by WORK_NET_COST for every further network of the
+            # set (phase B sums a slot once per network), its venues (zeroing, cum write-out) and its primary edges.
+            # Without the networks the items that take longest after the one-network blocks of the first round - the
+            # leisure blocks - were dispatched fifth and ended the launch.  (GJ_WORK_NET_COST=0: that order, for A/Bs.)
+            net_cost = float(os.environ.get("GJ_WORK_NET_COST", WORK_NET_COST))
             for j in range(t.n_blocks):
-                work.append((int(blk_e0[j + 1] - blk_e0[j]) + int(blk_v0[j + 1] - blk_v0[j]) + int(prim[j]), sid, j))
+                work.append((int((blk_e0[j + 1] - blk_e0[j]) * (1.0 + net_cost * (k - 1))) + int(blk_v0[j + 1] - blk_v0[j])
+                             + int(prim[j]), sid, j))
         if progress:
             progress(f"compiled edge set {name}")
         if not want_csr:

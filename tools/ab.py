@@ -3,9 +3,10 @@
 and/or different bench.py arguments), back to back, sharing a world cache, and print one table.  Boxes differ by
 up to 10 % on the same binary, so variants are only comparable inside one invocation.
 
-    python tools/ab.py [--steps 30] [--rounds 2] label[:DEFINE=VAL,...][@bench args] ...
+    python tools/ab.py [--steps 30] [--rounds 2] label[:DEFINE=VAL,...][%ENV=VAL,...][@bench args] ...
 
-e.g.  python tools/ab.py base unroll8:GJ_UNROLL_NARROW=8 "nodirect@--direct off"
+e.g.  python tools/ab.py base unroll8:GJ_UNROLL_NARROW=8 "nodirect@--direct off" "light%GJ_WORK_ORDER=light"
+(%ENV=VAL: environment of that variant's bench.py run - what the host-side plan compile reads.)
 Variants are built here (hipcc cross-compiles without a GPU) by `--build-only`; on the GPU box the prebuilt
 libraries under gradabm-june_amd/grad_june_amd/lib/variants/ are used.
 """
@@ -28,8 +29,9 @@ def parse_variant(v):
     if "@" in v:
         v, rest = v.split("@", 1)
         bench_args = rest.split()
+    v, _, envs = v.partition("%")
     label, _, defs = v.partition(":")
-    return label, [d for d in defs.split(",") if d], bench_args
+    return label, [d for d in defs.split(",") if d], bench_args, dict(e.split("=", 1) for e in envs.split(",") if e)
 
 
 def lib_path(label):
@@ -60,7 +62,7 @@ def main():
     a = ap.parse_args()
     vs = [parse_variant(v) for v in a.variants]
     if a.build_only:
-        for label, defs, bargs in vs:
+        for label, defs, bargs, _ in vs:
             if defs or label == "base" or not bargs:
                 build(label, defs)
                 print("built", lib_path(label))
@@ -68,8 +70,8 @@ def main():
     rows = []
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     for rnd in range(a.rounds):
-        for label, defs, bargs in vs:
-            env = dict(os.environ, GJ_LIB_PATH=lib_of(label))
+        for label, defs, bargs, envs in vs:
+            env = dict(os.environ, GJ_LIB_PATH=lib_of(label), **envs)
             cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(a.steps), "--warmup", "5",
                    "--world-cache", "/tmp/gj_worlds", *a.common.split(), *bargs]
             r = subprocess.run(cmd, env=env, capture_output=True, text=True)
@@ -87,7 +89,7 @@ def main():
             print(f"[r{rnd}] {label:24s} {d['ms_per_step'] * 1e3:7.1f} us/step   {km}{full}   infected={row['checksum']['infected']:.0f}",
                   flush=True)
     print("\nbest of rounds:")
-    for label, _, _ in vs:
+    for label, _, _, _ in vs:
         mine = [r for r in rows if r["label"] == label]
         if mine:
             b = min(mine, key=lambda r: r["ms_per_step"])
