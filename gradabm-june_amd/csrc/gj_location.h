@@ -22,6 +22,71 @@ constexpr int kLocLoads = 4;                     // new_infected loads in flight
 constexpr int kLocGroup = 16;                    // lanes per newly infected agent; lane i of a group holds t_i
 static_assert(GJ_MAX_NETS <= kLocGroup && kWave % kLocGroup == 0 && GJ_LOC_UNIT == (1ll << 30), "gj_location_stats");
 
+// The loop the sparse per-agent kernels share (k_location_stats here, the three of gj_infector.h): a workgroup takes a
+// contiguous share of the n agents in rounds of kLocLoads * 64 agents per wave; a lane reads flag[] for its agents
+// (4 B per agent, coalesced), the wave ballots `flagged` over the round's 256 agents and hands the flagged ones to its
+// four groups of kLocGroup lanes, four agents at a time: take(on, a, flag[a]) runs in EVERY lane of the wave - the sums
+// of a group go through shuffles - with `on` false in a group that has no agent this time.
+// kDenseFrom > 0: a round with at least that many flagged agents is not handed to the groups; every lane takes its own
+// flagged agents, one after the other, with solo(a, flag[a]) - 64 agents side by side where the groups hold four.
+struct NoSolo {
+  __device__ void operator()(int64_t, float) const {}
+};
+template <int kDenseFrom = 0, typename Flagged, typename Take, typename Solo = NoSolo>
+__device__ __forceinline__ void for_flagged_agents(int64_t n, const float* __restrict__ flag, Flagged flagged, Take take,
+                                                   Solo solo = Solo()) {
+  const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave, waves = blockDim.x / kWave;
+  const int slot = lane / kLocGroup;
+  const int64_t round = (int64_t)kLocLoads * kWave;
+  int64_t per = (n + gridDim.x - 1) / gridDim.x;
+  per = (per + round - 1) / round * round;
+  const int64_t u0 = (int64_t)blockIdx.x * per, u1 = (u0 + per < n) ? u0 + per : n;
+  for (int64_t base = u0 + wave * round; base < u1; base += waves * round) {
+    float nu[kLocLoads];
+    unsigned long long m[kLocLoads], any = 0;
+#pragma unroll
+    for (int j = 0; j < kLocLoads; ++j) {
+      const int64_t i = base + j * kWave + lane;
+      nu[j] = i < u1 ? flag[i] : 0.0f;
+    }
+#pragma unroll
+    for (int j = 0; j < kLocLoads; ++j) any |= m[j] = __ballot(flagged(nu[j]));
+    if (kDenseFrom > 0) {
+      int count = 0;
+#pragma unroll
+      for (int j = 0; j < kLocLoads; ++j) count += __popcll(m[j]);
+      if (count >= kDenseFrom) {                       // (uniform over the wave)
+#pragma unroll
+        for (int j = 0; j < kLocLoads; ++j)
+          if (flagged(nu[j])) solo(base + j * kWave + lane, nu[j]);
+        continue;
+      }
+    }
+    while (any) {                                      // the round's flagged agents, one per group of lanes at a time
+      bool on = false;
+      int64_t a = 0;
+      float v = 0.0f;
+#pragma unroll
+      for (int p = 0; p < kWave / kLocGroup; ++p) {
+        bool found = false;
+#pragma unroll
+        for (int j = 0; j < kLocLoads; ++j) {
+          if (found || !m[j]) continue;
+          const int bit = __ffsll((long long)m[j]) - 1;
+          m[j] &= m[j] - 1;
+          found = true;
+          const float x = __shfl(nu[j], bit, kWave);
+          if (slot == p) on = true, a = base + j * kWave + bit, v = x;
+        }
+      }
+      any = 0;
+#pragma unroll
+      for (int j = 0; j < kLocLoads; ++j) any |= m[j];
+      take(on, a, v);
+    }
+  }
+}
+
 struct LocSet {                                  // one edge set with networks active in this step
   const int32_t* rowptr;                         // by-agent rows [n_agents + 1]; NULL: the set contributes nothing
   const int32_t* venue;                          // [n_edges], the set's own venue numbering
@@ -33,6 +98,54 @@ struct LocSet {                                  // one edge set with networks a
   int32_t mask[GJ_MAX_NETS_PER_SET];             // gj_mask_kind
   int32_t table[GJ_MAX_NETS_PER_SET];            // leisure table, -1: none
 };
+
+// w_n (receiving = true) or m_n (false) of gj_mask_kind for an agent of class c with quarantine factor q: 1 (RAW), q (Q),
+// q * L[day_type][c] (QL), and on the receiving side that times (age > 75) (QL_AGE75).
+__device__ __forceinline__ double mask_weight(int m, double q, int c, const float* tables, int table, int day_type,
+                                              bool receiving) {
+  double w = (m == GJ_MASK_RAW) ? 1.0 : q;
+  if (m >= GJ_MASK_QL) w = w * (c < 200 ? (double)tables[(int64_t)table * GJ_TABLE_SIZE + day_type * 200 + c] : 0.0);
+  if (receiving && m == GJ_MASK_QL_AGE75) w = w * (((c % 100) > 75) ? 1.0 : 0.0);
+  return w;
+}
+
+// t_n[a] = w_n[a] * s0[a] * sum over a's edges of cum_n[v] for the network n == sub of the calling lane (0 for
+// sub >= n_nets), by the group of kLocGroup lanes that holds agent a (`on` false: empty rows): the lanes stride over the
+// edges of every set's row, the sums go through the group's butterfly.  Set: LocSet or a struct derived from it.
+template <typename Set>
+__device__ __forceinline__ double network_term(const Set* sets, int n_sets, bool on, int64_t a, int sub, double s0, double q,
+                                               int c, const float* tables, int day_type, uint32_t& err) {
+  double t = 0.0;
+  for (int s = 0; s < n_sets; ++s) {
+    const Set& S = sets[s];
+    if (!S.rowptr) continue;                         // (uniform)
+    int32_t r0 = 0, r1 = 0;
+    if (on) {
+      r0 = S.rowptr[a], r1 = S.rowptr[a + 1];
+      if (r0 < 0 || r1 < r0 || r1 > S.n_edges) err |= kLocBadRows, r0 = r1 = 0;
+    }
+    double acc[GJ_MAX_NETS_PER_SET];
+#pragma unroll
+    for (int k = 0; k < GJ_MAX_NETS_PER_SET; ++k) acc[k] = 0.0;
+    for (int64_t e = (int64_t)r0 + sub; e < r1; e += kLocGroup) {   // the group's lanes stride over the agent's edges
+      const int32_t v = S.venue[e];
+      if ((uint32_t)v >= (uint32_t)S.n_venues) { err |= kLocBadRows; continue; }
+      const float* row = S.cum + (int64_t)v * S.stride;
+#pragma unroll
+      for (int k = 0; k < GJ_MAX_NETS_PER_SET; ++k)
+        if (k < S.nk) acc[k] += (double)row[k];
+    }
+#pragma unroll
+    for (int k = 0; k < GJ_MAX_NETS_PER_SET; ++k) {
+      if (k >= S.nk) continue;                       // (nk is uniform: whole waves skip)
+      const double sum = group_sum<kLocGroup>(acc[k]);
+      double tk = mask_weight(S.mask[k], q, c, tables, S.table[k], day_type, true) * s0 * sum;
+      if (!(tk >= 0.0)) { tk = 0.0; err |= kLocBadValue; }      // NaN or negative: counts as 0
+      if (sub == S.first + k) t = tk;
+    }
+  }
+  return t;
+}
 
 struct LocArgs {
   int64_t n;
@@ -61,8 +174,8 @@ __global__ __launch_bounds__(kThreads) void k_location_stats(const LocArgs A) {
     for (int i = threadIdx.x; i < bins; i += blockDim.x) loc_hist[i] = 0;
     __syncthreads();
   }
-  const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave, waves = blockDim.x / kWave;
-  const int sub = lane % kLocGroup, slot = lane / kLocGroup, first_lane = lane - sub;
+  const int lane = threadIdx.x % kWave;
+  const int sub = lane % kLocGroup, first_lane = lane - sub;
   uint32_t err = 0;
   int col = 0;                                         // the output column of this lane's network (sub < n_nets)
 #pragma unroll
@@ -89,40 +202,7 @@ __global__ __launch_bounds__(kThreads) void k_location_stats(const LocArgs A) {
       q = (!A.has_q || A.stage[a] < A.q_thr) ? 1.0 : 0.0;
       c = A.cls ? A.cls[a] : 0;
     }
-    double t = 0.0;                                    // t_n of the network n == sub
-    for (int s = 0; s < A.n_sets; ++s) {
-      const LocSet& S = A.sets[s];
-      if (!S.rowptr) continue;                         // (uniform)
-      int32_t r0 = 0, r1 = 0;
-      if (on) {
-        r0 = S.rowptr[a], r1 = S.rowptr[a + 1];
-        if (r0 < 0 || r1 < r0 || r1 > S.n_edges) err |= kLocBadRows, r0 = r1 = 0;
-      }
-      double acc[GJ_MAX_NETS_PER_SET];
-#pragma unroll
-      for (int k = 0; k < GJ_MAX_NETS_PER_SET; ++k) acc[k] = 0.0;
-      for (int64_t e = (int64_t)r0 + sub; e < r1; e += kLocGroup) {   // the group's lanes stride over the agent's edges
-        const int32_t v = S.venue[e];
-        if ((uint32_t)v >= (uint32_t)S.n_venues) { err |= kLocBadRows; continue; }
-        const float* row = S.cum + (int64_t)v * S.stride;
-#pragma unroll
-        for (int k = 0; k < GJ_MAX_NETS_PER_SET; ++k)
-          if (k < S.nk) acc[k] += (double)row[k];
-      }
-#pragma unroll
-      for (int k = 0; k < GJ_MAX_NETS_PER_SET; ++k) {
-        if (k >= S.nk) continue;                       // (nk is uniform: whole waves skip)
-        const double sum = group_sum<kLocGroup>(acc[k]);
-        const int m = S.mask[k];
-        double w = (m == GJ_MASK_RAW) ? 1.0 : q;       // the mask recipe of gj_mask_kind
-        if (m >= GJ_MASK_QL)
-          w = w * (c < 200 ? (double)A.tables[(int64_t)S.table[k] * GJ_TABLE_SIZE + A.day_type * 200 + c] : 0.0);
-        if (m == GJ_MASK_QL_AGE75) w = w * (((c % 100) > 75) ? 1.0 : 0.0);
-        double tk = w * s0 * sum;
-        if (!(tk >= 0.0)) { tk = 0.0; err |= kLocBadValue; }      // NaN or negative: counts as 0
-        if (sub == S.first + k) t = tk;
-      }
-    }
+    const double t = network_term(A.sets, A.n_sets, on, a, sub, s0, q, c, A.tables, A.day_type, err);   // t_n, n == sub
     double T = 0.0, t_best = 0.0;                      // T in the order of nets; the largest term, lowest index on a tie
     int best = 0;
     for (int i = 0; i < A.n_nets; ++i) {
@@ -142,44 +222,7 @@ __global__ __launch_bounds__(kThreads) void k_location_stats(const LocArgs A) {
       add(g, A.background, unit);                      // nobody transmitted: the reference's probability floor
     }
   };
-  // this workgroup's contiguous share of the agents, in rounds of kLocLoads * 64 agents per wave
-  const int64_t round = (int64_t)kLocLoads * kWave;
-  int64_t per = (A.n + gridDim.x - 1) / gridDim.x;
-  per = (per + round - 1) / round * round;
-  const int64_t u0 = (int64_t)blockIdx.x * per, u1 = (u0 + per < A.n) ? u0 + per : A.n;
-  for (int64_t base = u0 + wave * round; base < u1; base += waves * round) {
-    float nu[kLocLoads];
-    unsigned long long m[kLocLoads], any = 0;          // (NaN is flagged too, and refused in take)
-#pragma unroll
-    for (int j = 0; j < kLocLoads; ++j) {
-      const int64_t i = base + j * kWave + lane;
-      nu[j] = i < u1 ? A.nu[i] : 0.0f;
-    }
-#pragma unroll
-    for (int j = 0; j < kLocLoads; ++j) any |= m[j] = __ballot(nu[j] != 0.0f);
-    while (any) {                                      // the round's flagged agents, one per group of lanes at a time
-      bool on = false;
-      int64_t a = 0;
-      float v = 0.0f;
-#pragma unroll
-      for (int p = 0; p < kWave / kLocGroup; ++p) {
-        bool found = false;
-#pragma unroll
-        for (int j = 0; j < kLocLoads; ++j) {
-          if (found || !m[j]) continue;
-          const int bit = __ffsll((long long)m[j]) - 1;
-          m[j] &= m[j] - 1;
-          found = true;
-          const float x = __shfl(nu[j], bit, kWave);
-          if (slot == p) on = true, a = base + j * kWave + bit, v = x;
-        }
-      }
-      any = 0;
-#pragma unroll
-      for (int j = 0; j < kLocLoads; ++j) any |= m[j];
-      take(on, a, v);
-    }
-  }
+  for_flagged_agents(A.n, A.nu, [](float x) { return x != 0.0f; }, take);   // (NaN is flagged too, and refused in take)
   if (err) atomicOr(A.err, err);
   if (LDS) {
     __syncthreads();

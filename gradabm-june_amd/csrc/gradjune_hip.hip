@@ -20,6 +20,7 @@
 #include "gj_tiled.h"
 #include "gj_agent.h"
 #include "gj_location.h"
+#include "gj_infector.h"
 
 namespace gj {
 
@@ -1757,6 +1758,115 @@ int gj_location_stats(const gj_plan* plan, const gj_step_params* params, const g
     return gj::launch(gj::k_location_stats<true>, blocks, gj::kThreads, (size_t)bins * sizeof(unsigned long long),
                       (hipStream_t)stream, A);
   return gj::launch(gj::k_location_stats<false>, blocks, gj::kThreads, 0, (hipStream_t)stream, A);
+}
+
+// the sets of the step's networks as the infector kernels take them: the location kernel's, with p_contact, U and beta
+static int infector_sets(const gj_plan* plan, const gj_step_params* params, const gj_location_rows* rows,
+                         int64_t* const* U, gj::InfArgs* A) {
+  int rc = gj::check_plan(plan);
+  if (rc) return rc;
+  gj::Groups G;
+  rc = gj::group_networks(plan, params, &G);
+  if (rc) return rc;
+  if ((plan->n_sets > 0 && !rows) || (params->n_nets > 0 && !U)) return GJ_E_NULL;
+  for (int g = 0; g < G.n; ++g) {
+    const gj_edge_set& E = plan->sets[G.set[g]];
+    const gj_location_rows& R = rows[G.set[g]];
+    if (R.a_rowptr && !R.a_venue && E.n_edges > 0) return GJ_E_NULL;
+    if (R.a_rowptr && E.n_venues > 0 && !U[G.set[g]]) return GJ_E_NULL;
+    const gj::NetGroup C = gj::classify_group(params, G, g);
+    gj::InfSet& S = A->sets[g];
+    S.rowptr = R.a_rowptr;
+    S.venue = R.a_venue;
+    S.cum = E.cum;
+    S.n_edges = (int32_t)E.n_edges;
+    S.n_venues = (int32_t)E.n_venues;
+    S.stride = E.cum_stride;
+    S.nk = C.nk;
+    S.first = G.first[g];
+    memcpy(S.mask, C.mask, sizeof(S.mask));
+    memcpy(S.table, C.table, sizeof(S.table));
+    memcpy(S.beta, C.beta, sizeof(S.beta));
+    S.pc = E.v_pcontact;
+    S.U = (unsigned long long*)U[G.set[g]];
+  }
+  A->n = plan->n_agents;
+  A->cls = plan->agent_class;
+  A->tables = plan->tables;
+  A->n_nets = params->n_nets;
+  A->n_sets = G.n;
+  A->has_q = params->has_quarantine ? 1 : 0;
+  A->day_type = params->day_type;
+  A->q_thr = params->q_threshold;
+  return GJ_OK;
+}
+
+int gj_infector_scatter(const gj_plan* plan, const gj_step_params* params, const gj_location_rows* rows,
+                        const float* new_infected, const float* susceptibility0, const float* current_stage,
+                        int64_t* const* U, int64_t* unattributed, int32_t* cohort, int32_t cohort_value, uint32_t* err,
+                        void* stream) {
+  gj::InfArgs A = {};
+  if (const int rc = infector_sets(plan, params, rows, U, &A)) return rc;
+  if (!new_infected || !susceptibility0 || !unattributed || !err) return GJ_E_NULL;
+  if (params->has_quarantine && !current_stage) return GJ_E_NULL;
+  if (plan->n_agents == 0) return GJ_OK;
+  A.flag = new_infected;
+  A.s0 = susceptibility0;
+  A.stage = params->has_quarantine ? current_stage : nullptr;
+  A.unattributed = (unsigned long long*)unattributed;
+  A.cohort = cohort;
+  A.cohort_value = cohort_value;
+  A.err = err;
+  return gj::launch(gj::k_infector_scatter, gj::grid_for(A.n, gj::kLocBlocks, gj::kLocLoads * gj::kWave), gj::kThreads, 0,
+                    (hipStream_t)stream, A);
+}
+
+int gj_infector_gather(const gj_plan* plan, const gj_step_params* params, const gj_location_rows* rows,
+                       const float* transmission, const float* current_stage, int64_t* const* U, const int32_t* group,
+                       int32_t n_groups, double* caused, int64_t* out, uint32_t* err, void* stream) {
+  gj::InfArgs A = {};
+  if (const int rc = infector_sets(plan, params, rows, U, &A)) return rc;
+  if (!transmission || !err || (!caused && !out)) return GJ_E_NULL;
+  if (params->has_quarantine && !current_stage) return GJ_E_NULL;
+  if (n_groups < 1 || n_groups > GJ_MAX_GROUPS || (!group && n_groups != 1)) return GJ_E_RANGE;
+  if (plan->n_agents == 0 || params->n_nets == 0) return GJ_OK;
+  A.flag = transmission;
+  A.stage = params->has_quarantine ? current_stage : nullptr;
+  A.group = group;
+  A.n_groups = n_groups;
+  A.caused = caused;
+  A.out = (unsigned long long*)out;
+  A.err = err;
+  const int64_t blocks = gj::grid_for(A.n, gj::kLocBlocks, gj::kLocLoads * gj::kWave);
+  if (out && n_groups <= gj::kLocLdsBins)
+    return gj::launch(gj::k_infector_gather<true>, blocks, gj::kThreads, (size_t)n_groups * sizeof(unsigned long long),
+                      (hipStream_t)stream, A);
+  return gj::launch(gj::k_infector_gather<false>, blocks, gj::kThreads, 0, (hipStream_t)stream, A);
+}
+
+int gj_infector_clear(const gj_plan* plan, const gj_location_rows* rows, const float* new_infected, int64_t* const* U,
+                      void* stream) {
+  const int rc = gj::check_plan(plan);
+  if (rc) return rc;
+  if (!new_infected || (plan->n_sets > 0 && (!rows || !U))) return GJ_E_NULL;
+  gj::InfArgs A = {};
+  for (int s = 0; s < plan->n_sets; ++s) {
+    const gj_edge_set& E = plan->sets[s];
+    if (!rows[s].a_rowptr || !U[s] || E.n_venues == 0) continue;      // no rows or no U: nothing of this set to clear
+    if (!rows[s].a_venue && E.n_edges > 0) return GJ_E_NULL;
+    gj::InfSet& S = A.sets[A.n_sets++];
+    S.rowptr = rows[s].a_rowptr;
+    S.venue = rows[s].a_venue;
+    S.n_edges = (int32_t)E.n_edges;
+    S.n_venues = (int32_t)E.n_venues;
+    S.stride = E.cum_stride;
+    S.U = (unsigned long long*)U[s];
+  }
+  if (plan->n_agents == 0 || A.n_sets == 0) return GJ_OK;
+  A.n = plan->n_agents;
+  A.flag = new_infected;
+  return gj::launch(gj::k_infector_clear, gj::grid_for(A.n, gj::kLocBlocks, gj::kLocLoads * gj::kWave), gj::kThreads, 0,
+                    (hipStream_t)stream, A);
 }
 
 int gj_step(const gj_plan* plan, const gj_agent_state* state, const gj_step_params* params, const gj_step_io* io,

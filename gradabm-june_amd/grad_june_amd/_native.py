@@ -282,6 +282,17 @@ SYMBOLS = {
         [C.POINTER(Plan), C.POINTER(StepParams), C.POINTER(LocationRows), _vp, _vp, _vp, _vp, C.c_int32,
          C.POINTER(C.c_int32), C.c_int32, C.c_int32, _vp, _vp, _vp],
     ),
+    "gj_infector_scatter": (
+        C.c_int,
+        [C.POINTER(Plan), C.POINTER(StepParams), C.POINTER(LocationRows), _vp, _vp, _vp, C.POINTER(_vp), _vp, _vp,
+         C.c_int32, _vp, _vp],
+    ),
+    "gj_infector_gather": (
+        C.c_int,
+        [C.POINTER(Plan), C.POINTER(StepParams), C.POINTER(LocationRows), _vp, _vp, C.POINTER(_vp), _vp, C.c_int32, _vp,
+         _vp, _vp, _vp],
+    ),
+    "gj_infector_clear": (C.c_int, [C.POINTER(Plan), C.POINTER(LocationRows), _vp, C.POINTER(_vp), _vp]),
     "gj_step": (C.c_int, [C.POINTER(Plan), C.POINTER(AgentState), C.POINTER(StepParams), C.POINTER(StepIO), _vp]),
     "gj_step_phase": (
         C.c_int,

@@ -311,6 +311,8 @@ class HotPathStep(torch.autograd.Function):
         ctx.save_for_backward(susc.detach().to(torch.float32).contiguous(), inf.detach().to(torch.float32).contiguous(),
                               time.detach().to(torch.float32).contiguous())
         ctx.transmission = bufs.tensors["transmission"]
+        if env.get("keep_transmission") is not None:      # the infector series reads the step's transmissions after it
+            env["keep_transmission"]["transmission"] = ctx.transmission
         ctx.kept = (acc, _clone_forward_cum(plan, nets)) if keep else None      # (cum: complete after the all-reduce)
         return out_s, out_i, out_t, new_inf
 

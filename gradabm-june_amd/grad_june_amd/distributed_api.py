@@ -165,12 +165,15 @@ class DistributedGradJune(GradJune):
 class DistributedRunner(Runner):
     """``Runner`` for one rank; see the module docstring."""
 
-    _supports_locations = False      # the infection-location series needs every venue's sums and rows on one device
+    # the infection-location series needs every venue's sums and rows on one device; the infector series also an
+    # exchange of the credits of halo agents
+    _supports_locations = False
 
     @classmethod
     def from_parameters(cls, params, group=None, rank: Optional[int] = None, world_size: Optional[int] = None,
                         collectives: bool = True):
         cls._refuse_locations(params.get("locations_to_save"))
+        cls._refuse_infectors(params.get("infectors_to_save"))
         model = DistributedGradJune.from_parameters(params)
         full = Runner.get_data(params)                # the whole world, identical on every rank (same torch seed)
         n_total = len(full["agent"]["id"])

@@ -324,6 +324,149 @@ class LocationStats:
             raise LocationError(f"{what}: " + " and ".join(why))
 
 
+class InfectorError(RuntimeError):
+    """gj_infector_scatter / gj_infector_gather met a label outside [0, n_groups), a new_infected that is neither 0 nor
+    1, a NaN or negative term, a credit that is not finite, or a row outside its edge set."""
+
+
+def infectors_to_save(spec) -> bool:
+    """The YAML key ``infectors_to_save`` / the Runner's ``infectors=``: true or false (absent: false)."""
+    if spec is None:
+        return False
+    if isinstance(spec, (bool, np.bool_)):
+        return bool(spec)
+    raise ValueError(f"infectors_to_save: expected true or false, not {spec!r}")
+
+
+class InfectorStats:
+    """``gj_infector_scatter`` / ``gj_infector_gather`` for a world of ``n_agents`` and any number of labellings
+    (``labellings``: {name: (labels, n_groups)}; the national sums are kept under the key None).  Owns what the two passes
+    accumulate over a run: ``caused`` (fp64 [n]: the infections every agent caused), ``infected_row`` (int32 [n]: the row
+    an agent was infected in, -1: never), the integer series ``out[key]`` [rows, n_groups] - units of 1 / GJ_LOC_UNIT of
+    an infection, by the INFECTOR's group - and ``unattributed`` [rows] (exact counts), and the sticky error word.  ``U``,
+    the per-venue units of one step, lives with the plan (``DevicePlan.infector_units``) and is zero between steps:
+    ``clear`` = "memset" zeroes all of it, "walk" only the venues the step's new infections touched."""
+
+    def __init__(self, n_agents: int, labellings=None, device=None, n_rows: int = 1, clear: str = "memset"):
+        if clear not in ("memset", "walk"):
+            raise ValueError(f"clear = {clear!r}: 'memset' or 'walk'")
+        self.n, self.device, self.clear_by = int(n_agents), torch.device(device), clear
+        self.labels, self.n_groups = {None: None}, {None: 1}
+        for name, (labels, n_groups) in (labellings or {}).items():
+            if n_groups < 1 or n_groups > N.GJ_MAX_GROUPS:
+                raise ValueError(f"n_groups = {n_groups}: expected 1 .. {N.GJ_MAX_GROUPS}")
+            if labels.numel() != self.n:
+                raise ValueError(f"{self.n} agents for {labels.numel()} labels of '{name}'")
+            self.labels[name] = labels.detach().to(device=self.device, dtype=torch.int32).contiguous()
+            self.n_groups[name] = int(n_groups)
+        self.err = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self.reset(n_rows)
+
+    def reset(self, n_rows: int = 1) -> None:
+        dev = self.device
+        self.caused = torch.zeros(self.n, dtype=torch.float64, device=dev)
+        self.infected_row = torch.full((self.n,), -1, dtype=torch.int32, device=dev)
+        self.unattributed = torch.zeros(int(n_rows), dtype=torch.int64, device=dev)
+        self.out = {key: torch.zeros(int(n_rows), G, dtype=torch.int64, device=dev) for key, G in self.n_groups.items()}
+
+    def _agents(self, *per_agent) -> None:
+        for t in per_agent:
+            if t is not None and (t.numel() != self.n or t.dtype != torch.float32 or not t.is_contiguous()
+                                  or t.device != self.device):
+                raise ValueError(f"per-agent arguments: contiguous float32[{self.n}] on {self.device}")
+
+    def scatter(self, plan, params, new_infected, susceptibility0, current_stage, row: int = 0, edges=None,
+                cohort: bool = True) -> None:
+        """Pass 1 of the step ``params`` describes, into the plan's ``U`` (zero before); unattributed[row] += the
+        infections nobody transmitted; infected_row = row for the step's new infections (``cohort``)."""
+        import ctypes as C
+
+        if plan.host.n_agents != self.n:
+            raise ValueError(f"a plan of {plan.host.n_agents} agents for {self.n}")
+        self._agents(new_infected, susceptibility0, current_stage)
+        if not 0 <= row < self.unattributed.numel():
+            raise IndexError(f"row {row} of {self.unattributed.numel()}")
+        N.check(N.load().gj_infector_scatter(
+            C.byref(plan.c), C.byref(params), plan.location_rows(edges), N.ptr(new_infected), N.ptr(susceptibility0),
+            N.ptr(current_stage), plan.infector_units()[1], N.ptr(self.unattributed[row:]),
+            N.ptr(self.infected_row) if cohort else None, int(row), N.ptr(self.err), N.current_stream()),
+            "gj_infector_scatter")
+
+    def gather(self, plan, params, transmission, current_stage, row: int = 0, edges=None) -> None:
+        """Pass 2: caused += the step's credits (once), out[key][row] += their sums by group for every labelling."""
+        import ctypes as C
+
+        n_ext = plan.host.n_ext_agents      # (the step's transmission array: the owned agents come first)
+        if (transmission.numel() != n_ext or transmission.dtype != torch.float32 or not transmission.is_contiguous()
+                or transmission.device != self.device):
+            raise ValueError(f"transmission: contiguous float32[{n_ext}] on {self.device}")
+        self._agents(current_stage)
+        if not 0 <= row < self.unattributed.numel():
+            raise IndexError(f"row {row} of {self.unattributed.numel()}")
+        for key, G in self.n_groups.items():
+            N.check(N.load().gj_infector_gather(
+                C.byref(plan.c), C.byref(params), plan.location_rows(edges), N.ptr(transmission), N.ptr(current_stage),
+                plan.infector_units()[1], N.ptr(self.labels[key]), G, N.ptr(self.caused) if key is None else None,
+                N.ptr(self.out[key][row]), N.ptr(self.err), N.current_stream()), "gj_infector_gather")
+
+    def clear(self, plan, new_infected=None, edges=None) -> None:
+        """The plan's ``U`` back to zero: all of it, or (``clear`` = "walk") what the step of ``new_infected`` touched."""
+        import ctypes as C
+
+        U, pointers = plan.infector_units()
+        if self.clear_by == "walk" and new_infected is not None:
+            N.check(N.load().gj_infector_clear(C.byref(plan.c), plan.location_rows(edges), N.ptr(new_infected), pointers,
+                                               N.current_stream()), "gj_infector_clear")
+        else:
+            for u in U:
+                u.zero_()
+
+    def record(self, plan, params, new_infected, susceptibility0, current_stage, transmission, row: int = 0,
+               edges=None) -> None:
+        """One step: scatter, gather (a step with networks), clear."""
+        self.scatter(plan, params, new_infected, susceptibility0, current_stage, row=row, edges=edges)
+        if params.n_nets > 0:
+            self.gather(plan, params, transmission, current_stage, row=row, edges=edges)
+            self.clear(plan, new_infected, edges=edges)
+
+    def values(self, key=None, n_rows=None) -> torch.Tensor:
+        """A series in infections: out / GJ_LOC_UNIT formed in fp64, then float32 [rows, n_groups]."""
+        out = self.out[key] if n_rows is None else self.out[key][:n_rows]
+        return (out.to(torch.float64) / float(N.GJ_LOC_UNIT)).to(torch.float32)
+
+    def reproduction(self, n_rows: int, key=None) -> torch.Tensor:
+        """The case reproduction number by cohort, float32 [n_rows, n_groups]: the mean of ``caused`` over the agents
+        infected in row r (of group g); NaN for an empty cohort.  One ``gj_group_stats`` pass on the label
+        ``infected_row * G + g`` with ``caused`` as float32 values; the counts are an integer bincount."""
+        G, T = self.n_groups[key], int(n_rows)
+        row = self.infected_row.long()
+        label = row * G + (0 if key is None else self.labels[key].long())
+        if key is not None:
+            label = torch.where((self.labels[key] >= 0) & (self.labels[key] < G), label, torch.full_like(label, T * G))
+        label = torch.where((row >= 0) & (row < T), label, torch.full_like(label, T * G))      # bin T * G: not a cohort
+        stats = GroupStats(label, T * G + 1, device=self.device)
+        sums = torch.zeros(2 * (T * G + 1), dtype=torch.float64, device=self.device)
+        stats.add(self.caused.to(torch.float32), torch.zeros(self.n, dtype=torch.float32, device=self.device), 1, sums)
+        stats.check("reproduction number")
+        counts = torch.bincount(label, minlength=T * G + 1)[: T * G]
+        return (sums[: T * G] / counts.to(torch.float64)).to(torch.float32).view(T, G)
+
+    def check(self, what: str = "gj_infector_scatter / gj_infector_gather") -> None:
+        """Raise if a launch since the last check met bad input (one device read)."""
+        err = int(self.err.item()) & 0xFFFFFFFF
+        if err:
+            self.err.zero_()
+            why = []
+            if err & N.GJ_LOC_ERR_LABEL:
+                why.append("a label outside its labelling's groups (its agent was skipped)")
+            if err & N.GJ_LOC_ERR_VALUE:
+                why.append("a new_infected that is neither 0 nor 1 (skipped), a NaN / negative term (counted as 0) "
+                           "or a credit that is not finite (skipped)")
+            if err & N.GJ_LOC_ERR_ROWS:
+                why.append("a row pointer or venue id outside its edge set (skipped)")
+            raise InfectorError(f"{what}: " + " and ".join(why))
+
+
 class SeedPlan:
     """One labelling as ``gj_adjoint_seed`` wants it (include/gradjune_hip.h, gj_seed_plan): the agents with a label in
     [0, n_groups) sorted by label (stable), every group's segment cut into chunks of GJ_SEED_CHUNK agents.  Built once per

@@ -33,6 +33,7 @@ class GradJune(torch.nn.Module):
         self.n_steps = 0            # Philox stream id: one stream per forward() call
         self.step_stats = None      # see forward()
         self.location_stats = None  # see forward()
+        self.infector_stats = None  # see forward()
 
     @classmethod
     def from_file(cls, fpath=None):
@@ -80,7 +81,9 @@ class GradJune(torch.nn.Module):
         exp_noise = self._exp_noise(engine, exp_noise)
         # infection-location series: what forward() launches gj_location_stats with after the step (s0 and stage are
         # filled in by the path taken)
-        self._location_step = (None if getattr(self, "location_stats", None) is None else
+        # ... and gj_infector_scatter / gj_infector_gather: the two series share one record (and one clone of s0)
+        wanted = getattr(self, "location_stats", None) is not None or getattr(self, "infector_stats", None) is not None
+        self._location_step = (None if not wanted else
                                {"engine": engine, "params": where["params"], "active": [n.name for n in active]})
         if differentiable:
             return self._hot_path_differentiable(data, engine, where, active, betas, has_q, exp_noise, want_probs)
@@ -116,6 +119,8 @@ class GradJune(torch.nn.Module):
             self._location_step.update(s0=bufs.tensors["susceptibility"].clone(), stage=bufs.tensors["current_stage"])
         engine.step(bufs, where["params"],
                     engine.io(not_infected_probs=probs, new_infected=new_infected, exp_noise=exp_noise))
+        if self._location_step is not None:
+            self._location_step["transmission"] = bufs.tensors["transmission"]
         return new_infected, probs
 
     def _hot_path_differentiable(self, data, engine, where, active, betas, has_q, exp_noise, want_probs):
@@ -131,6 +136,8 @@ class GradJune(torch.nn.Module):
         fixed = {k: f(ip[k]) for k in ("max_infectiousness", "shape", "rate", "shift")}
         stage = f(ag["symptoms"]["current_stage"]).clone() if has_q else None
         env = dict(where, fixed=fixed, stage=stage, exp_noise=exp_noise, nets=list(active), betas=betas)
+        if getattr(self, "infector_stats", None) is not None:      # the node leaves its transmission array here
+            env["keep_transmission"] = self._location_step
         state = [ag[k] if ag[k].dtype == torch.float32 else ag[k].to(torch.float32) for k in
                  ("susceptibility", "is_infected", "infection_time")]
         if self._location_step is not None:      # the node returns new tensors: the incoming one stays as it is
@@ -159,6 +166,15 @@ class GradJune(torch.nn.Module):
             stats.add(plan, step["params"], nu, step["s0"], step["stage"], active=step["active"],
                       background="background", row=sink["row"], edges=edges)
 
+    def _record_infectors(self, sink, data, new_infected):
+        """gj_infector_scatter and gj_infector_gather on the step just run, for the ``groups.InfectorStats`` of the sink:
+        the location series' launch point and record, and the step's own transmissions.  No gradient."""
+        step = self._location_step
+        plan = step["engine"].plan
+        nu = new_infected.detach().to(device=plan.device, dtype=torch.float32).contiguous()
+        sink["stats"].record(plan, step["params"], nu, step["s0"], step["stage"], step["transmission"].detach(),
+                             row=sink["row"], edges=self.location_edges(data, plan))
+
     def _vaccination_env(self):
         """(global id of local agent 0, sum over the ranks of the efficacy's gradient or None): a rank of a partitioned
         world overrides it (distributed_api.DistributedGradJune)."""
@@ -182,6 +198,10 @@ class GradJune(torch.nn.Module):
         sink = getattr(self, "location_stats", None)
         if sink is not None:
             self._record_locations(sink, data, new_infected)
+        # infector_stats: the same for the infector series (groups.InfectorStats), at the same point
+        sink = getattr(self, "infector_stats", None)
+        if sink is not None:
+            self._record_infectors(sink, data, new_infected)
         # in grad mode new_infected stays on the graph: the symptoms update is then an autograd node too
         # (autograd.SymptomsStep), which is what makes the deaths series differentiable (runner.py:198-215)
         # step_stats: set by the Runner for the duration of its time loop - the per-step result reductions

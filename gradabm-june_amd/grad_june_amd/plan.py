@@ -699,6 +699,17 @@ class DevicePlan:
         self._location_rows = rows
         return rows
 
+    def infector_units(self):
+        """``(U, pointers)`` of ``gj_infector_scatter`` / ``gj_infector_gather``: one zeroed int64 tensor [n_venues,
+        cum_stride] per edge set and the host array of their device pointers, allocated on first use and kept with the
+        plan (only the infector series asks for it)."""
+        if getattr(self, "_infector_units", None) is None:
+            U = [torch.zeros(max(1, s.n_venues), int(self.c.sets[i].cum_stride), dtype=torch.int64, device=self.device)
+                 for i, s in enumerate(self.host.sets)]
+            pointers = (C.c_void_p * N.GJ_MAX_SETS)(*[u.data_ptr() for u in U])
+            self._infector_units = (U, pointers)
+        return self._infector_units
+
     def bytes_resident(self) -> int:
         n = 0
         for t in self.keep:

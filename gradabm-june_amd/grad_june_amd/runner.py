@@ -50,9 +50,10 @@ def world_from_npz(path) -> HeteroData:
 
 class Runner(torch.nn.Module):
     def __init__(self, model, data, timer, log_fraction_initial_cases, save_path, parameters,
-                 age_bins=(0, 18, 65, 100), groups=None, seed_group=None, stages=None, locations=None):
+                 age_bins=(0, 18, 65, 100), groups=None, seed_group=None, stages=None, locations=None, infectors=None):
         super().__init__()
         self._refuse_locations(locations)
+        self._refuse_infectors(infectors)
         self.model = model
         self.data = data
         self.data_backup = self.backup_infection_data(data)
@@ -94,6 +95,13 @@ class Runner(torch.nn.Module):
         self.locations_saved = locations_to_save(locations)
         self.location_keys = location_keys(model.infection_networks.networks) if self.locations_saved else []
         self._location_stats = None
+        # infector series (not in the reference): ``infectors=True`` (the YAML key ``infectors_to_save``): each step's new
+        # infections attributed to the agents who transmitted - infections caused per step, nationally and by every
+        # labelling of the INFECTOR, per agent over the run, and the case reproduction number by cohort
+        from .groups import infectors_to_save
+
+        self.infectors_saved = infectors_to_save(infectors)
+        self._infector_stats = None
         self.restore_initial_data()
 
     _supports_locations = True
@@ -105,6 +113,13 @@ class Runner(torch.nn.Module):
         if locations_to_save(spec) and not cls._supports_locations:
             raise NotImplementedError("locations_to_save: the infection-location series is not available in a "
                                       "partitioned run")
+
+    @classmethod
+    def _refuse_infectors(cls, spec):
+        from .groups import infectors_to_save
+
+        if infectors_to_save(spec) and not cls._supports_locations:      # a halo infector's credit belongs to another rank
+            raise NotImplementedError("infectors_to_save: the infector series is not available in a partitioned run")
 
     @classmethod
     def from_file(cls, fpath=None):
@@ -130,6 +145,7 @@ class Runner(torch.nn.Module):
             seed_group=seed_group,
             stages=params.get("stages_to_save"),
             locations=params.get("locations_to_save"),
+            infectors=params.get("infectors_to_save"),
         )
 
     @staticmethod
@@ -245,7 +261,7 @@ class Runner(torch.nn.Module):
                 data=self.data, timer=self.timer, symptoms_updater=self.model.symptoms_updater,
                 fractions=fractions, labels=labels, device=self.device,
                 agent_offset=getattr(self, "agent_offset", 0), plan=plan, all_reduce=self._seed_all_reduce())
-        if self.locations_saved:      # row 0 of the infection-location series
+        if self.locations_saved or self.infectors_saved:      # row 0 of the infection-location and infector series
             self._seed_new_infected = new_infected.detach()
         self.model.symptoms_updater(data=self.data, timer=self.timer, new_infected=new_infected)
 
@@ -351,7 +367,7 @@ class Runner(torch.nn.Module):
                     self._location_stats[name] = LocationStats(st.labels, st.n_groups, self.location_keys, device=dev)
         return self._location_stats
 
-    def _record_seed_locations(self, locations):
+    def _record_seed_locations(self, locations, infectors=None):
         """Row 0: the seeding step.  No network is active, so every seeded agent lands in the column ``seed``."""
         dev = require_hip(self.device)
         engine = self.model._engine(self.data, dev)
@@ -361,7 +377,23 @@ class Runner(torch.nn.Module):
         for stats in locations.values():
             stats.add(engine.plan, params, nu, s0, None, active=(), background="seed", row=0,
                       edges=self.model.location_edges(self.data, engine.plan))
+        if infectors is not None:      # nobody transmitted a seed: all unattributed; the seeds are the cohort of row 0
+            infectors.clear(engine.plan)      # (U is zero between steps; a run that was interrupted may have left some)
+            infectors.record(engine.plan, params, nu, s0, None, None, row=0,
+                             edges=self.model.location_edges(self.data, engine.plan))
         self._seed_new_infected = None
+
+    # per-step infector series: gj_infector_scatter once, gj_infector_gather for the nation and once per labelling -------
+    def _infectors(self):
+        """The run's ``groups.InfectorStats``, or None without ``infectors_to_save`` (nothing is allocated, cloned or
+        launched)."""
+        if self._infector_stats is None and self.infectors_saved:
+            from .groups import InfectorStats
+
+            self._infector_stats = InfectorStats(
+                self.n_agents, {name: (st.labels, st.n_groups) for name, st in self._groups().items()},
+                device=require_hip(self.device))
+        return self._infector_stats
 
     # vaccination series: the launches' own counts, and one gj_group_stats pass per labelling on a launch's mask ----------
     def _campaigns(self):
@@ -419,8 +451,11 @@ class Runner(torch.nn.Module):
         locations = self._locations()
         for st in locations.values():
             st.reset(n_rows)
-        if locations:
-            self._record_seed_locations(locations)
+        infectors = self._infectors()
+        if infectors is not None:
+            infectors.reset(n_rows)
+        if locations or infectors is not None:
+            self._record_seed_locations(locations, infectors)
         # vaccination series (not in the reference), whenever the model has a Vaccination policy: the doses given so far,
         # by campaign (the launches' own counts) and by every labelling (gj_group_stats on a launch's mask of the newly
         # vaccinated).  Integer counts, so a by-group row sums to the national row exactly; row 0 is zero; no gradient
@@ -462,6 +497,8 @@ class Runner(torch.nn.Module):
             model.step_stats = sink
             if locations:
                 model.location_stats = {"stats": list(locations.values()), "row": row}
+            if infectors is not None:
+                model.infector_stats = {"stats": infectors, "row": row}
             if campaigns is not None:      # cumulative: a row starts from the one before it
                 for series in self._vaccine_group_series.values():
                     series[row].copy_(series[row - 1])
@@ -472,6 +509,7 @@ class Runner(torch.nn.Module):
             finally:
                 model.step_stats = None
                 model.location_stats = None
+                model.infector_stats = None
                 if campaigns is not None:
                     campaigns.on_newly = None
             if campaigns is not None and campaigns.doses is not None:
@@ -522,6 +560,21 @@ class Runner(torch.nn.Module):
                 results["infections_by_location"] = values[:, 0, :]
             else:
                 results[f"infections_by_location_by_{key}"] = values
+        if infectors is not None:      # by the infector's group; R by the cohort's row (and group); no gradient
+            infectors.check("infector series")
+            T = row + 1
+            results["infections_caused_per_timestep"] = infectors.values(None, T)[:, 0]
+            results["infections_unattributed_per_timestep"] = infectors.unattributed[:T].to(torch.float64)      # counts: exact
+            results["reproduction_number_per_timestep"] = infectors.reproduction(T)[:, 0]
+            for name in groups:
+                results[f"infections_caused_by_{name}"] = infectors.values(name, T)
+                results[f"reproduction_number_by_{name}"] = infectors.reproduction(T, name)
+            caused, infected_row = infectors.caused, infectors.infected_row
+            if "original_index" in data["agent"]:      # per agent, in the file's order like is_infected below
+                index = data["agent"].original_index.to(caused.device)
+                caused, infected_row = torch.empty_like(caused), torch.empty_like(infected_row)
+                caused[index], infected_row[index] = infectors.caused, infectors.infected_row
+            data["agent"]["infections_caused"], data["agent"]["infected_row"] = caused, infected_row
         if campaigns is not None:      # counts as float64: exact (float32 holds integers up to 2^24 only)
             by_campaign = self._vaccine_series[: row + 1].to(torch.float64)
             results["vaccine_doses_per_timestep"] = by_campaign.sum(1)
@@ -580,6 +633,19 @@ class Runner(torch.nn.Module):
                               "location": np.tile(self.location_keys, len(dates) * G),
                               "infections": results[f"infections_by_location_by_{name}"].detach().cpu().numpy().reshape(-1)}
                              ).to_csv(self.save_path / f"results_by_location_by_{name}.csv", index=False)
+        if "infections_caused_per_timestep" in results:      # long format: date, series, value
+            dates = np.asarray(results["dates"], dtype=object)
+            series = ("infections_caused", "infections_unattributed", "reproduction_number")
+            pd.DataFrame({"date": np.repeat(dates, len(series)), "series": np.tile(series, len(dates)),
+                          "value": np.stack([results[f"{k}_per_timestep"].detach().cpu().numpy() for k in series], 1).reshape(-1)}
+                         ).to_csv(self.save_path / "results_infectors.csv", index=False)
+            for name, keys in self.group_keys.items():
+                if f"infections_caused_by_{name}" not in results:
+                    continue
+                pd.DataFrame({"date": np.repeat(dates, len(keys)), name: np.tile(keys, len(dates)),
+                              "infections_caused": results[f"infections_caused_by_{name}"].detach().cpu().numpy().reshape(-1),
+                              "reproduction_number": results[f"reproduction_number_by_{name}"].detach().cpu().numpy().reshape(-1)}
+                             ).to_csv(self.save_path / f"results_infectors_by_{name}.csv", index=False)
         pd.DataFrame({"is_infected": is_infected.detach().cpu().numpy()}).to_csv(
             self.save_path / "results_is_infected.csv")
 

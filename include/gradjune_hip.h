@@ -542,6 +542,70 @@ int gj_location_stats(const gj_plan* plan, const gj_step_params* params, const g
                       const int32_t* group, int32_t n_groups, const int32_t* cols /* host [n_nets] */, int32_t n_cols,
                       int32_t background_col, int64_t* out, uint32_t* err, void* stream);
 
+/* ---- row f2 by infector: the step's new infections attributed to the agents who transmitted ----------------------------
+ * A pure addition to ABI 7: gj_location_stats carried one level further, through the venue.  Run at the same point -
+ * AFTER a step, with its `params`, while plan->sets[s].cum holds the step's sums, current_stage is the stage the
+ * quarantine mask was formed from and state->transmission is the step's - as two sparse passes over `rows`.
+ * Notation: network i of params->nets lives on set s_i, column k_i of that set's cum, with beta_i; w_i[a] is the
+ * receiving-side weight of gj_mask_kind exactly as gj_location_stats forms it, m_i[b] the transmitting-side one: 1 (RAW),
+ * q[b] (Q), q[b] * L_i[day_type][class[b]] (QL and QL_AGE75: care_visit's age > 75 is on the receiving side only,
+ * leisure_network.py:107-120).  U[s]: device int64 [n_venues][cum_stride] per set, HOST array [plan->n_sets] of device
+ * pointers, all zero before pass 1 (gj_infector_clear, or a memset).
+ *
+ * gj_infector_scatter (pass 1).  For every agent a with new_infected[a] == 1: t_i and T = t_0 + t_1 + ... are exactly
+ * gj_location_stats' values, and for every edge e of a's row in set s_i, at venue v_e, in fp64
+ *   t_{i,e} = (w_i[a] * susceptibility0[a]) * cum_{s_i}[v_e][k_i]          (NaN or negative: 0, sets GJ_LOC_ERR_VALUE)
+ * A network whose t_i is 0 - by its mask, or because gj_location_stats' rule refused it - has t_{i,e} = 0 at every edge.
+ * T finite and > 0: u_{i,e} = floor(t_{i,e} / T * GJ_LOC_UNIT) (at most GJ_LOC_UNIT), and the remainder GJ_LOC_UNIT - sum u
+ * goes to the pair with the largest t_{i,e}: the lowest i on a tie, then the lowest position in the row.  The remainder
+ * is >= 0: every term is non-negative and at most GJ_MAX_NETS * 4096 of them reassociate in fp64, which moves the sum
+ * by less than 2^-7 of a unit.  (Only a negative cum next to larger positive ones - reported as GJ_LOC_ERR_VALUE - can
+ * make sum u exceed GJ_LOC_UNIT; nothing is taken back then.)  Every u is added to U[s_i][v_e][k_i] with a 64-bit integer
+ * atomic, so no order of the agents or of the workgroups changes a bit of U, and U sums to GJ_LOC_UNIT * (attributed
+ * infections).  Otherwise nothing is scattered and *unattributed (device int64; the call ADDS) counts the infection:
+ * the decision that sends it to background_col in gj_location_stats, from the same values.
+ * cohort (device int32 [n_agents], or NULL): cohort[a] = cohort_value for every a with new_infected[a] == 1.
+ * n_nets == 0 is valid (the seeding step): every infection is unattributed, cohort is written, U may be NULL.
+ *
+ * gj_infector_gather (pass 2).  For every agent b with transmission[b] > 0, in fp64:
+ *   credit[b] = sum_i sum over the edges e of b's row in s_i with U != 0 of
+ *               U[s_i][v_e][k_i] / GJ_LOC_UNIT * beta_i * pc[v_e] * m_i[b] * transmission[b] / cum_{s_i}[v_e][k_i]
+ * pc = gj_edge_set.v_pcontact; cum is read only where U != 0 - the few venues with a new infection - and a cum that is
+ * not finite or <= 0 there cannot follow from pass 1: the pair is skipped and GJ_LOC_ERR_VALUE set; so is an agent whose
+ * credit is not finite.  Then caused[b] += credit (caused: device fp64 [n_agents] or NULL) and out[group[b]] +=
+ * llrint(credit * GJ_LOC_UNIT) (out: device int64 [n_groups] or NULL; integer adds, order-free).  caused and out are
+ * separate so that several labellings can be summed from one step (one call with caused, the others without).
+ * The credits of one venue sum to its U / GJ_LOC_UNIT only up to the fp32 roundings inside cum - cum is
+ * fp32(beta * pc) * fp32(sum of m * transmission) - so a step's credits sum to its attributed infections approximately
+ * (relative 2^-22 per venue at worst), not exactly; U itself and the counts are exact.
+ * An agent with transmission <= 0 or NaN is untouched.  n_nets == 0 launches nothing.
+ *
+ * gj_infector_clear: U back to zero by the way it was filled - plain stores of 0 to every column of the venues that the
+ * rows of the agents with new_infected != 0 name - instead of a memset of all of U.  Sets without rows or U are skipped.
+ *
+ * All three: rows as for gj_location_stats; n_agents == 0 launches nothing; one launch each, the launch shape of
+ * gj_location_stats (a wave ballots 256 agents and hands the flagged ones to its four groups of 16 lanes, whose lanes
+ * stride over the agent's edges); the gather adds through an LDS histogram up to GJ_LOC_LDS_BINS groups, and takes a
+ * round of 256 agents with 16 or more infectious ones one agent per lane instead (late in an epidemic a third of the
+ * agents transmit: four agents per wave at a time are then too few loads in flight).  The credit's terms are added in
+ * fp64 in the order of the path taken - all non-negative, so the paths agree to 4096 * 2^-53 relative.  Bad input
+ * never reaches memory: a label outside [0, n_groups) skips its agent (never an index) and sets GJ_LOC_ERR_LABEL; a
+ * new_infected that is neither 0 nor 1 is skipped and sets GJ_LOC_ERR_VALUE; a row pointer or venue id outside its set is
+ * skipped and sets GJ_LOC_ERR_ROWS.  *err (device uint32) is sticky until the caller clears it.
+ * Errors, returned before any device work: what gj_location_stats returns for a bad plan, params or rows; GJ_E_NULL for
+ * a NULL new_infected, susceptibility0, unattributed or err (scatter), transmission or err or both of caused and out
+ * (gather), a NULL current_stage with has_quarantine, a NULL U with n_nets > 0 or U[s] of a set with rows, venues and an
+ * active network; GJ_E_RANGE for n_groups outside 1..GJ_MAX_GROUPS or group == NULL with n_groups != 1.             */
+int gj_infector_scatter(const gj_plan* plan, const gj_step_params* params, const gj_location_rows* rows /* [plan->n_sets] */,
+                        const float* new_infected, const float* susceptibility0, const float* current_stage,
+                        int64_t* const* U /* host [plan->n_sets] */, int64_t* unattributed, int32_t* cohort,
+                        int32_t cohort_value, uint32_t* err, void* stream);
+int gj_infector_gather(const gj_plan* plan, const gj_step_params* params, const gj_location_rows* rows /* [plan->n_sets] */,
+                       const float* transmission, const float* current_stage, int64_t* const* U /* host [plan->n_sets] */,
+                       const int32_t* group, int32_t n_groups, double* caused, int64_t* out, uint32_t* err, void* stream);
+int gj_infector_clear(const gj_plan* plan, const gj_location_rows* rows /* [plan->n_sets] */, const float* new_infected,
+                      int64_t* const* U /* host [plan->n_sets] */, void* stream);
+
 /* ---- row f3: adjoint (backward) of one hot-path step, forward-only kernels reused ---------------
  * The aggregation ts = susc * sum_n w_n * (M_n^T diag(beta_n p_contact) M_n)(m_n * transmission) is
  * self-adjoint up to the exchange of the masks m_n <-> w_n, so its backward is the same four tiled
