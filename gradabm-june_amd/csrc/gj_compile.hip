@@ -269,6 +269,12 @@ __global__ void k_ell_fill(const uint32_t* keys, const uint32_t* order, int64_t 
   }
 }
 
+// gj_aux.e_lv8 (plan.narrow_venue_ids): the local venue of every slot in one byte, for a set whose blocks hold <= 255 venues
+__global__ void k_narrow_venue_ids(const uint16_t* e_lv, int64_t n, uint8_t* e_lv8) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    e_lv8[i] = e_lv[i] == 0xFFFF ? (uint8_t)0xFF : (uint8_t)e_lv[i];
+}
+
 // explicit slots (tiling.build_tiled, slot_idx): the block-major slot of every slice-major edge position
 __global__ void k_explicit_slots(const int32_t* sptr, const int32_t* tile_jpos, int64_t n_tiles, int64_t E, int32_t* slots) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < E; i += (int64_t)gridDim.x * blockDim.x) {
@@ -736,6 +742,14 @@ int gj_compile_multi_slots(const gj_compile_set* set, const gj_compile_out* out,
   gjc::k_multi_fill<<<gjc::grid_for((int64_t)n_chunks * 64), gjc::kThreads, 0, st>>>(
       out->chunk_ptr, out->tile_sptr, out->tile_jpos, set->n_blocks, set->n_slices, n_chunks, wide, rows, desc, multi_slots,
       counts);
+  return (int)hipGetLastError();
+}
+
+int gj_narrow_venue_ids(int64_t n_slots, const uint16_t* e_lv, uint8_t* e_lv8, void* stream) {
+  if (n_slots < 0) return GJ_E_RANGE;
+  if (n_slots == 0) return 0;
+  if (!e_lv || !e_lv8) return GJ_E_NULL;
+  gjc::k_narrow_venue_ids<<<gjc::grid_for(n_slots), gjc::kThreads, 0, (hipStream_t)stream>>>(e_lv, n_slots, e_lv8);
   return (int)hipGetLastError();
 }
 

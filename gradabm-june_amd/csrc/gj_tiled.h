@@ -560,6 +560,7 @@ struct TSetB {
   const int32_t* blk_v0;
   const int32_t* blk_e0;
   const uint16_t* e_lv;
+  const uint8_t* e_lv8;                    // gj_aux.e_lv8: e_lv in one byte per slot (blocks of <= 255 venues), or NULL
   const uint8_t* e_cls;
   float* val;
   const float* v_pc;
@@ -669,6 +670,20 @@ struct Group8 {
   }
 };
 
+// Eight slots' local venues from their one-byte form (gj_aux.e_lv8: a set whose blocks hold <= 255 venues) to the 16
+// bytes Group8 takes: the same integers, the pad value 0xFF becoming 0xFFFF.  Three instructions per pair of slots:
+// v_perm_b32 spreads two bytes over the halves of a word; + 0x7F01 per half sets a half's top bit for 0xFF alone (no
+// carry leaves a half: 0xFF + 0x7F01 = 0x8000); a second v_perm_b32 writes that bit over the half's high byte
+// (selectors 8 / 9: bit 15 / 31 of the second operand replicated, 12: 0x00, 4-7: bytes of the first operand).
+__device__ __forceinline__ uint32_t widen_lv_pair(uint32_t four, uint32_t spread) {
+  const uint32_t w = __builtin_amdgcn_perm(0u, four, spread);
+  return __builtin_amdgcn_perm(w, w + 0x7F017F01u, 0x09060804u);
+}
+__device__ __forceinline__ uint4 widen_lv8(uint2 raw) {
+  return make_uint4(widen_lv_pair(raw.x, 0x0c010c00u), widen_lv_pair(raw.x, 0x0c030c02u),
+                    widen_lv_pair(raw.y, 0x0c010c00u), widen_lv_pair(raw.y, 0x0c030c02u));
+}
+
 // timing diagnostics (tools/venue_timeline.py, a -DGJ_DIAG_STAMPS build): start / end time and XCD of every workgroup
 // of the last venue launch
 #ifdef GJ_DIAG_STAMPS
@@ -712,7 +727,12 @@ struct VenueItem {
         tabs(lds + 2 * (((size_t)nk * nv + 64 + 1) & ~(size_t)1)), tabs2(tabs + (T_.leisure ? (wpad ? wpad : nk) * 200 : 0)),
         vflags(reinterpret_cast<uint32_t*>(tabs2 + (T_.leisure ? nk * 200 : 0))), vwords((nk * nv + 64 + 31) / 32),
         dummy(nk * nv + (tid_ & 63)) {}
-  __device__ __forceinline__ const uint4* lv8() const { return reinterpret_cast<const uint4*>(T.e_lv); }
+  // group g's local venues; NARROW (wave-uniform per set, chosen outside the group loops): from the one-byte form
+  template <bool NARROW>
+  __device__ __forceinline__ uint4 lv8(int g) const {
+    if (NARROW) return widen_lv8(reinterpret_cast<const uint2*>(T.e_lv8)[g]);
+    return reinterpret_cast<const uint4*>(T.e_lv)[g];
+  }
   __device__ __forceinline__ const uint2* cls8() const { return reinterpret_cast<const uint2*>(T.e_cls); }
   __device__ __forceinline__ float4* val4() const { return reinterpret_cast<float4*>(T.val); }
 };
@@ -863,6 +883,7 @@ __device__ __forceinline__ void venue_zero(const VenueItem& W, fx_t* sums, uint3
 
 // Phase B over the block's tiled groups: each lane takes 8 consecutive slots (48 bytes), merges runs of one venue in
 // registers and adds each run to the block's LDS sums; kVenueUnroll such groups are loaded before the first is used.
+template <bool NARROW>
 __device__ __forceinline__ void venue_sums_tiled(const VenueItem& W, const float* weights, fx_t* sums, uint32_t* vflags) {
   const TSetB& T = W.T;
   const float wmax = T.multinet ? max_class_weight(weights, 200 * W.wpad, W.tid) : 0.0f;
@@ -889,7 +910,7 @@ __device__ __forceinline__ void venue_sums_tiled(const VenueItem& W, const float
 #pragma unroll
     for (int u = 0; u < kVenueUnroll; ++u) {     // clamped, unconditional: all loads in flight together
       const int gu = min(g + u * kTileThreads, W.g1 - 1);
-      raw[u] = W.lv8()[gu];
+      raw[u] = W.lv8<NARROW>(gu);
       xa[u] = load_nt(W.val4() + 2 * gu);        // read once, written by phase A: non-temporal
       xb[u] = load_nt(W.val4() + 2 * gu + 1);
       craw[u] = T.leisure ? W.cls8()[gu] : make_uint2(0u, 0u);
@@ -986,6 +1007,7 @@ __device__ __forceinline__ void venue_cum_read(const VenueItem& W, float* cumf) 
 }
 
 // Phase C: per slot, the venue's cum (leisure: weighted over the set's networks by the agent's class)
+template <bool NARROW>
 __device__ __forceinline__ void venue_gather(const VenueItem& W, const float* weights, const float* cumf) {
   const TSetB& T = W.T;
   const int nk = W.nk, nv = W.nv;
@@ -995,7 +1017,7 @@ __device__ __forceinline__ void venue_gather(const VenueItem& W, const float* we
 #pragma unroll
     for (int u = 0; u < kVenueUnrollC; ++u) {
       const int gu = min(g + u * kTileThreads, W.g1 - 1);
-      raw[u] = W.lv8()[gu];
+      raw[u] = W.lv8<NARROW>(gu);
       craw[u] = T.leisure ? W.cls8()[gu] : make_uint2(0u, 0u);
     }
 #pragma unroll
@@ -1050,7 +1072,11 @@ __global__ __launch_bounds__(kTileThreads, GJ_VENUE_WAVES_PER_SIMD) void k_tile_
   if (B.mode != 2) {
     venue_zero(W, W.sums, W.vflags);
     __syncthreads();                            // the sums are zero and the tables written before the first add
-    venue_sums_tiled(W, W.tabs, W.sums, W.vflags);
+    if (T.e_lv8) {
+      venue_sums_tiled<true>(W, W.tabs, W.sums, W.vflags);
+    } else {
+      venue_sums_tiled<false>(W, W.tabs, W.sums, W.vflags);
+    }
     if (T.pv_blk) venue_sums_runs(W, j, W.sums, W.vflags);
     __syncthreads();                            // every wave's adds have landed
     venue_cum_write(W, W.sums, W.vflags, W.cumf);
@@ -1060,7 +1086,11 @@ __global__ __launch_bounds__(kTileThreads, GJ_VENUE_WAVES_PER_SIMD) void k_tile_
     venue_cum_read(W, W.cumf);
   }
   __syncthreads();                              // cumf is complete
-  venue_gather(W, W.tabs2, W.cumf);
+  if (T.e_lv8) {
+    venue_gather<true>(W, W.tabs2, W.cumf);
+  } else {
+    venue_gather<false>(W, W.tabs2, W.cumf);
+  }
 }
 
 // ---- pass 1 in the "direct" form (sets with few venues whose edges all belong to owned agents) ----------------------

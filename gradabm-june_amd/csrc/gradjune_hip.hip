@@ -976,7 +976,7 @@ static uint32_t venue_term_limit(int32_t max_venue_edges) {
 }
 
 static int tiled_venues(const gj_plan* plan, const gj_agent_state* st, const gj_step_params* p, const Groups& G, int mode,
-                        hipStream_t stream) {
+                        hipStream_t stream, const gj_aux* aux = nullptr) {
   const gj_tiled* T = plan->tiled;
   if (G.n == 0) return GJ_OK;
   if (T->n_work == 0) return mode == 2 ? GJ_OK : tiled_presum_reduce(plan, p, G, stream);
@@ -991,6 +991,9 @@ static int tiled_venues(const gj_plan* plan, const gj_agent_state* st, const gj_
     X.blk_v0 = S.blk_v0;
     X.blk_e0 = S.blk_e0;
     X.e_lv = S.e_lv;
+    // gj_aux.e_lv8: the same ids in one byte per slot, for the forward step of a set whose blocks hold <= 255 venues
+    X.e_lv8 = (aux && !p->transpose) ? aux->e_lv8[s] : nullptr;
+    if (X.e_lv8 && (S.max_block_venues > 255 || (uintptr_t)X.e_lv8 % 8 != 0)) return GJ_E_PLAN;
     X.e_cls = S.e_cls;
     X.val = S.val;
     X.v_pc = E.v_pcontact;
@@ -1871,6 +1874,11 @@ int gj_infector_clear(const gj_plan* plan, const gj_location_rows* rows, const f
 
 int gj_step(const gj_plan* plan, const gj_agent_state* state, const gj_step_params* params, const gj_step_io* io,
             void* stream) {
+  return gj_step_aux(plan, state, params, io, nullptr, stream);
+}
+
+int gj_step_aux(const gj_plan* plan, const gj_agent_state* state, const gj_step_params* params, const gj_step_io* io,
+                const gj_aux* aux, void* stream) {
   int rc = gj::check_plan(plan);
   if (rc) return rc;
   gj::Groups G;
@@ -1883,7 +1891,7 @@ int gj_step(const gj_plan* plan, const gj_agent_state* state, const gj_step_para
   if (plan->tiled) {
     rc = gj::tiled_scatter(plan, state, params, G, (hipStream_t)stream);
     if (rc) return rc;
-    rc = gj::tiled_venues(plan, state, params, G, 0, (hipStream_t)stream);
+    rc = gj::tiled_venues(plan, state, params, G, 0, (hipStream_t)stream, aux);
     if (rc) return rc;
     return gj::tiled_agents(plan, state, params, G, io, 1, (hipStream_t)stream);
   }
@@ -1894,6 +1902,11 @@ int gj_step(const gj_plan* plan, const gj_agent_state* state, const gj_step_para
 
 int gj_step_phase(const gj_plan* plan, const gj_agent_state* state, const gj_step_params* params,
                   const gj_step_io* io, int phase, void* stream) {
+  return gj_step_phase_aux(plan, state, params, io, nullptr, phase, stream);
+}
+
+int gj_step_phase_aux(const gj_plan* plan, const gj_agent_state* state, const gj_step_params* params,
+                      const gj_step_io* io, const gj_aux* aux, int phase, void* stream) {
   int rc = gj::check_plan(plan);
   if (rc) return rc;
   gj::Groups G;
@@ -1906,19 +1919,19 @@ int gj_step_phase(const gj_plan* plan, const gj_agent_state* state, const gj_ste
     case 0: return gj::do_transmission(plan, state, params, st);
     case 1: return plan->tiled ? gj::tiled_scatter(plan, state, params, G, st)
                                : gj::do_venue_reduce(plan, state, params, G, st);
-    case 2: return plan->tiled ? gj::tiled_venues(plan, state, params, G, 0, st) : GJ_OK;
+    case 2: return plan->tiled ? gj::tiled_venues(plan, state, params, G, 0, st, aux) : GJ_OK;
     case 3: return plan->tiled ? gj::tiled_agents(plan, state, params, G, io, 1, st)
                                : gj::do_agent_gather(plan, state, params, G, io, 1, st);
     case 4: return plan->tiled ? gj::tiled_agents(plan, state, params, G, io, 0, st)
                                : gj::do_agent_gather(plan, state, params, G, io, 0, st);
-    case 5: return plan->tiled ? gj::tiled_venues(plan, state, params, G, 1, st) : GJ_OK;
-    case 6: return plan->tiled ? gj::tiled_venues(plan, state, params, G, 2, st) : GJ_OK;
+    case 5: return plan->tiled ? gj::tiled_venues(plan, state, params, G, 1, st, aux) : GJ_OK;
+    case 6: return plan->tiled ? gj::tiled_venues(plan, state, params, G, 2, st, aux) : GJ_OK;
     case 7:   // 1 then 5 (A + B) in one call: the launch path of a partial-sum group
     case 8:   // 1 then 2 (A + B + C)
       if (!plan->tiled) return gj::do_venue_reduce(plan, state, params, G, st);
       rc = gj::tiled_scatter(plan, state, params, G, st);
       if (rc) return rc;
-      return gj::tiled_venues(plan, state, params, G, phase == 7 ? 1 : 0, st);
+      return gj::tiled_venues(plan, state, params, G, phase == 7 ? 1 : 0, st, aux);
     default: return GJ_E_RANGE;
   }
 }

@@ -173,6 +173,12 @@ class StepIO(C.Structure):
     ]
 
 
+class Aux(C.Structure):
+    _fields_ = [
+        ("e_lv8", _vp * GJ_MAX_SETS),
+    ]
+
+
 GJ_MAX_STAGES = 16
 
 
@@ -298,6 +304,12 @@ SYMBOLS = {
         C.c_int,
         [C.POINTER(Plan), C.POINTER(AgentState), C.POINTER(StepParams), C.POINTER(StepIO), C.c_int, _vp],
     ),
+    "gj_step_aux": (
+        C.c_int, [C.POINTER(Plan), C.POINTER(AgentState), C.POINTER(StepParams), C.POINTER(StepIO), C.POINTER(Aux), _vp]),
+    "gj_step_phase_aux": (
+        C.c_int,
+        [C.POINTER(Plan), C.POINTER(AgentState), C.POINTER(StepParams), C.POINTER(StepIO), C.POINTER(Aux), C.c_int, _vp],
+    ),
     "gj_clock_advance": (C.c_int, [_vp, C.c_double, _vp]),
     "gj_symptoms_step_stats": (
         C.c_int,
@@ -345,6 +357,7 @@ SYMBOLS.update({
     "gj_compile_explicit_slots": (C.c_int, [C.POINTER(CompileSet), C.POINTER(CompileOut), _vp, _vp]),
     "gj_compile_multi_slots": (C.c_int, [C.POINTER(CompileSet), C.POINTER(CompileOut), C.c_int32, C.c_int32, _vp,
                                           C.c_int32, _vp, _vp, _vp, C.c_int64, _vp]),
+    "gj_narrow_venue_ids": (C.c_int, [C.c_int64, _vp, _vp, _vp]),
     "gj_compile_runs_pick": (C.c_int, [C.POINTER(CompileSet), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gj_compile_runs_rest": (C.c_int, [C.POINTER(CompileSet), _vp, _vp, _vp, _vp, C.c_int64, _vp, _vp]),
     "gj_compile_runs_index": (C.c_int, [C.POINTER(CompileSet), _vp, _vp, C.c_int32, C.c_int64, _vp, _vp, _vp, _vp, _vp]),

@@ -81,6 +81,9 @@ class InfectionEngine:
         self.lib = N.load()
         self.plan = plan
         self._q_trans: Optional[torch.Tensor] = None
+        self.aux = N.Aux()                   # the plan's narrower copies of what the step streams (gj_aux)
+        for i, t in enumerate(plan.lv8):
+            self.aux.e_lv8[i] = N.ptr(t)
 
     # -- parameter marshalling --------------------------------------------------------------
     def q_transmission_buffer(self) -> torch.Tensor:
@@ -147,13 +150,13 @@ class InfectionEngine:
 
     def step(self, bufs: AgentBuffers, p: N.StepParams, io: N.StepIO):
         self._prep(bufs, p)
-        N.check(self.lib.gj_step(C.byref(self.plan.c), C.byref(bufs.c), C.byref(p), C.byref(io),
-                                 N.current_stream()), "gj_step")
+        N.check(self.lib.gj_step_aux(C.byref(self.plan.c), C.byref(bufs.c), C.byref(p), C.byref(io), C.byref(self.aux),
+                                     N.current_stream()), "gj_step")
 
     def step_phase(self, bufs: AgentBuffers, p: N.StepParams, io: N.StepIO, phase: int):
         self._prep(bufs, p)
-        N.check(self.lib.gj_step_phase(C.byref(self.plan.c), C.byref(bufs.c), C.byref(p), C.byref(io), int(phase),
-                                       N.current_stream()), "gj_step_phase")
+        N.check(self.lib.gj_step_phase_aux(C.byref(self.plan.c), C.byref(bufs.c), C.byref(p), C.byref(io),
+                                           C.byref(self.aux), int(phase), N.current_stream()), "gj_step_phase")
 
     def sample_infect(self, not_infected_probs, *, now: float, susceptibility, is_infected, infection_time,
                       exp_noise=None, new_infected=None, seed: int = 0, step: int = 0, agent_offset: int = 0):

@@ -282,6 +282,18 @@ def load_plan(path) -> HostPlan:
                     slice_agents=int(a["meta/slice_agents"]), work=a.get("work"))
 
 
+LV8_MAX_BLOCK_VENUES = 255   # a set whose every venue block holds at most this many venues has one-byte local ids
+
+
+def narrow_venue_ids(e_lv) -> np.ndarray:
+    """``e_lv`` (uint16 local venue of every block-major slot, 0xFFFF = pad) in one byte per slot, 0xFF = pad: what the
+    venue launch reads for a set whose blocks hold at most 255 venues (``gj_aux.e_lv8``).  The specification of the
+    device kernel ``gj_narrow_venue_ids``, which is what ``DevicePlan`` runs."""
+    e = _host(e_lv)
+    e = e.view(np.uint16) if e.dtype == np.int16 else e.astype(np.uint16)
+    return np.where(e == 0xFFFF, 0xFF, e).astype(np.uint8)
+
+
 def agent_class_of(age, sex) -> np.ndarray:
     age = np.asarray(age).astype(np.int64)
     sex = np.asarray(sex).astype(np.int64)
@@ -508,10 +520,16 @@ class DevicePlan:
     """The plan resident in HBM + the ctypes ``gj_plan`` that points at it."""
 
     def __init__(self, host: HostPlan, networks: Sequence[NetworkSpec], device, flat_cum_sets: Sequence[str] = (),
-                 split_epilogue: bool = False, direct_table_floats: int = 0):
+                 split_epilogue: bool = False, direct_table_floats: int = 0, lv8: Optional[bool] = None):
         """flat_cum_sets: edge sets whose ``cum`` workspaces are carved from ONE contiguous buffer
-        (``self.flat_cum``) so that a single collective can combine them across ranks."""
+        (``self.flat_cum``) so that a single collective can combine them across ranks.
+        lv8: a tiled set whose every block holds at most 255 venues also gets its local venue ids in one byte per slot
+        (``self.lv8[set]``, ``gj_aux.e_lv8``: 1 byte per slot more memory, 1 byte per slot less for the venue launch to
+        read, same results bit for bit).  None: on, unless GJ_LV8=0."""
         self.host = host
+        if lv8 is None:
+            lv8 = os.environ.get("GJ_LV8", "1") != "0"
+        self.lv8: List[Optional[torch.Tensor]] = [None] * len(host.sets)
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("grad_june_amd runs the infection path on a HIP device only (no CPU path)")
@@ -607,6 +625,12 @@ class DevicePlan:
                 c.tile_sptr, c.tile_jpos, c.val = t["tile_sptr"].data_ptr(), t["tile_jpos"].data_ptr(), t["val"].data_ptr()
                 c.chunk_ptr, c.chunk_desc = t["chunk_ptr"].data_ptr(), N.ptr(t["chunk_desc"])
                 c.ell_k, c.ell = int(ts.ell_k), N.ptr(t.get("ell"))
+                if lv8 and 0 < c.max_block_venues <= LV8_MAX_BLOCK_VENUES and t["e_lv"].numel():
+                    n_lv = t["e_lv"].numel()
+                    t["e_lv8"] = torch.full((-(-n_lv // 8) * 8,), 0xFF, dtype=torch.uint8, device=dev)
+                    N.check(N.load().gj_narrow_venue_ids(n_lv, t["e_lv"].data_ptr(), t["e_lv8"].data_ptr(),
+                                                         N.current_stream()), "gj_narrow_venue_ids")
+                    self.lv8[i] = t["e_lv8"]
                 if ts.runs is not None:
                     rf = ts.runs
                     pad16 = lambda a: torch.cat([a, torch.full((8,), -1, dtype=a.dtype, device=a.device)])  # 16-byte groups

@@ -780,6 +780,21 @@ int gj_step(const gj_plan* plan, const gj_agent_state* state, const gj_step_para
 int gj_step_phase(const gj_plan* plan, const gj_agent_state* state, const gj_step_params* params,
                   const gj_step_io* io, int phase, void* stream);
 
+/* Narrower copies of arrays the step streams, built ONCE from data that stays the same from step to step (the contact
+ * graph).  Every pointer may be NULL: that stream is then read in its original form.
+ * A NULL `aux` is gj_step / gj_step_phase exactly; no result depends on it, bit for bit.  A pure addition to ABI 7.
+ *   e_lv8[s]           device uint8 [slots of set s, rounded up to 8] = gj_tiled_set.e_lv in one byte per slot, 0xFF
+ *                      for the pad value 0xFFFF (gj_narrow_venue_ids), 8-byte aligned.  Only for a set whose every
+ *                      block holds at most 255 venues (max_block_venues <= 255, else GJ_E_PLAN): the venue launch of
+ *                      the forward step reads it instead of e_lv.  Every other reader keeps the 16-bit array. */
+typedef struct gj_aux {
+  const uint8_t* e_lv8[GJ_MAX_SETS];
+} gj_aux;
+int gj_step_aux(const gj_plan* plan, const gj_agent_state* state, const gj_step_params* params,
+                const gj_step_io* io, const gj_aux* aux, void* stream);
+int gj_step_phase_aux(const gj_plan* plan, const gj_agent_state* state, const gj_step_params* params,
+                      const gj_step_io* io, const gj_aux* aux, int phase, void* stream);
+
 /* clock->step += 1; clock->now = (float)(now0 + (step - step0) * delta_now), in double: a step length that is not a
  * power of two (hours / 24) does not drift over the replays.  One tiny launch on `stream` (the first node of a
  * captured step).                                                                                                 */
@@ -876,6 +891,9 @@ int gj_compile_explicit_slots(const gj_compile_set* set, const gj_compile_out* o
 int gj_compile_multi_slots(const gj_compile_set* set, const gj_compile_out* out, int32_t n_chunks, int32_t wide,
                            int32_t* desc, int32_t n_multi, int32_t* multi_slots, int32_t* counts, void* workspace,
                            int64_t workspace_bytes, void* stream);
+/* (after the compile, for a set whose every block holds at most 255 venues) gj_aux.e_lv8:
+ * e_lv8[i] = e_lv[i] == 0xFFFF ? 0xFF : (uint8_t)e_lv[i] for i < n_slots.  The caller decides eligibility from blk_v0. */
+int gj_narrow_venue_ids(int64_t n_slots, const uint16_t* e_lv, uint8_t* e_lv8, void* stream);
 
 /* ---- run form of the set that orders the agents (gj_tiled_set.run_*; specification: tiling.split_primary_runs /
  * finish_run_form).  Three steps around the compile of the set's remaining edges:

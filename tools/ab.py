@@ -9,6 +9,9 @@ e.g.  python tools/ab.py base unroll8:GJ_UNROLL_NARROW=8 "nodirect@--direct off"
 (%ENV=VAL: environment of that variant's bench.py run - what the host-side plan compile reads.)
 Variants are built here (hipcc cross-compiles without a GPU) by `--build-only`; on the GPU box the prebuilt
 libraries under gradabm-june_amd/grad_june_amd/lib/variants/ are used.
+`--tree label=DIR`: variant `label` is another checkout of the project, built (the parent commit of a change to the ABI
+or the Python layer): DIR/bench.py runs with DIR's own library.
+A run that fails or exceeds `--run-timeout` ends the comparison: nothing more is started on that GPU.
 """
 from __future__ import annotations
 
@@ -59,24 +62,39 @@ def main():
     ap.add_argument("--common", default="--device-compile --no-cpu-baseline --full",
                     help="bench.py arguments of every variant")
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "ab.jsonl"))
+    ap.add_argument("--tree", action="append", default=[], metavar="LABEL=DIR")
+    ap.add_argument("--run-timeout", type=float, default=300.0, help="seconds per bench.py run")
     a = ap.parse_args()
+    trees = dict(t.split("=", 1) for t in a.tree)
     vs = [parse_variant(v) for v in a.variants]
     if a.build_only:
         for label, defs, bargs, _ in vs:
+            if label in trees:
+                continue
             if defs or label == "base" or not bargs:
                 build(label, defs)
                 print("built", lib_path(label))
         return
     rows = []
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    failed = False
     for rnd in range(a.rounds):
         for label, defs, bargs, envs in vs:
-            env = dict(os.environ, GJ_LIB_PATH=lib_of(label), **envs)
-            cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(a.steps), "--warmup", "5",
+            if failed:
+                break
+            root = os.path.abspath(trees[label]) if label in trees else ROOT
+            env = dict(os.environ, **envs) if label in trees else dict(os.environ, GJ_LIB_PATH=lib_of(label), **envs)
+            cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", str(a.steps), "--warmup", "5",
                    "--world-cache", "/tmp/gj_worlds", *a.common.split(), *bargs]
-            r = subprocess.run(cmd, env=env, capture_output=True, text=True)
+            try:
+                r = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=a.run_timeout)
+            except subprocess.TimeoutExpired:
+                print(f"{label}: no result after {a.run_timeout:.0f} s", flush=True)
+                failed = True
+                continue
             if r.returncode != 0:
-                print(f"{label}: FAILED\n{r.stderr[-2000:]}", flush=True)
+                print(f"{label}: FAILED ({r.returncode})\n{r.stderr[-2000:]}", flush=True)
+                failed = True
                 continue
             d = json.loads(r.stdout.strip().splitlines()[-1])
             row = {"label": label, "round": rnd, "ms_per_step": d["ms_per_step"], "kernel_ms": d["kernel_ms"],
