@@ -1763,20 +1763,24 @@ int gj_location_stats(const gj_plan* plan, const gj_step_params* params, const g
   return gj::launch(gj::k_location_stats<false>, blocks, gj::kThreads, 0, (hipStream_t)stream, A);
 }
 
-// the sets of the step's networks as the infector kernels take them: the location kernel's, with p_contact, U and beta
+// the sets of the step's networks as the infector kernels take them: the location kernel's, with p_contact, U and beta;
+// and UG where the caller takes it (the infection-matrix launches: the scatter takes UG alone, the gather both)
+enum { kInfU = 1, kInfUG = 2 };
 static int infector_sets(const gj_plan* plan, const gj_step_params* params, const gj_location_rows* rows,
-                         int64_t* const* U, gj::InfArgs* A) {
+                         int64_t* const* U, gj::InfArgs* A, int64_t* const* UG = nullptr, int takes = kInfU) {
   int rc = gj::check_plan(plan);
   if (rc) return rc;
   gj::Groups G;
   rc = gj::group_networks(plan, params, &G);
   if (rc) return rc;
-  if ((plan->n_sets > 0 && !rows) || (params->n_nets > 0 && !U)) return GJ_E_NULL;
+  if (plan->n_sets > 0 && !rows) return GJ_E_NULL;
+  if (params->n_nets > 0 && (((takes & kInfU) && !U) || ((takes & kInfUG) && !UG))) return GJ_E_NULL;
   for (int g = 0; g < G.n; ++g) {
     const gj_edge_set& E = plan->sets[G.set[g]];
     const gj_location_rows& R = rows[G.set[g]];
     if (R.a_rowptr && !R.a_venue && E.n_edges > 0) return GJ_E_NULL;
-    if (R.a_rowptr && E.n_venues > 0 && !U[G.set[g]]) return GJ_E_NULL;
+    if ((takes & kInfU) && R.a_rowptr && E.n_venues > 0 && !U[G.set[g]]) return GJ_E_NULL;
+    if ((takes & kInfUG) && R.a_rowptr && E.n_venues > 0 && !UG[G.set[g]]) return GJ_E_NULL;
     const gj::NetGroup C = gj::classify_group(params, G, g);
     gj::InfSet& S = A->sets[g];
     S.rowptr = R.a_rowptr;
@@ -1791,7 +1795,8 @@ static int infector_sets(const gj_plan* plan, const gj_step_params* params, cons
     memcpy(S.table, C.table, sizeof(S.table));
     memcpy(S.beta, C.beta, sizeof(S.beta));
     S.pc = E.v_pcontact;
-    S.U = (unsigned long long*)U[G.set[g]];
+    S.U = (takes & kInfU) ? (unsigned long long*)U[G.set[g]] : nullptr;
+    S.UG = (takes & kInfUG) ? (unsigned long long*)UG[G.set[g]] : nullptr;
   }
   A->n = plan->n_agents;
   A->cls = plan->agent_class;
@@ -1820,8 +1825,8 @@ int gj_infector_scatter(const gj_plan* plan, const gj_step_params* params, const
   A.cohort = cohort;
   A.cohort_value = cohort_value;
   A.err = err;
-  return gj::launch(gj::k_infector_scatter, gj::grid_for(A.n, gj::kLocBlocks, gj::kLocLoads * gj::kWave), gj::kThreads, 0,
-                    (hipStream_t)stream, A);
+  return gj::launch(gj::k_infector_scatter<false>, gj::grid_for(A.n, gj::kLocBlocks, gj::kLocLoads * gj::kWave),
+                    gj::kThreads, 0, (hipStream_t)stream, A);
 }
 
 int gj_infector_gather(const gj_plan* plan, const gj_step_params* params, const gj_location_rows* rows,
@@ -1847,12 +1852,14 @@ int gj_infector_gather(const gj_plan* plan, const gj_step_params* params, const 
   return gj::launch(gj::k_infector_gather<false>, blocks, gj::kThreads, 0, (hipStream_t)stream, A);
 }
 
-int gj_infector_clear(const gj_plan* plan, const gj_location_rows* rows, const float* new_infected, int64_t* const* U,
-                      void* stream) {
+// gj_infector_clear (n_groups == 0: U) and gj_infection_matrix_clear (UG, n_groups cells per column)
+static int infector_clear(const gj_plan* plan, const gj_location_rows* rows, const float* new_infected, int64_t* const* U,
+                          int32_t n_groups, void* stream) {
   const int rc = gj::check_plan(plan);
   if (rc) return rc;
   if (!new_infected || (plan->n_sets > 0 && (!rows || !U))) return GJ_E_NULL;
   gj::InfArgs A = {};
+  A.n_groups = n_groups;
   for (int s = 0; s < plan->n_sets; ++s) {
     const gj_edge_set& E = plan->sets[s];
     if (!rows[s].a_rowptr || !U[s] || E.n_venues == 0) continue;      // no rows or no U: nothing of this set to clear
@@ -1863,13 +1870,71 @@ int gj_infector_clear(const gj_plan* plan, const gj_location_rows* rows, const f
     S.n_edges = (int32_t)E.n_edges;
     S.n_venues = (int32_t)E.n_venues;
     S.stride = E.cum_stride;
-    S.U = (unsigned long long*)U[s];
+    (n_groups ? S.UG : S.U) = (unsigned long long*)U[s];
   }
   if (plan->n_agents == 0 || A.n_sets == 0) return GJ_OK;
   A.n = plan->n_agents;
   A.flag = new_infected;
-  return gj::launch(gj::k_infector_clear, gj::grid_for(A.n, gj::kLocBlocks, gj::kLocLoads * gj::kWave), gj::kThreads, 0,
-                    (hipStream_t)stream, A);
+  const int64_t blocks = gj::grid_for(A.n, gj::kLocBlocks, gj::kLocLoads * gj::kWave);
+  if (n_groups) return gj::launch(gj::k_infector_clear<true>, blocks, gj::kThreads, 0, (hipStream_t)stream, A);
+  return gj::launch(gj::k_infector_clear<false>, blocks, gj::kThreads, 0, (hipStream_t)stream, A);
+}
+
+int gj_infector_clear(const gj_plan* plan, const gj_location_rows* rows, const float* new_infected, int64_t* const* U,
+                      void* stream) {
+  return infector_clear(plan, rows, new_infected, U, 0, stream);
+}
+
+static int matrix_groups(const int32_t* group, int32_t n_groups) {
+  return (n_groups < 1 || n_groups > GJ_MATRIX_MAX_GROUPS || (!group && n_groups != 1)) ? GJ_E_RANGE : GJ_OK;
+}
+
+int gj_infection_matrix_scatter(const gj_plan* plan, const gj_step_params* params, const gj_location_rows* rows,
+                                const float* new_infected, const float* susceptibility0, const float* current_stage,
+                                const int32_t* group, int32_t n_groups, int64_t* const* UG,
+                                int64_t* unattributed_by_group, uint32_t* err, void* stream) {
+  gj::InfArgs A = {};
+  if (const int rc = infector_sets(plan, params, rows, nullptr, &A, UG, kInfUG)) return rc;
+  if (!new_infected || !susceptibility0 || !err) return GJ_E_NULL;
+  if (params->has_quarantine && !current_stage) return GJ_E_NULL;
+  if (const int rc = matrix_groups(group, n_groups)) return rc;
+  if (plan->n_agents == 0) return GJ_OK;
+  A.flag = new_infected;
+  A.s0 = susceptibility0;
+  A.stage = params->has_quarantine ? current_stage : nullptr;
+  A.group = group;
+  A.n_groups = n_groups;
+  A.unattributed = (unsigned long long*)unattributed_by_group;
+  A.err = err;
+  return gj::launch(gj::k_infector_scatter<true>, gj::grid_for(A.n, gj::kLocBlocks, gj::kLocLoads * gj::kWave),
+                    gj::kThreads, 0, (hipStream_t)stream, A);
+}
+
+int gj_infection_matrix_gather(const gj_plan* plan, const gj_step_params* params, const gj_location_rows* rows,
+                               const float* transmission, const float* current_stage, int64_t* const* U,
+                               int64_t* const* UG, const int32_t* group, int32_t n_groups, int64_t* out, uint32_t* err,
+                               void* stream) {
+  static_assert(GJ_MATRIX_MAX_GROUPS * GJ_MATRIX_MAX_GROUPS <= GJ_LOC_LDS_BINS, "the matrix fits the LDS histogram");
+  gj::InfArgs A = {};
+  if (const int rc = infector_sets(plan, params, rows, U, &A, UG, kInfU | kInfUG)) return rc;
+  if (!transmission || !out || !err) return GJ_E_NULL;
+  if (params->has_quarantine && !current_stage) return GJ_E_NULL;
+  if (const int rc = matrix_groups(group, n_groups)) return rc;
+  if (plan->n_agents == 0 || params->n_nets == 0) return GJ_OK;
+  A.flag = transmission;
+  A.stage = params->has_quarantine ? current_stage : nullptr;
+  A.group = group;
+  A.n_groups = n_groups;
+  A.out = (unsigned long long*)out;
+  A.err = err;
+  return gj::launch(gj::k_infector_gather<true, true>, gj::grid_for(A.n, gj::kLocBlocks, gj::kLocLoads * gj::kWave),
+                    gj::kThreads, (size_t)n_groups * n_groups * sizeof(unsigned long long), (hipStream_t)stream, A);
+}
+
+int gj_infection_matrix_clear(const gj_plan* plan, const gj_location_rows* rows, const float* new_infected,
+                              int64_t* const* UG, int32_t n_groups, void* stream) {
+  if (n_groups < 1 || n_groups > GJ_MATRIX_MAX_GROUPS) return plan ? GJ_E_RANGE : GJ_E_NULL;
+  return infector_clear(plan, rows, new_infected, UG, n_groups, stream);
 }
 
 int gj_step(const gj_plan* plan, const gj_agent_state* state, const gj_step_params* params, const gj_step_io* io,

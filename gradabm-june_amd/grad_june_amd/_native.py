@@ -31,6 +31,8 @@ GJ_STAGE_MAX_AGENTS = 1 << 40
 GJ_LOC_UNIT = 1 << 30
 GJ_LOC_ERR_LABEL, GJ_LOC_ERR_VALUE, GJ_LOC_ERR_ROWS = 1, 2, 4
 GJ_LOC_MAX_COLS, GJ_LOC_LDS_BINS, GJ_LOC_BLOCKS = 64, 4096, 2048
+# gj_infection_matrix_*: the largest labelling that gets a who-infects-whom matrix (G * G <= GJ_LOC_LDS_BINS)
+GJ_MATRIX_MAX_GROUPS = 64
 
 MASK_RAW, MASK_Q, MASK_QL, MASK_QL_AGE75 = 0, 1, 2, 3
 
@@ -299,6 +301,18 @@ SYMBOLS = {
          _vp, _vp, _vp],
     ),
     "gj_infector_clear": (C.c_int, [C.POINTER(Plan), C.POINTER(LocationRows), _vp, C.POINTER(_vp), _vp]),
+    "gj_infection_matrix_scatter": (
+        C.c_int,
+        [C.POINTER(Plan), C.POINTER(StepParams), C.POINTER(LocationRows), _vp, _vp, _vp, _vp, C.c_int32, C.POINTER(_vp),
+         _vp, _vp, _vp],
+    ),
+    "gj_infection_matrix_gather": (
+        C.c_int,
+        [C.POINTER(Plan), C.POINTER(StepParams), C.POINTER(LocationRows), _vp, _vp, C.POINTER(_vp), C.POINTER(_vp), _vp,
+         C.c_int32, _vp, _vp, _vp],
+    ),
+    "gj_infection_matrix_clear": (
+        C.c_int, [C.POINTER(Plan), C.POINTER(LocationRows), _vp, C.POINTER(_vp), C.c_int32, _vp]),
     "gj_step": (C.c_int, [C.POINTER(Plan), C.POINTER(AgentState), C.POINTER(StepParams), C.POINTER(StepIO), _vp]),
     "gj_step_phase": (
         C.c_int,

@@ -48,6 +48,9 @@ def encode_groups(agent, spec) -> Tuple[Dict[str, torch.Tensor], Dict[str, list]
     An attribute - strings or numbers - is encoded with ``np.unique(..., return_inverse=True)``: the columns are the
     sorted distinct values of the WHOLE world it is called on.  Integer labels of a dict are used as they are: they must
     lie in ``[0, G)`` with ``G = max + 1``, and a group without agents keeps its (zero) column.
+    A dict entry whose value is a mapping bins a numeric attribute instead - ``{age_band: {attribute: age, bins: [0, 18,
+    65, 100]}}``: the label is the band with ``lo <= value < hi``, the column keys are ``"0-18"``, ``"18-65"``, ... (the
+    naming of ``Vaccination``'s efficacy bands), and a band without agents keeps its column (:func:`bin_attribute`).
     Returns ``({name: int32 labels [n_agents]}, {name: list of column keys})``."""
     n = len(agent["id"])
     items: List[Tuple[str, object]] = []
@@ -68,7 +71,9 @@ def encode_groups(agent, spec) -> Tuple[Dict[str, torch.Tensor], Dict[str, list]
         check_group_name(name)
         if name in labels:
             raise ValueError(f"group '{name}' is given twice")
-        if given is None:
+        if isinstance(given, dict):
+            lab, key = bin_attribute(agent, name, given)
+        elif given is None:
             if name not in agent:
                 raise KeyError(f"groups: the world's agents have no attribute '{name}' "
                                f"(present: {sorted(k for k in agent.keys())})")
@@ -89,6 +94,35 @@ def encode_groups(agent, spec) -> Tuple[Dict[str, torch.Tensor], Dict[str, list]
         labels[name] = torch.from_numpy(np.ascontiguousarray(lab, dtype=np.int32))
         keys[name] = key
     return labels, keys
+
+
+def bin_attribute(agent, name, spec) -> Tuple[np.ndarray, List[str]]:
+    """The labelling ``name: {attribute: <agent attribute>, bins: [e0, e1, ...]}``: (labels, column keys).  Band i is
+    ``bins[i] <= value < bins[i + 1]`` and is called ``"<bins[i]>-<bins[i + 1]>"``.  The bins must increase strictly, and
+    every agent's value must lie in one of them: both are ``ValueError`` otherwise."""
+    unknown = set(spec) - {"attribute", "bins"}
+    if unknown or "attribute" not in spec or "bins" not in spec:
+        raise ValueError(f"group '{name}': a binned labelling is {{attribute: <name>, bins: [..]}}, not {dict(spec)!r}")
+    attribute, bins = spec["attribute"], spec["bins"]
+    if not isinstance(attribute, str) or attribute not in agent:
+        raise KeyError(f"group '{name}': the world's agents have no attribute '{attribute}' "
+                       f"(present: {sorted(k for k in agent.keys())})")
+    values = _as_numpy(agent[attribute])
+    n = len(agent["id"])
+    if values.ndim != 1 or values.shape[0] != n or values.dtype.kind not in "iuf":
+        raise ValueError(f"group '{name}': attribute '{attribute}' of shape {values.shape} and type {values.dtype}, "
+                         f"expected {n} numbers")
+    if isinstance(bins, (str, bytes)) or not hasattr(bins, "__len__") or len(bins) < 2:
+        raise ValueError(f"group '{name}': bins = {bins!r}, expected at least two edges")
+    edges = np.asarray(bins, dtype=np.float64)
+    if edges.ndim != 1 or not np.all(np.isfinite(edges)) or not np.all(np.diff(edges) > 0):
+        raise ValueError(f"group '{name}': bins {list(bins)} are not strictly increasing")
+    lab = np.digitize(values, edges) - 1                      # edges[i] <= value < edges[i + 1]
+    outside = (lab < 0) | (lab >= len(edges) - 1) | ~np.isfinite(values.astype(np.float64))
+    if outside.any():
+        raise ValueError(f"group '{name}': {int(outside.sum())} agents have a value of '{attribute}' outside every bin of "
+                         f"{list(bins)} (lo <= value < hi), e.g. {values[outside][:3].tolist()}")
+    return lab, [f"{lo}-{hi}" for lo, hi in zip(bins[:-1], bins[1:])]
 
 
 def attach_groups(agent, spec) -> None:
@@ -324,6 +358,19 @@ class LocationStats:
             raise LocationError(f"{what}: " + " and ".join(why))
 
 
+def infection_matrices_to_save(spec) -> List[str]:
+    """The YAML key ``infection_matrices_to_save`` / the Runner's ``matrices=``: a list of labelling names (absent: none)."""
+    if spec is None:
+        return []
+    if isinstance(spec, str):
+        spec = [spec]
+    if not isinstance(spec, (list, tuple)) or not all(isinstance(s, str) for s in spec):
+        raise ValueError(f"infection_matrices_to_save: expected a list of labelling names, not {spec!r}")
+    if len(set(spec)) != len(spec):
+        raise ValueError(f"infection_matrices_to_save: a labelling is given twice ({list(spec)})")
+    return list(spec)
+
+
 class InfectorError(RuntimeError):
     """gj_infector_scatter / gj_infector_gather met a label outside [0, n_groups), a new_infected that is neither 0 nor
     1, a NaN or negative term, a credit that is not finite, or a row outside its edge set."""
@@ -345,12 +392,22 @@ class InfectorStats:
     an agent was infected in, -1: never), the integer series ``out[key]`` [rows, n_groups] - units of 1 / GJ_LOC_UNIT of
     an infection, by the INFECTOR's group - and ``unattributed`` [rows] (exact counts), and the sticky error word.  ``U``,
     the per-venue units of one step, lives with the plan (``DevicePlan.infector_units``) and is zero between steps:
-    ``clear`` = "memset" zeroes all of it, "walk" only the venues the step's new infections touched."""
+    ``clear`` = "memset" zeroes all of it, "walk" only the venues the step's new infections touched.
 
-    def __init__(self, n_agents: int, labellings=None, device=None, n_rows: int = 1, clear: str = "memset"):
-        if clear not in ("memset", "walk"):
-            raise ValueError(f"clear = {clear!r}: 'memset' or 'walk'")
+    ``matrices``: the names of the labellings (a list, or a dict by name) that also get a who-infects-whom matrix
+    (``gj_infection_matrix_scatter`` / ``gj_infection_matrix_gather``): ``matrix[name]`` [rows, G, G] - the same units,
+    [infector's group, infected's group] - and ``unattributed_by[name]`` [rows, G] (exact counts, by the infected agent's
+    group).  A labelling of more than GJ_MATRIX_MAX_GROUPS groups cannot have one.  ``UG``, the units of one step by the
+    infected's group, lives with the plan too (``DevicePlan.infection_matrix_units``), G times the size of ``U``;
+    ``matrix_clear`` = "memset" or "walk" as for ``U``."""
+
+    def __init__(self, n_agents: int, labellings=None, device=None, n_rows: int = 1, clear: str = "memset",
+                 matrices=None, matrix_clear: str = "walk"):
+        for how in (clear, matrix_clear):
+            if how not in ("memset", "walk"):
+                raise ValueError(f"clear = {how!r}: 'memset' or 'walk'")
         self.n, self.device, self.clear_by = int(n_agents), torch.device(device), clear
+        self.matrix_clear_by = matrix_clear
         self.labels, self.n_groups = {None: None}, {None: 1}
         for name, (labels, n_groups) in (labellings or {}).items():
             if n_groups < 1 or n_groups > N.GJ_MAX_GROUPS:
@@ -359,6 +416,14 @@ class InfectorStats:
                 raise ValueError(f"{self.n} agents for {labels.numel()} labels of '{name}'")
             self.labels[name] = labels.detach().to(device=self.device, dtype=torch.int32).contiguous()
             self.n_groups[name] = int(n_groups)
+        self.matrix_names = list(matrices or ())
+        for name in self.matrix_names:
+            if name is None or name not in self.labels:
+                raise ValueError(f"infection matrix by '{name}': no such labelling (present: "
+                                 f"{sorted(k for k in self.labels if k is not None)})")
+            if self.n_groups[name] > N.GJ_MATRIX_MAX_GROUPS:
+                raise ValueError(f"infection matrix by '{name}': {self.n_groups[name]} groups, a matrix takes at most "
+                                 f"{N.GJ_MATRIX_MAX_GROUPS} (GJ_MATRIX_MAX_GROUPS)")
         self.err = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.reset(n_rows)
 
@@ -368,6 +433,10 @@ class InfectorStats:
         self.infected_row = torch.full((self.n,), -1, dtype=torch.int32, device=dev)
         self.unattributed = torch.zeros(int(n_rows), dtype=torch.int64, device=dev)
         self.out = {key: torch.zeros(int(n_rows), G, dtype=torch.int64, device=dev) for key, G in self.n_groups.items()}
+        groups = {name: self.n_groups[name] for name in self.matrix_names}
+        self.matrix = {name: torch.zeros(int(n_rows), G, G, dtype=torch.int64, device=dev) for name, G in groups.items()}
+        self.unattributed_by = {name: torch.zeros(int(n_rows), G, dtype=torch.int64, device=dev)
+                                for name, G in groups.items()}
 
     def _agents(self, *per_agent) -> None:
         for t in per_agent:
@@ -421,17 +490,81 @@ class InfectorStats:
             for u in U:
                 u.zero_()
 
+    def matrix_scatter(self, plan, params, new_infected, susceptibility0, current_stage, row: int = 0, edges=None) -> None:
+        """Pass 1 once more for every labelling with a matrix, into the plan's ``UG`` of that labelling (zero before);
+        unattributed_by[name][row] += the infections nobody transmitted, by the infected agent's group."""
+        import ctypes as C
+
+        if plan.host.n_agents != self.n:
+            raise ValueError(f"a plan of {plan.host.n_agents} agents for {self.n}")
+        self._agents(new_infected, susceptibility0, current_stage)
+        if not 0 <= row < self.unattributed.numel():
+            raise IndexError(f"row {row} of {self.unattributed.numel()}")
+        for name in self.matrix_names:
+            G = self.n_groups[name]
+            N.check(N.load().gj_infection_matrix_scatter(
+                C.byref(plan.c), C.byref(params), plan.location_rows(edges), N.ptr(new_infected), N.ptr(susceptibility0),
+                N.ptr(current_stage), N.ptr(self.labels[name]), G, plan.infection_matrix_units(name, G)[1],
+                N.ptr(self.unattributed_by[name][row]), N.ptr(self.err), N.current_stream()),
+                "gj_infection_matrix_scatter")
+
+    def matrix_gather(self, plan, params, transmission, current_stage, row: int = 0, edges=None) -> None:
+        """Pass 2 by pairs of groups: matrix[name][row] += the step's terms, for every labelling with a matrix.  Needs
+        the step's ``U`` (``scatter``) beside its ``UG``."""
+        import ctypes as C
+
+        n_ext = plan.host.n_ext_agents
+        if (transmission.numel() != n_ext or transmission.dtype != torch.float32 or not transmission.is_contiguous()
+                or transmission.device != self.device):
+            raise ValueError(f"transmission: contiguous float32[{n_ext}] on {self.device}")
+        self._agents(current_stage)
+        if not 0 <= row < self.unattributed.numel():
+            raise IndexError(f"row {row} of {self.unattributed.numel()}")
+        for name in self.matrix_names:
+            G = self.n_groups[name]
+            N.check(N.load().gj_infection_matrix_gather(
+                C.byref(plan.c), C.byref(params), plan.location_rows(edges), N.ptr(transmission), N.ptr(current_stage),
+                plan.infector_units()[1], plan.infection_matrix_units(name, G)[1], N.ptr(self.labels[name]), G,
+                N.ptr(self.matrix[name][row]), N.ptr(self.err), N.current_stream()), "gj_infection_matrix_gather")
+
+    def matrix_clear(self, plan, new_infected=None, edges=None) -> None:
+        """The plan's ``UG`` of every labelling with a matrix back to zero: all of it, or (``matrix_clear`` = "walk")
+        what the step of ``new_infected`` touched."""
+        import ctypes as C
+
+        for name in self.matrix_names:
+            G = self.n_groups[name]
+            UG, pointers = plan.infection_matrix_units(name, G)
+            if self.matrix_clear_by == "walk" and new_infected is not None:
+                N.check(N.load().gj_infection_matrix_clear(C.byref(plan.c), plan.location_rows(edges), N.ptr(new_infected),
+                                                           pointers, G, N.current_stream()), "gj_infection_matrix_clear")
+            else:
+                for u in UG:
+                    u.zero_()
+
     def record(self, plan, params, new_infected, susceptibility0, current_stage, transmission, row: int = 0,
                edges=None) -> None:
-        """One step: scatter, gather (a step with networks), clear."""
+        """One step: scatter, the matrix scatters, then (a step with networks) the gathers, the matrix gathers and the
+        clears."""
         self.scatter(plan, params, new_infected, susceptibility0, current_stage, row=row, edges=edges)
+        if self.matrix_names:
+            self.matrix_scatter(plan, params, new_infected, susceptibility0, current_stage, row=row, edges=edges)
         if params.n_nets > 0:
             self.gather(plan, params, transmission, current_stage, row=row, edges=edges)
+            if self.matrix_names:
+                self.matrix_gather(plan, params, transmission, current_stage, row=row, edges=edges)
             self.clear(plan, new_infected, edges=edges)
+            if self.matrix_names:
+                self.matrix_clear(plan, new_infected, edges=edges)
 
     def values(self, key=None, n_rows=None) -> torch.Tensor:
         """A series in infections: out / GJ_LOC_UNIT formed in fp64, then float32 [rows, n_groups]."""
         out = self.out[key] if n_rows is None else self.out[key][:n_rows]
+        return (out.to(torch.float64) / float(N.GJ_LOC_UNIT)).to(torch.float32)
+
+    def matrix_values(self, name, n_rows=None) -> torch.Tensor:
+        """A matrix series in infections, formed as ``values`` forms its: float32 [rows, G (infector), G (infected)]."""
+        out = self.matrix[name] if n_rows is None else self.matrix[name][:n_rows]
         return (out.to(torch.float64) / float(N.GJ_LOC_UNIT)).to(torch.float32)
 
     def reproduction(self, n_rows: int, key=None) -> torch.Tensor:

@@ -734,6 +734,22 @@ class DevicePlan:
             self._infector_units = (U, pointers)
         return self._infector_units
 
+    def infection_matrix_units(self, name, G: int):
+        """``(UG, pointers)`` of ``gj_infection_matrix_scatter`` / ``gj_infection_matrix_gather`` for the labelling
+        ``name`` of ``G`` groups: one zeroed int64 tensor [n_venues, cum_stride, G] per edge set - G times the memory of
+        ``infector_units()`` - allocated on first use and kept with the plan per labelling (only the infection matrices
+        ask for it)."""
+        if not 1 <= int(G) <= N.GJ_MATRIX_MAX_GROUPS:
+            raise ValueError(f"infection matrix by '{name}': {G} groups, expected 1 .. {N.GJ_MATRIX_MAX_GROUPS}")
+        held = getattr(self, "_infection_matrix_units", None)
+        if held is None:
+            held = self._infection_matrix_units = {}
+        if name not in held or held[name][0][0].shape[-1] != int(G):
+            UG = [torch.zeros(max(1, s.n_venues), int(self.c.sets[i].cum_stride), int(G), dtype=torch.int64,
+                              device=self.device) for i, s in enumerate(self.host.sets)]
+            held[name] = (UG, (C.c_void_p * N.GJ_MAX_SETS)(*[u.data_ptr() for u in UG]))
+        return held[name]
+
     def bytes_resident(self) -> int:
         n = 0
         for t in self.keep:

@@ -50,10 +50,12 @@ def world_from_npz(path) -> HeteroData:
 
 class Runner(torch.nn.Module):
     def __init__(self, model, data, timer, log_fraction_initial_cases, save_path, parameters,
-                 age_bins=(0, 18, 65, 100), groups=None, seed_group=None, stages=None, locations=None, infectors=None):
+                 age_bins=(0, 18, 65, 100), groups=None, seed_group=None, stages=None, locations=None, infectors=None,
+                 matrices=None):
         super().__init__()
         self._refuse_locations(locations)
         self._refuse_infectors(infectors)
+        self._refuse_matrices(matrices)
         self.model = model
         self.data = data
         self.data_backup = self.backup_infection_data(data)
@@ -102,6 +104,10 @@ class Runner(torch.nn.Module):
 
         self.infectors_saved = infectors_to_save(infectors)
         self._infector_stats = None
+        # who-infects-whom matrices (not in the reference): ``matrices=[name, ...]`` (the YAML key
+        # ``infection_matrices_to_save``): for each of these labellings the infector series by PAIRS of groups - a step's
+        # infections caused by group g in group g' - and the unattributed infections by the infected agent's group
+        self.matrices_saved = self._check_matrices(matrices)
         self.restore_initial_data()
 
     _supports_locations = True
@@ -120,6 +126,35 @@ class Runner(torch.nn.Module):
 
         if infectors_to_save(spec) and not cls._supports_locations:      # a halo infector's credit belongs to another rank
             raise NotImplementedError("infectors_to_save: the infector series is not available in a partitioned run")
+
+    @classmethod
+    def _refuse_matrices(cls, spec):
+        from .groups import infection_matrices_to_save
+
+        if infection_matrices_to_save(spec) and not cls._supports_locations:      # they are sums of the infector series' terms
+            raise NotImplementedError("infection_matrices_to_save: the infection matrices are not available in a "
+                                      "partitioned run")
+
+    def _check_matrices(self, spec):
+        """The labellings that get an infection matrix: each a labelling with result series (``groups_to_save``) of at
+        most GJ_MATRIX_MAX_GROUPS groups, and only next to the infector series."""
+        from . import _native as N
+        from .groups import infection_matrices_to_save
+
+        names = infection_matrices_to_save(spec)
+        if names and not self.infectors_saved:
+            raise ValueError("infection_matrices_to_save needs infectors_to_save: true (the matrices are the infector "
+                             "series by pairs of groups)")
+        skip = self.data["agent"].get("groups_without_series", None) or []
+        for name in names:
+            if name not in self.group_keys or name in skip:
+                raise ValueError(f"infection_matrices_to_save: '{name}' is no labelling of groups_to_save (present: "
+                                 f"{sorted(k for k in self.group_keys if k not in skip)})")
+            if len(self.group_keys[name]) > N.GJ_MATRIX_MAX_GROUPS:
+                raise ValueError(f"infection_matrices_to_save: '{name}' has {len(self.group_keys[name])} groups, a matrix "
+                                 f"takes at most {N.GJ_MATRIX_MAX_GROUPS}; bin the attribute (groups_to_save: "
+                                 f"[{{<name>: {{attribute: {name}, bins: [..]}}}}])")
+        return names
 
     @classmethod
     def from_file(cls, fpath=None):
@@ -146,6 +181,7 @@ class Runner(torch.nn.Module):
             stages=params.get("stages_to_save"),
             locations=params.get("locations_to_save"),
             infectors=params.get("infectors_to_save"),
+            matrices=params.get("infection_matrices_to_save"),
         )
 
     @staticmethod
@@ -392,7 +428,7 @@ class Runner(torch.nn.Module):
 
             self._infector_stats = InfectorStats(
                 self.n_agents, {name: (st.labels, st.n_groups) for name, st in self._groups().items()},
-                device=require_hip(self.device))
+                device=require_hip(self.device), matrices=self.matrices_saved)
         return self._infector_stats
 
     # vaccination series: the launches' own counts, and one gj_group_stats pass per labelling on a launch's mask ----------
@@ -569,6 +605,9 @@ class Runner(torch.nn.Module):
             for name in groups:
                 results[f"infections_caused_by_{name}"] = infectors.values(name, T)
                 results[f"reproduction_number_by_{name}"] = infectors.reproduction(T, name)
+            for name in self.matrices_saved:      # [t, infector's group, infected's group]; the counts are exact
+                results[f"infection_matrix_by_{name}"] = infectors.matrix_values(name, T)
+                results[f"infections_unattributed_by_{name}"] = infectors.unattributed_by[name][:T].to(torch.float64)
             caused, infected_row = infectors.caused, infectors.infected_row
             if "original_index" in data["agent"]:      # per agent, in the file's order like is_infected below
                 index = data["agent"].original_index.to(caused.device)
@@ -642,10 +681,18 @@ class Runner(torch.nn.Module):
             for name, keys in self.group_keys.items():
                 if f"infections_caused_by_{name}" not in results:
                     continue
-                pd.DataFrame({"date": np.repeat(dates, len(keys)), name: np.tile(keys, len(dates)),
-                              "infections_caused": results[f"infections_caused_by_{name}"].detach().cpu().numpy().reshape(-1),
-                              "reproduction_number": results[f"reproduction_number_by_{name}"].detach().cpu().numpy().reshape(-1)}
+                flat = lambda key: results[key].detach().cpu().numpy().reshape(-1)
+                cols = {"infections_caused": flat(f"infections_caused_by_{name}"),
+                        "reproduction_number": flat(f"reproduction_number_by_{name}")}
+                if f"infections_unattributed_by_{name}" in results:      # (a labelling with an infection matrix)
+                    cols["infections_unattributed"] = flat(f"infections_unattributed_by_{name}")
+                pd.DataFrame({"date": np.repeat(dates, len(keys)), name: np.tile(keys, len(dates)), **cols}
                              ).to_csv(self.save_path / f"results_infectors_by_{name}.csv", index=False)
+                if f"infection_matrix_by_{name}" in results:      # long format: date, infector, infected, infections
+                    G = len(keys)
+                    pd.DataFrame({"date": np.repeat(dates, G * G), "infector": np.tile(np.repeat(np.asarray(keys), G), len(dates)),
+                                  "infected": np.tile(keys, len(dates) * G), "infections": flat(f"infection_matrix_by_{name}")}
+                                 ).to_csv(self.save_path / f"results_infection_matrix_by_{name}.csv", index=False)
         pd.DataFrame({"is_infected": is_infected.detach().cpu().numpy()}).to_csv(
             self.save_path / "results_is_infected.csv")
 

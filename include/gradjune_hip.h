@@ -606,6 +606,54 @@ int gj_infector_gather(const gj_plan* plan, const gj_step_params* params, const 
 int gj_infector_clear(const gj_plan* plan, const gj_location_rows* rows /* [plan->n_sets] */, const float* new_infected,
                       int64_t* const* U /* host [plan->n_sets] */, void* stream);
 
+/* ---- row f2 by pairs of groups: who infects whom ------------------------------------------------------------------------
+ * A pure addition to ABI 7: the two passes above with the units kept apart by the group of the INFECTED agent, so that
+ * pass 2 is a sum over pairs of groups.  G = n_groups <= GJ_MATRIX_MAX_GROUPS, so that G * G <= GJ_LOC_LDS_BINS.
+ * UG[s]: device int64 [n_venues][cum_stride][G] per set, HOST array [plan->n_sets] of device pointers, all zero before
+ * pass 1.  It sits beside U, which keeps its layout and its meaning; a step runs both scatters, from the same inputs.
+ *
+ * gj_infection_matrix_scatter: gj_infector_scatter's rule - the same kernel body: t_i, T, t_{i,e}, floors, remainder and
+ * tie-break - with every u added to UG[s_i][v_e][k_i][group[a]] (64-bit integer atomics).  After both scatters of a step
+ * the sum over g' of UG[s][v][k][g'] therefore equals U[s][v][k] exactly, in every cell.  An infection nobody
+ * transmitted adds 1 to unattributed_by_group[group[a]] (device int64 [G], the call ADDS; may be NULL).  No cohort is
+ * written and U is not touched.  n_nets == 0 is valid as for gj_infector_scatter (the seeding step): every infection is
+ * counted in unattributed_by_group, UG may be NULL.
+ *
+ * gj_infection_matrix_gather: gj_infector_gather's walk, both forms of it.  For every agent b with transmission[b] > 0
+ * and every edge of its rows where U[s_i][v_e][k_i] != 0 (read first; only there the G cells of UG are read), for every
+ * g' with UG[s_i][v_e][k_i][g'] != 0, in fp64 and in the order of gj_infector_gather's term:
+ *   out[group[b]][g'] += llrint(UG / GJ_LOC_UNIT * (beta_i * pc[v_e]) * (m_i[b] * transmission[b]) / cum * GJ_LOC_UNIT)
+ * out: device int64 [G][G], [infector's group][infected's group]; the call ADDS.  Every term is rounded on its own - a
+ * chain of correctly rounded fp64 products and quotients, then one round-to-nearest-even - and the sums are integers
+ * (an LDS histogram of G * G bins, one global 64-bit atomic per non-zero bin at the end), so out is independent of the
+ * order of the agents, of the workgroups and of which form of the walk took a round.  Against gj_infector_gather's
+ * out[g] on the same inputs the row sum over g' differs by the roundings alone: half a unit per non-zero term of the
+ * group's agents and half a unit per infectious agent of the group.  n_nets == 0 launches nothing.
+ *
+ * gj_infection_matrix_clear: UG back to zero by gj_infector_clear's walk: plain stores of 0 to the cum_stride * G cells
+ * of every venue that the rows of the agents with new_infected != 0 name.
+ *
+ * All three: rows, launch shape and bad input as for the three above - a label outside [0, G) skips its agent (in the
+ * scatter too: the infected agent's) and sets GJ_LOC_ERR_LABEL; a cum that is not finite or <= 0 where U != 0, or a term
+ * that is not finite, skips the pair and sets GJ_LOC_ERR_VALUE; rows outside the set set GJ_LOC_ERR_ROWS.  n_agents == 0
+ * launches nothing.  Errors, returned before any device work: as above, with GJ_E_NULL for a NULL UG (n_nets > 0) or
+ * UG[s] of a set with rows, venues and an active network, and for a NULL out; GJ_E_RANGE for n_groups outside
+ * 1..GJ_MATRIX_MAX_GROUPS or group == NULL with n_groups != 1.                                                        */
+#define GJ_MATRIX_MAX_GROUPS 64
+int gj_infection_matrix_scatter(const gj_plan* plan, const gj_step_params* params,
+                                const gj_location_rows* rows /* [plan->n_sets] */, const float* new_infected,
+                                const float* susceptibility0, const float* current_stage, const int32_t* group,
+                                int32_t n_groups, int64_t* const* UG /* host [plan->n_sets] */,
+                                int64_t* unattributed_by_group, uint32_t* err, void* stream);
+int gj_infection_matrix_gather(const gj_plan* plan, const gj_step_params* params,
+                               const gj_location_rows* rows /* [plan->n_sets] */, const float* transmission,
+                               const float* current_stage, int64_t* const* U /* host [plan->n_sets] */,
+                               int64_t* const* UG /* host [plan->n_sets] */, const int32_t* group, int32_t n_groups,
+                               int64_t* out, uint32_t* err, void* stream);
+int gj_infection_matrix_clear(const gj_plan* plan, const gj_location_rows* rows /* [plan->n_sets] */,
+                              const float* new_infected, int64_t* const* UG /* host [plan->n_sets] */, int32_t n_groups,
+                              void* stream);
+
 /* ---- row f3: adjoint (backward) of one hot-path step, forward-only kernels reused ---------------
  * The aggregation ts = susc * sum_n w_n * (M_n^T diag(beta_n p_contact) M_n)(m_n * transmission) is
  * self-adjoint up to the exchange of the masks m_n <-> w_n, so its backward is the same four tiled
