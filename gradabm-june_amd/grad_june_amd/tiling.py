@@ -423,8 +423,12 @@ def finish_run_form(rf: RunForm, blk_v0: np.ndarray, n_agents: int, slice_agents
 # 10^3-10^4 venues against 10^7 agents), pass 2 needs no per-edge workspace at all: phase C is skipped and
 # phase D, after the tiled sets are accumulated, loads the set's cum into LDS and every lane adds up the
 # venues of ITS agents from an ELL table (K 16-bit venue ids per agent, 0xFFFF = none).  Per edge that is
-# ~2*K/deg bytes of indices instead of 12.5 (C: e_lv + val write, D: a_la + val read + descriptors), no LDS
-# atomics, and the sum of an agent is taken in its COO edge order.
+# ~2*K/deg bytes of indices instead of 12.5 (C: e_lv + val write, D: a_la + val read + descriptors), and no LDS
+# atomics.  The sum of an agent is taken in fp32 in the order of phase D's work items, NOT in its COO edge order:
+# (direct set in launch order, venue group, plane), each item adding the fp32 sum of its pair of entries - so an agent's
+# two entries of one plane fall into different items when their venues lie in different groups, and the venue-group
+# size (the launch layer's LDS rule; the test knob direct_table_floats) can change the last bit of a sum.
+# tests/gj_pass2_ref.py restates that order; tests/test_gpu_pass2_kernels.py holds the device to it bit for bit.
 DIRECT_MAX_VENUES = 65534     # venue ids are 16-bit, 0xFFFF = pad
 DIRECT_MAX_K = 8              # ELL columns (a power of two: one 2/4/8/16-byte load per agent)
 DIRECT_TABLE_GROUPS = 4       # the venues' cum may be staged through LDS in at most this many groups
@@ -495,28 +499,33 @@ def ell_rows(ell) -> np.ndarray:
 def emulate_direct_pass2(ell: np.ndarray, cum: np.ndarray, n_agents: int, weights: Optional[np.ndarray] = None,
                          agent_class: Optional[np.ndarray] = None, group_venues: Optional[int] = None):
     """Phase D's direct form: acc[a] = sum over the agent's ELL entries of cum[v] (x weights[k][class[a]] summed
-    over the set's networks k when ``cum`` is [V, nk]), venue groups of ``group_venues`` in turn, fp32."""
+    over the set's networks k when ``cum`` is [V, nk]), fp32, in the order of the kernel's work items: venue groups of
+    ``group_venues`` in turn and, within a group, one item per plane (pair of columns) - an item adds the sum of its
+    pair to acc.  The device is held to this order bit for bit by tests/test_gpu_pass2_kernels.py (through the
+    restatement tests/gj_pass2_ref.py, which tests/test_pass2_ref.py compares with this function)."""
     if ell.ndim == 3:
         ell = ell_rows(ell)
     cum = np.asarray(cum, dtype=np.float32)
     cum2 = cum.reshape(len(cum), -1)
     V, nk = cum2.shape
     gv = group_venues or max(1, V)
+    K = ell.shape[1]
     acc = np.zeros(n_agents, dtype=np.float32)
     for v0 in range(0, max(V, 1), gv):
-        s = np.zeros(n_agents, dtype=np.float32)              # one lane's sum over its agent's entries in this group
-        for c in range(ell.shape[1]):
-            lv = ell[:n_agents, c].astype(np.int64)
-            ok = (lv != 0xFFFF) & (lv >= v0) & (lv < v0 + gv)
-            idx = np.where(ok, lv, 0)
-            if weights is None:
-                term = cum2[idx, 0]
-            else:
-                term = np.zeros(n_agents, dtype=np.float32)
-                for k in range(nk):
-                    term = term + weights[k][agent_class[:n_agents]] * cum2[idx, k]
-            s = s + np.where(ok, term, np.float32(0)).astype(np.float32)
-        acc = acc + s
+        for c0 in range(0, K, 2):
+            s = np.zeros(n_agents, dtype=np.float32)          # one lane's sum over its agent's pair of entries
+            for c in range(c0, min(c0 + 2, K)):
+                lv = ell[:n_agents, c].astype(np.int64)
+                ok = (lv != 0xFFFF) & (lv >= v0) & (lv < v0 + gv)
+                idx = np.where(ok, lv, 0)
+                if weights is None:
+                    term = cum2[idx, 0]
+                else:
+                    term = np.zeros(n_agents, dtype=np.float32)
+                    for k in range(nk):
+                        term = term + weights[k][agent_class[:n_agents]] * cum2[idx, k]
+                s = s + np.where(ok, term, np.float32(0)).astype(np.float32)
+            acc = acc + s
     return acc
 
 
