@@ -21,6 +21,11 @@ ranks / is large goes the *partial-sum* way - and only those venues are in the a
 kinds is cut in two (the "split" form: ``<set>`` keeps the local + halo venues, ``<set>~big`` the partial-sum ones);
 the per-set rule of rounds 1-3 (``mode_of``) remains as ``GJ_EXCHANGE_RULE=set`` for comparison.
 
+The rules that cut a world into ranks (``classify_venues``, ``order_halo``, ``RankPartitioner``) are each stated once,
+in torch ops that run where their inputs live: numpy arrays are viewed as CPU tensors (``torch.from_numpy`` semantics,
+no copy) and handed back as numpy arrays, device tensors stay on their device.  ``tests/gj_partition_ref.py`` restates
+the partition of one rank in plain Python loops; the tests compare the two array for array.
+
 Per step:  transmission -> [all_to_all halo] -> phase A, phase B -> [all_reduce partial sums]
            -> phase C, phase D.   Pass 2 and the epilogue are purely local.
 Sampling noise is Philox keyed by the GLOBAL agent id, so results do not depend on the partition.
@@ -35,7 +40,7 @@ import numpy as np
 import torch
 
 from . import tiling as TL
-from .plan import SPLIT_SUFFIX
+from .plan import SPLIT_SUFFIX, _host
 
 HALO_MAX_MEAN_DEGREE = 8.0     # sets whose venues average more attendees use partial sums
 SPLIT_MIN_WEIGHTED_SIZE = 64.0  # venue size seen by the average EDGE of a small-mean set above which the set is split
@@ -50,7 +55,12 @@ MIN_SPLIT_HALO_SHARE = 0.05      # ... and at least this share of the halo float
 MIN_SPLIT_VENUE_SHARE = 0.10     # ... and takes at least this share of the set's venues out of the all-reduce
 
 
-def classify_venues(agent: np.ndarray, venue: np.ndarray, n_venues: int, bounds: np.ndarray, nets_on_set: int = 1,
+def _tensor(a) -> torch.Tensor:
+    """A tensor as it is, anything else as a CPU tensor over the same memory (no copy of a numpy array)."""
+    return a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))
+
+
+def classify_venues(agent, venue, n_venues: int, bounds: np.ndarray, nets_on_set: int = 1,
                     factor: float = PARTIAL_COST_FACTOR):
     """Exchange class of every venue of one edge set, from the venue's own attendee list (global data: every rank
     computes the same answer).  With n attendees living on T ranks:
@@ -62,22 +72,19 @@ def classify_venues(agent: np.ndarray, venue: np.ndarray, n_venues: int, bounds:
                              HALO_MAX_MEAN_DEGREE (8) attendees -, else *partial-sum*.
 
     A boundary household is a halo venue, a school with one pupil from the next rank or a 50 000-attendee venue a
-    partial-sum one.  Returns (partial[V] bool, n[V], T[V])."""
+    partial-sum one.  Computed where ``agent`` lives (a streamed 1e8-agent world never leaves the device).  Returns
+    (partial[V] bool, n[V], T[V]): numpy arrays for numpy input, tensors on the input's device otherwise."""
+    as_numpy = not isinstance(agent, torch.Tensor)
+    agent, venue = _tensor(agent).to(torch.int64), _tensor(venue).to(torch.int64)
     R = len(bounds) - 1
-    if isinstance(agent, torch.Tensor):          # the same on the device (a streamed 1e8-agent world never leaves it)
-        b = torch.as_tensor(np.asarray(bounds), device=agent.device)
-        owner = torch.searchsorted(b, agent, right=True) - 1
-        cnt = torch.bincount(venue * R + owner, minlength=n_venues * R).view(n_venues, R)
-        n = cnt.sum(1)
-        T = (cnt > 0).sum(1)
-        del cnt, owner
-        return (n > HALO_MAX_MEAN_DEGREE) & (n * (T - 1) > factor * 2.0 * max(1, nets_on_set) * (R - 1)), n, T
-    owner = np.searchsorted(bounds, agent, side="right") - 1
-    cnt = np.bincount(venue * R + owner, minlength=n_venues * R).reshape(n_venues, R)
+    b = torch.as_tensor(np.asarray(bounds), device=agent.device)
+    owner = torch.searchsorted(b, agent, right=True) - 1
+    cnt = torch.bincount(venue * R + owner, minlength=n_venues * R).view(n_venues, R)
     n = cnt.sum(1)
     T = (cnt > 0).sum(1)
-    del cnt
-    return (n > HALO_MAX_MEAN_DEGREE) & (n * (T - 1) > factor * 2.0 * max(1, nets_on_set) * (R - 1)), n, T
+    del cnt, owner
+    out = (n > HALO_MAX_MEAN_DEGREE) & (n * (T - 1) > factor * 2.0 * max(1, nets_on_set) * (R - 1)), n, T
+    return tuple(x.numpy() for x in out) if as_numpy else out
 
 
 def reduce_groups(floats: Dict[str, int], min_floats: int = 1 << 16) -> List[List[str]]:
@@ -170,17 +177,15 @@ def order_halo(lists, bounds, device=None):
     (first halo set that needs the agent, its venue there, id).  A halo agent has ~1 halo edge; in id order the halo
     slices' tiles hold a handful of edges each (a rank's C5 share spent a third of its step scattering them); in this
     order the agents a venue block needs are neighbours, so a halo slice meets few venue blocks and its tiles are long.
-    Returns (ids, owner) as numpy arrays, or as torch tensors when the lists hold tensors."""
-    on_torch = bool(lists) and isinstance(lists[0][0], torch.Tensor)
+    Returns (ids, owner) as tensors where the lists' tensors live (no lists: on ``device``), or as numpy arrays when the
+    lists hold numpy arrays (no lists: when ``device`` is None)."""
+    as_numpy = isinstance(lists[0][0], np.ndarray) if lists else device is None
     if not lists:
-        if device is not None:
-            z = torch.zeros(0, dtype=torch.int64, device=device)
-            return z, z.clone()
-        return np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)
-    if on_torch:
-        ids = torch.cat([a for a, _ in lists])
-        ven = torch.cat([v for _, v in lists])
-        si = torch.cat([torch.full((a.numel(),), i, dtype=torch.int64, device=a.device) for i, (a, _) in enumerate(lists)])
+        ids, owner = (torch.zeros(0, dtype=torch.int64, device=device) for _ in range(2))
+    else:
+        ids = torch.cat([_tensor(a) for a, _ in lists])
+        ven = torch.cat([_tensor(v) for _, v in lists])
+        si = torch.cat([torch.full((len(a),), i, dtype=torch.int64, device=ids.device) for i, (a, _) in enumerate(lists)])
         o = _lexsort_torch((si, ids))
         ids, ven, si = ids[o], ven[o], si[o]
         first = torch.ones(ids.numel(), dtype=torch.bool, device=ids.device)
@@ -190,27 +195,15 @@ def order_halo(lists, bounds, device=None):
         if HALO_ORDER == "venue":
             o = _lexsort_torch((ids, ven, si, owner))
             ids, owner = ids[o], owner[o]
-        return ids, owner
-    ids = np.concatenate([a for a, _ in lists])
-    ven = np.concatenate([v for _, v in lists])
-    si = np.concatenate([np.full(len(a), i, dtype=np.int64) for i, (a, _) in enumerate(lists)])
-    o = np.lexsort((si, ids))
-    ids, ven, si = ids[o], ven[o], si[o]
-    first = np.ones(len(ids), dtype=bool)
-    first[1:] = ids[1:] != ids[:-1]
-    ids, ven, si = ids[first], ven[first], si[first]
-    owner = np.searchsorted(bounds, ids, side="right") - 1
-    if HALO_ORDER == "venue":
-        o = np.lexsort((ids, ven, si, owner))
-        ids, owner = ids[o], owner[o]
-    return ids, owner
+    return (ids.numpy(), owner.numpy()) if as_numpy else (ids, owner)
 
 
 class RankPartitioner:
     """Cuts a world into the parts of one or several ranks, ONE EDGE SET AT A TIME: a set's global COO is needed
     only while ``add_set`` runs, so a rank never holds more than one set of the whole world (a 10^8-agent world
-    is ~14 GB of COO; ``bench.py --gpus N`` streams it set by set out of the generator) and a single process that
-    wants every rank's part (``PartitionedHotPath``) sorts each set once instead of scanning it once per rank."""
+    is ~14 GB of COO; ``bench.py --gpus N`` streams it set by set out of the generator).  Every rule is stated once,
+    in torch ops that run where the inputs live: numpy arrays are viewed as CPU tensors on the way in and handed back
+    as numpy arrays, device tensors never leave their device."""
 
     def __init__(self, n_agents: int, world_size: int, ranks: Optional[Sequence[int]] = None,
                  modes: Optional[Dict[str, str]] = None, networks: Optional[Sequence[str]] = None,
@@ -241,23 +234,20 @@ class RankPartitioner:
         self.total_edges = 0
         self.sizes: Dict[str, tuple] = {}          # global (edges, venues) per set
         self.classes: Dict[str, dict] = {}         # per set: venues by exchange class (global counts; reporting)
+        self._as_numpy, self._device = True, torch.device("cpu")   # what add_set was given, and where it lives
 
     def add_set(self, name: str, agent, venue, people) -> str:
-        """``agent`` / ``venue`` / ``people``: numpy arrays, or torch tensors (any device) - the part is then cut out with
-        torch ops where the tensors live and the rank world's edge lists stay there (``compile_plan(device=...)``)."""
-        on_torch = isinstance(agent, torch.Tensor)
-        if on_torch:
-            agent, venue = agent.to(torch.int64).reshape(-1), venue.to(torch.int64).reshape(-1)
-            people = torch.as_tensor(people, device=agent.device)
-        else:
-            agent = np.asarray(agent, dtype=np.int64).ravel()
-            venue = np.asarray(venue, dtype=np.int64).ravel()
-            people = np.asarray(people)
+        """``agent`` / ``venue`` / ``people``: numpy arrays, or torch tensors (any device).  The part is cut out with
+        torch ops where the inputs live - numpy arrays are viewed as CPU tensors, not copied - and the rank world's edge
+        lists come back as what went in: numpy arrays, or tensors that stay on their device (``compile_plan(device=...)``)."""
+        self._as_numpy = not isinstance(agent, torch.Tensor)
+        agent, venue = _tensor(agent).to(torch.int64).reshape(-1), _tensor(venue).to(torch.int64).reshape(-1)
+        people = _tensor(people).to(agent.device)
+        self._device = agent.device
         mode = self.mode_override.get(name)
         big = None
         if mode is None and (EXCHANGE_RULE == "set" or self.world_size == 1):
-            mode = mode_of(len(agent), len(people), self.world_size,
-                           people.cpu().numpy() if on_torch and self.world_size > 1 else (None if on_torch else people))
+            mode = mode_of(len(agent), len(people), self.world_size, people.cpu().numpy())
         elif mode is None:
             mode, big = self._mode_by_venue(name, agent, venue, len(people))
         self.total_edges += len(agent)
@@ -272,13 +262,10 @@ class RankPartitioner:
             # forced / per-set form of rounds 2-3 cuts by size: venues of up to HALO_MAX_MEAN_DEGREE attendees are halo.)
             if big is None:
                 big = people > HALO_MAX_MEAN_DEGREE
-            if on_torch and not isinstance(big, torch.Tensor):
-                big = torch.as_tensor(big, device=agent.device)
             e_big = big[venue]
-            xp = torch if on_torch else np
             for part, sel_v, sel_e, m in ((name, ~big, ~e_big, "halo"), (name + SPLIT_SUFFIX, big, e_big, "partial")):
-                remap = xp.cumsum(sel_v, 0) - 1
-                ids = torch.nonzero(sel_v).reshape(-1) if on_torch else np.flatnonzero(sel_v)
+                remap = torch.cumsum(sel_v, 0) - 1
+                ids = torch.nonzero(sel_v).reshape(-1)
                 self._add_part(part, agent[sel_e], remap[venue[sel_e]], people[sel_v], m, ids)
             return mode
         self._add_part(name, agent, venue, people, mode)
@@ -332,49 +319,13 @@ class RankPartitioner:
                       f"{self._n_sets_added} sets and {self._n_nets} networks so far) - runs in {mode} mode")
         return mode
 
-    def _add_part(self, name: str, agent: np.ndarray, venue: np.ndarray, people: np.ndarray, mode: str,
-                  part_venues: Optional[np.ndarray] = None) -> None:
+    def _add_part(self, name: str, agent: torch.Tensor, venue: torch.Tensor, people: torch.Tensor, mode: str,
+                  part_venues: Optional[torch.Tensor] = None) -> None:
         """``part_venues``: the set's venue ids of this part's venues (a split set's half has a numbering of its own);
-        ``venue_global`` then maps a rank's local venues to ids of the WHOLE set."""
+        ``venue_global`` then maps a rank's local venues to ids of the WHOLE set.  The part's ``people`` and
+        ``venue_global`` go to the host (the graph compile takes p_contact from there), everything per edge stays where
+        it is."""
         self.modes[name] = mode
-        b = self.bounds
-        if isinstance(agent, torch.Tensor):
-            return self._add_part_torch(name, agent, venue, people, mode, part_venues)
-        if len(self.ranks) > 2:
-            # every rank's own edges with one stable sort by owner (COO order kept inside a rank)
-            owner = np.searchsorted(b, agent, side="right") - 1
-            order = np.argsort(owner, kind="stable")
-            cut = np.searchsorted(owner[order], np.arange(self.world_size + 1))
-            mine_idx = {r: order[cut[r]:cut[r + 1]] for r in self.ranks}
-            del owner, order
-        else:
-            mine_idx = {r: np.flatnonzero((agent >= b[r]) & (agent < b[r + 1])) for r in self.ranks}
-        for r in self.ranks:
-            idx = mine_idx[r]
-            if mode in ("partial", "local"):
-                self.local_sets[r][name] = {"agent_global": agent[idx], "venue": venue[idx], "people": people}
-                self.venue_global[r][name] = part_venues
-                continue
-            touched = np.zeros(len(people), dtype=bool)
-            touched[venue[idx]] = True
-            keep = np.flatnonzero(touched[venue])          # every edge of a touched venue, local or remote, COO order
-            vg = np.flatnonzero(touched)
-            remap = np.full(len(people), -1, dtype=np.int64)
-            remap[vg] = np.arange(len(vg))
-            ag = agent[keep]
-            self.local_sets[r][name] = {"agent_global": ag, "venue": remap[venue[keep]], "people": people[vg]}
-            self.venue_global[r][name] = vg if part_venues is None else part_venues[vg]
-            rem = (ag < b[r]) | (ag >= b[r + 1])
-            ra, rv = ag[rem], self.local_sets[r][name]["venue"][rem]
-            o = np.lexsort((rv, ra))                               # per remote attendee: its smallest local venue of this part
-            ra, rv = ra[o], rv[o]
-            first = np.ones(len(ra), dtype=bool)
-            first[1:] = ra[1:] != ra[:-1]
-            self.halo_lists[r].append((ra[first], rv[first]))
-
-    def _add_part_torch(self, name, agent, venue, people, mode, part_venues) -> None:
-        """``_add_part`` with torch ops on the tensors' device; the part's ``people`` go to the host (the graph
-        compile takes p_contact from there), everything per edge stays."""
         b = self.bounds
         V = int(people.numel())
         for r in self.ranks:
@@ -395,80 +346,25 @@ class RankPartitioner:
             self.venue_global[r][name] = (vg if part_venues is None else part_venues[vg]).cpu().numpy()
             rem = (ag < int(b[r])) | (ag >= int(b[r + 1]))
             ra, rv = ag[rem], self.local_sets[r][name]["venue"][rem]
-            o = _lexsort_torch((rv, ra))
+            o = _lexsort_torch((rv, ra))                           # per remote attendee: its smallest local venue of this part
             ra, rv = ra[o], rv[o]
             first = torch.ones(ra.numel(), dtype=torch.bool, device=ra.device)
             first[1:] = ra[1:] != ra[:-1]
             self.halo_lists[r].append((ra[first], rv[first]))
 
-    def _finish_torch(self, age, sex, slice_agents):
-        """``RankPartitioner.finish`` for parts cut out on a device: the extended indices are computed there, the edge lists
-        stay there; the halo list, age and sex of the extended range come to the host (small)."""
-        out = {}
-        for r in self.ranks:
-            a0, a1 = int(self.bounds[r]), int(self.bounds[r + 1])
-            n_local = a1 - a0
-            hl = self.halo_lists[r]
-            dev = None
-            for ls in self.local_sets[r].values():
-                if isinstance(ls["agent_global"], torch.Tensor):
-                    dev = ls["agent_global"].device
-            halo_t, owner_t = order_halo(hl, self.bounds, device=dev)
-            halo_global = halo_t.cpu().numpy()
-            halo_from = np.bincount(owner_t.cpu().numpy(), minlength=self.world_size).astype(np.int64)
-            halo_sorted, sorter_t = torch.sort(halo_t, stable=True)
-            sa = slice_agents
-            if sa is None:
-                _, sa = TL.choose_slices(n_local + len(halo_global) if os.environ.get("GJ_RANK_SLICES", "owned") == "ext"
-                                         else n_local)
-            n_local_pad = -(-n_local // sa) * sa if len(halo_global) else n_local
-            n_ext = n_local_pad + len(halo_global)
-            n_slices = max(1, -(-n_ext // sa))
-            edge_sets = {}
-            for name, ls in self.local_sets[r].items():
-                g = ls.pop("agent_global")
-                if not isinstance(g, torch.Tensor):
-                    g = torch.as_tensor(g, device=dev)
-                ext = g - a0
-                rem = (g < a0) | (g >= a1)
-                if len(halo_global):
-                    ext = torch.where(rem, n_local_pad + sorter_t[torch.searchsorted(halo_sorted, g).clamp_(max=halo_t.numel() - 1)],
-                                      ext)
-                elif bool(rem.any()):
-                    raise RuntimeError("a remote attendee without a halo list")
-                edge_sets[name] = {"agent": ext, "venue": ls["venue"], "people": ls["people"]}
-
-            def ext_attr(v):
-                if isinstance(v, torch.Tensor):
-                    o = torch.full((n_ext,), int(v[0]), dtype=v.dtype, device=v.device)   # (padding rows: agent 0's, as finish())
-                    o[:n_local] = v[a0:a1]
-                    if len(halo_global):
-                        o[n_local_pad:] = v[halo_t.to(v.device)]
-                    return o.cpu().numpy()
-                v = np.asarray(v)
-                o = np.full(n_ext, v[0], dtype=v.dtype)
-                o[:n_local] = v[a0:a1]
-                o[n_local_pad:] = v[halo_global]
-                return o
-
-            out[r] = RankWorld(r, self.world_size, self.bounds, n_local, sa, n_local_pad, n_ext, n_slices, halo_global,
-                               halo_from, ext_attr(age), ext_attr(sex), edge_sets, dict(self.modes),
-                               dict(self.venue_global[r]))
-        self.local_sets = self.halo_lists = self.venue_global = None      # consumed
-        return out
-
     def finish(self, age, sex, slice_agents: Optional[int] = None) -> Dict[int, "RankWorld"]:
-        if any(isinstance(x[0], torch.Tensor) for hl in self.halo_lists.values() for x in hl) or any(
-                isinstance(ls["agent_global"], torch.Tensor) for sets in self.local_sets.values() for ls in sets.values()):
-            return self._finish_torch(age, sex, slice_agents)
-        age, sex = np.asarray(age), np.asarray(sex)
+        """The rank worlds of the sets added so far.  The extended indices are computed where the edge lists live and stay
+        there (numpy arrays for numpy input); the halo list, and age and sex of the extended range (``age`` / ``sex``:
+        numpy arrays or tensors on any device), come to the host - they are small."""
+        back = (lambda t: t.numpy()) if self._as_numpy else (lambda t: t)
         out = {}
         for r in self.ranks:
             a0, a1 = int(self.bounds[r]), int(self.bounds[r + 1])
             n_local = a1 - a0
-            halo_global, owner = order_halo(self.halo_lists[r], self.bounds)
-            halo_from = np.bincount(owner, minlength=self.world_size).astype(np.int64)   # grouped by owner
-            sorter = np.argsort(halo_global, kind="stable")
+            halo_t, owner_t = order_halo(self.halo_lists[r], self.bounds, device=self._device)
+            halo_global = halo_t.cpu().numpy()
+            halo_from = np.bincount(owner_t.cpu().numpy(), minlength=self.world_size).astype(np.int64)   # grouped by owner
+            halo_sorted, sorter_t = torch.sort(halo_t, stable=True)
             sa = slice_agents
             if sa is None:
                 # slices sized for the OWNED agents: phase D runs one workgroup per owned slice, and a rank whose halo
@@ -485,19 +381,26 @@ class RankPartitioner:
                 g = ls.pop("agent_global")
                 ext = g - a0
                 rem = (g < a0) | (g >= a1)
-                if rem.any():
-                    ext[rem] = n_local_pad + sorter[np.searchsorted(halo_global, g[rem], sorter=sorter)]
-                edge_sets[name] = {"agent": ext, "venue": ls["venue"], "people": ls["people"]}
-            ext_global = np.zeros(n_ext, dtype=np.int64)
-            ext_global[:n_local] = np.arange(a0, a1)
-            ext_global[n_local_pad:] = halo_global
+                if len(halo_global):
+                    ext = torch.where(rem, n_local_pad + sorter_t[torch.searchsorted(halo_sorted, g).clamp_(max=halo_t.numel() - 1)],
+                                      ext)
+                elif bool(rem.any()):
+                    raise RuntimeError("a remote attendee without a halo list")
+                edge_sets[name] = {"agent": back(ext), "venue": back(ls["venue"]), "people": ls["people"]}
+
+            def ext_attr(v):
+                v = _tensor(v)
+                o = torch.full((n_ext,), v[0].item(), dtype=v.dtype, device=v.device)   # (padding rows: agent 0's)
+                o[:n_local] = v[a0:a1]
+                if len(halo_global):
+                    o[n_local_pad:] = v[halo_t.to(v.device)]
+                return o.cpu().numpy()
+
             out[r] = RankWorld(r, self.world_size, self.bounds, n_local, sa, n_local_pad, n_ext, n_slices, halo_global,
-                               halo_from, age[ext_global], sex[ext_global], edge_sets, dict(self.modes),
+                               halo_from, ext_attr(age), ext_attr(sex), edge_sets, dict(self.modes),
                                dict(self.venue_global[r]))
         self.local_sets = self.halo_lists = self.venue_global = None      # consumed
         return out
-
-
 
 
 def build_rank_worlds(world: dict, world_size: int, ranks: Optional[Sequence[int]] = None,
@@ -555,10 +458,9 @@ def stream_rank_share(pieces, rank: int, world_size: int, reorder: Optional[str]
     sex = header["sex"] if order is None else header["sex"][order]
     total_edges, sizes, classes = part.total_edges, dict(part.sizes), dict(part.classes)
     rw = part.finish(age, sex, slice_agents)[rank]
-    host = lambda v: v.cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
-    share = {"networks": header["networks"], "state": {k: np.ascontiguousarray(host(pick(v))) for k, v in state.items()},
+    share = {"networks": header["networks"], "state": {k: np.ascontiguousarray(_host(pick(v))) for k, v in state.items()},
              "n_agents": header["n_agents"], "total_edges": total_edges, "sizes": sizes, "classes": classes,
-             "original_id": (np.arange(a0, a1) if order is None else host(order[a0:a1]))}
+             "original_id": (np.arange(a0, a1) if order is None else _host(order[a0:a1]))}
     return rw, share
 
 
@@ -1042,7 +944,7 @@ class PartitionedHotPath:
         self.device = torch.device(device)
         self.parts = parts
         self.ranks: List[DistributedHotPath] = []
-        rws = build_rank_worlds(world, parts, progress=progress)          # every set sorted once, not scanned per part
+        rws = build_rank_worlds(world, parts, progress=progress)
         total_edges = sum(len(es["agent"]) for es in world["edge_sets"].values())
         for r in range(parts):
             rw = rws.pop(r)

@@ -115,17 +115,12 @@ def _edge_set_on_device(name: str, es: dict, n_ext: int, n_agents: Optional[int]
     if E >= 2**31 or n_ext >= 2**31 or n_venues >= 2**31:
         raise ValueError("edge set exceeds int32 indexing")
     mve = mae = 0
-    if E and isinstance(es["venue"], torch.Tensor):
-        mve = int(torch.bincount(es["venue"].reshape(-1), minlength=1).max())
-        a = es["agent"].reshape(-1)
+    if E:                      # (numpy edge lists are viewed as CPU tensors, not copied)
+        mve = int(torch.bincount(torch.as_tensor(es["venue"]).reshape(-1), minlength=1).max())
+        a = torch.as_tensor(es["agent"]).reshape(-1)
         if n_agents is not None:
             a = a[a < n_agents]
         mae = int(torch.bincount(a, minlength=1).max()) if a.numel() else 0
-    elif E:
-        mve = int(np.bincount(np.asarray(es["venue"]).ravel(), minlength=1).max())
-        a = np.asarray(es["agent"]).ravel()
-        a = a[a < (n_ext if n_agents is None else n_agents)]
-        mae = int(np.bincount(a, minlength=1).max()) if len(a) else 0
     return HostEdgeSet(name, n_venues, E, None, None, p_contact(people), None, None, max_venue_edges=mve, max_agent_edges=mae)
 
 

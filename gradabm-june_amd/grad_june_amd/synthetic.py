@@ -383,22 +383,18 @@ def make_world(preset: str = "c3", n_agents: Optional[int] = None, seed: int = 1
 
 def locality_permutation(n_agents: int, agent, venue):
     """(order, new_of) of ``reorder_agents`` from the edge set that defines the locality order (numpy arrays, or torch
-    tensors on any device - the same permutation)."""
-    if not isinstance(agent, np.ndarray) and hasattr(agent, "device"):
-        import torch
+    tensors on any device - computed where they live, returned as what came in)."""
+    import torch
 
-        first = torch.full((n_agents,), torch.iinfo(torch.int64).max, dtype=torch.int64, device=agent.device)
-        first.scatter_reduce_(0, agent, venue, reduce="amin", include_self=True)
-        order = torch.sort(first, stable=True)[1]
-        new_of = torch.empty_like(order)
-        new_of[order] = torch.arange(n_agents, device=agent.device)
-        return order, new_of
-    first = np.full(n_agents, np.iinfo(np.int64).max, dtype=np.int64)
-    np.minimum.at(first, agent, venue)
-    order = np.argsort(first, kind="stable")            # new position -> original id
-    new_of = np.empty(n_agents, dtype=np.int64)
-    new_of[order] = np.arange(n_agents)
-    return order, new_of
+    as_numpy = not isinstance(agent, torch.Tensor)
+    if as_numpy:
+        agent, venue = torch.as_tensor(np.asarray(agent)), torch.as_tensor(np.asarray(venue))
+    first = torch.full((n_agents,), torch.iinfo(torch.int64).max, dtype=torch.int64, device=agent.device)
+    first.scatter_reduce_(0, agent.to(torch.int64), venue.to(torch.int64), reduce="amin", include_self=True)
+    order = torch.sort(first, stable=True)[1]            # new position -> original id
+    new_of = torch.empty_like(order)
+    new_of[order] = torch.arange(n_agents, device=agent.device)
+    return (order.numpy(), new_of.numpy()) if as_numpy else (order, new_of)
 
 
 def iter_world_torch(preset: str, n_agents: int, seed: int, device, infected_fraction: float = 0.01,

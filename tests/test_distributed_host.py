@@ -12,7 +12,9 @@ from grad_june_amd.distributed import (HaloExchange, build_rank_world, choose_mo
                                        partition_bounds)
 from grad_june_amd.plan import compile_plan
 from grad_june_amd.synthetic import make_world
-from grad_june_amd.tiling import emulate_pass1, emulate_pass2
+from grad_june_amd.tiling import choose_slices, emulate_pass1, emulate_pass2
+
+import gj_partition_ref as PR
 
 
 def small_world(n=6000, seed=5):
@@ -221,13 +223,77 @@ def test_clustered_world_venues_are_classified_one_by_one(R):
     assert classes_rnd["household"]["local"] < 0.9 * classes_rnd["household"]["venues"]
 
 
+def restatement_parts(world, R, modes):
+    """The world's edge sets as the parts tests/gj_partition_ref.py takes.  ``modes``: the exchange mode per part (a
+    RankWorld's; the mode decision has tests of its own) - a set that it holds in two halves is split by the restated
+    venue classes."""
+    from grad_june_amd.distributed import SPLIT_SUFFIX
+    from grad_june_amd.synthetic import edge_set_of
+
+    b = partition_bounds(world["n_agents"], R)
+    parts = []
+    for name, es in world["edge_sets"].items():
+        if name + SPLIT_SUFFIX in modes:
+            k = sum(edge_set_of(n) == name for n in world["networks"]) or 1
+            big = PR.venue_classes(es["agent"], es["venue"], len(es["people"]), b, k)
+            parts += PR.split_set(name, es["agent"], es["venue"], es["people"], big)
+        else:
+            parts.append(PR.part(name, es["agent"], es["venue"], es["people"], modes[name]))
+    return parts
+
+
+def assert_equals_restatement(rw, ref, edge_lists=np.ndarray):
+    """``rw`` (a RankWorld) against ``ref`` (gj_partition_ref.rank_world) array for array, and the types at the boundary:
+    the edge lists are ``edge_lists`` (int64 numpy arrays, or int64 tensors where the input lived), everything else is a
+    numpy array on the host."""
+    for k in ("rank", "world_size", "n_local", "slice_agents", "n_local_pad", "n_ext", "n_slices"):
+        assert getattr(rw, k) == ref[k], k
+    assert rw.modes == ref["modes"] and list(rw.edge_sets) == list(ref["edge_sets"])
+    for k in ("bounds", "halo_global", "halo_from", "age", "sex"):
+        assert isinstance(getattr(rw, k), np.ndarray) and np.array_equal(getattr(rw, k), ref[k]), k
+    assert rw.halo_global.dtype == rw.halo_from.dtype == np.int64
+    for name, want in ref["edge_sets"].items():
+        es = rw.edge_sets[name]
+        for k in ("agent", "venue"):
+            assert type(es[k]) is edge_lists and es[k].dtype in (np.int64, torch.int64), (name, k)
+            assert np.array_equal(np.asarray(es[k]), want[k]), (name, k)
+        assert isinstance(es["people"], np.ndarray) and np.array_equal(es["people"], want["people"]), name
+        vg = rw.venue_global[name]
+        if ref["venue_global"][name] is None:
+            assert vg is None, name
+        else:
+            assert isinstance(vg, np.ndarray) and np.array_equal(vg, ref["venue_global"][name]), name
+
+
+@pytest.mark.parametrize("preset,R,forced", [("c3", 2, None), ("c3", 3, None), ("c3", 8, None), ("c3", 2, "halo"),
+                                             ("c3", 3, "halo"), ("c3", 8, "halo"), ("c5", 2, None), ("c5", 5, None)])
+def test_partition_equals_the_plain_restatement(preset, R, forced):
+    """Every rank's part against tests/gj_partition_ref.py (loops, dicts and sorted() over the edge lists), array for
+    array: the small world under the default per-venue rule (which cuts sets in two) and with every set forced into halo
+    mode, and a heavy-tailed world; fed as numpy arrays and as CPU tensors - the same part, numpy edge lists for numpy
+    input, tensors for tensors, everything else numpy on the host."""
+    world = small_world() if preset == "c3" else make_world("c5", n_agents=6000, seed=2)
+    modes = {n: forced for n in world["edge_sets"]} if forced else None
+    as_tensors = dict(world, edge_sets={n: {k: torch.from_numpy(v) for k, v in es.items()}
+                                        for n, es in world["edge_sets"].items()})
+    parts = None
+    for r in range(R):
+        rw = build_rank_world(world, r, R, modes, slice_agents=256)
+        if parts is None:
+            assert forced or any(n.endswith("~big") for n in rw.modes)
+            parts = restatement_parts(world, R, rw.modes)
+        ref = PR.rank_world(world["n_agents"], world["age"], world["sex"], parts, r, R, 256)
+        assert_equals_restatement(rw, ref)
+        assert_equals_restatement(build_rank_world(as_tensors, r, R, modes, slice_agents=256), ref, torch.Tensor)
+
+
 @pytest.mark.parametrize("geography", ["random", "clustered"])
 @pytest.mark.parametrize("R", [2, 8])
 def test_torch_streamed_share_equals_the_numpy_partition(geography, R):
     """``bench.py --gpus N`` draws the world with torch's generator on every rank's own GPU (iter_world_torch) and cuts
-    the rank's part out with torch ops where the tensors live (here: CPU tensors, the same code path): array for array
-    what the numpy partitioner makes of the assembled world - per-venue classes, split halves, halo lists, extended
-    indices, the owned agents' state."""
+    the rank's part out where the tensors live (here: CPU tensors, the same code path): array for array what the plain
+    restatement of the partition (tests/gj_partition_ref.py) makes of the assembled world, and what build_rank_world
+    makes of it as numpy arrays - per-venue classes, split halves, halo lists, extended indices, the owned agents' state."""
     from grad_june_amd.distributed import stream_rank_share
     from grad_june_amd.synthetic import iter_world_torch, make_world_torch, reorder_agents
 
@@ -236,21 +302,17 @@ def test_torch_streamed_share_equals_the_numpy_partition(geography, R):
     wn = dict(w, edge_sets={k: {"agent": es["agent"].numpy(), "venue": es["venue"].numpy(), "people": es["people"]}
                             for k, es in w["edge_sets"].items()})
     wn = reorder_agents(wn, by="household")
+    parts = None
     for r in (0, R - 1):
-        ref = build_rank_world(wn, r, R)
+        via = build_rank_world(wn, r, R)
+        if parts is None:
+            parts = restatement_parts(wn, R, via.modes)
+        n_local = int(via.bounds[r + 1] - via.bounds[r])
+        ref = PR.rank_world(n, wn["age"], wn["sex"], parts, r, R, choose_slices(n_local)[1])
+        assert_equals_restatement(via, ref)
         got, share = stream_rank_share(iter_world_torch("c3", n, 7, "cpu", geography=geography), r, R, reorder="household")
-        assert (ref.n_local, ref.n_local_pad, ref.n_ext, ref.n_slices, ref.slice_agents) == \
-               (got.n_local, got.n_local_pad, got.n_ext, got.n_slices, got.slice_agents)
-        assert ref.modes == got.modes and list(ref.edge_sets) == list(got.edge_sets)
-        assert np.array_equal(ref.halo_global, got.halo_global) and np.array_equal(ref.halo_from, got.halo_from)
-        assert np.array_equal(ref.age, got.age) and np.array_equal(ref.sex, got.sex)
-        for k in ref.edge_sets:
-            for f in ("agent", "venue", "people"):
-                b = got.edge_sets[k][f]
-                assert np.array_equal(ref.edge_sets[k][f], b.numpy() if isinstance(b, torch.Tensor) else b), (k, f)
-            v1, v2 = ref.venue_global[k], got.venue_global[k]
-            assert (v1 is None and v2 is None) or np.array_equal(v1, v2), k
-        a0, a1 = ref.bounds[r], ref.bounds[r + 1]
+        assert_equals_restatement(got, ref, torch.Tensor)
+        a0, a1 = via.bounds[r], via.bounds[r + 1]
         for k, v in share["state"].items():
             assert np.array_equal(v, wn["state"][k][a0:a1]), k
         assert np.array_equal(share["original_id"], wn["original_id"][a0:a1])

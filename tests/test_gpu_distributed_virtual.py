@@ -205,6 +205,46 @@ def test_partial_sum_reduction_order_stays_within_fp32_rounding(device):
     assert int((na != nb).sum()) <= 2 and float(na.sum()) > 1000
 
 
+@pytest.mark.parametrize("geography", ["random", "clustered"])
+def test_streamed_share_cut_on_the_device_equals_the_cpu(device, geography):
+    """The partition is one set of torch ops that runs where its inputs live: a rank's share cut out of a world streamed
+    on the device (stable sort, searchsorted, bincount, nonzero there) equals, array for array, the share the same ops
+    cut on the CPU.  torch's device generator and its CPU generator draw different numbers from one seed, so the CPU run
+    is fed the very pieces the device drew, copied to the host: the same world on both sides."""
+    from grad_june_amd.distributed import stream_rank_share
+    from grad_june_amd.synthetic import iter_world_torch
+
+    def draw():
+        return iter_world_torch("c3", 20_000, 7, device, geography=geography)
+
+    def on_cpu(pieces):
+        for piece in pieces:
+            yield piece[:-1] + ({k: v.cpu() if isinstance(v, torch.Tensor) else v for k, v in piece[-1].items()},)
+
+    R = 3
+    for r in range(R):
+        got, share = stream_rank_share(draw(), r, R, reorder="household")
+        ref, share_ref = stream_rank_share(on_cpu(draw()), r, R, reorder="household")
+        assert (ref.n_local, ref.n_local_pad, ref.n_ext, ref.n_slices, ref.slice_agents) == \
+               (got.n_local, got.n_local_pad, got.n_ext, got.n_slices, got.slice_agents)
+        assert ref.modes == got.modes and list(ref.edge_sets) == list(got.edge_sets) and got.n_halo > 0
+        assert "halo" in got.modes.values() and "partial" in got.modes.values()
+        for k in ("bounds", "halo_global", "halo_from", "age", "sex"):
+            assert isinstance(getattr(got, k), np.ndarray) and np.array_equal(getattr(got, k), getattr(ref, k)), k
+        for name, es in ref.edge_sets.items():
+            for k in ("agent", "venue"):
+                t = got.edge_sets[name][k]
+                assert t.device.type == "cuda" and es[k].device.type == "cpu" and torch.equal(t.cpu(), es[k]), (name, k)
+            assert np.array_equal(got.edge_sets[name]["people"], es["people"]), name
+            v1, v2 = ref.venue_global[name], got.venue_global[name]
+            assert (v1 is None and v2 is None) or np.array_equal(v1, v2), name
+        for k, v in share_ref["state"].items():
+            assert np.array_equal(share["state"][k], v), k
+        assert np.array_equal(share["original_id"], share_ref["original_id"])
+        assert (share["total_edges"], share["sizes"], share["classes"]) == \
+               (share_ref["total_edges"], share_ref["sizes"], share_ref["classes"])
+
+
 def test_pack_unpack_kernels(device):
     """gj_pack_f32 / gj_unpack_f32 (halo send / receive buffers)."""
     from grad_june_amd import _native as N

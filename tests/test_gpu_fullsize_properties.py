@@ -277,7 +277,7 @@ def test_c5_full_size_seven_partitions_equal_one(device):
     SEVEN rank-like partitions on the one GPU against the single partition: every partition exactly a rank of the
     multi-GPU run (per-venue exchange classes: every set comes as a local + halo half and a partial-sum half, the two
     collectives become device copies / fp32 sums in rank order).  The world is drawn on the device
-    (synthetic.make_world_torch) and the partitions are cut out there (RankPartitioner's torch path: what
+    (synthetic.make_world_torch) and the partitions are cut out there (RankPartitioner runs where its inputs live: what
     ``bench.py --gpus 8 --preset c5`` does per rank).  Same discrete state after three Philox steps, up to the handful of
     decisions that may sit within fp32 rounding of a partial sum."""
     import time
