@@ -1108,7 +1108,8 @@ struct TPSet {
   fx_t* partial;          // [workgroups][V * stride]
   int32_t planes, V, stride, nk;
   int32_t group_venues;   // venues per LDS table
-  int32_t raw, leisure, _pad;
+  int32_t raw, leisure;
+  uint32_t term_limit;   // bit pattern of the largest |term| a venue sum takes: the set's window, as TSetB has it
   int32_t table[GJ_MAX_NETS_PER_SET];
   int32_t age75[GJ_MAX_NETS_PER_SET];
 };
@@ -1125,9 +1126,12 @@ struct TilePArgs {
 };
 
 constexpr int kPresumQuads = 3;     // quads of agents a lane keeps in flight
-// (the opt-in experiment keeps round 3's rule: one flag per sum, anything that cannot be summed reads back NaN)
-__device__ __forceinline__ void fx_add_or_poison(fx_t* sums, uint32_t* flags, int i, float x) {
-  const bool ok = fabsf(x) <= fx_max<kFxVenue>();
+// (the opt-in experiment keeps round 3's rule: one flag per sum, anything that cannot be summed reads back NaN).  What
+// can be summed is decided as in run_sums: on the bit patterns, against the set's window (`limit`, at most the pattern
+// of fx_max<kFxVenue>(); smaller for a set with venues of more than 4 096 attendees) - each workgroup's table would
+// hold larger terms, the sum of the tables in k_presum_reduce would not.
+__device__ __forceinline__ void fx_add_or_poison(fx_t* sums, uint32_t* flags, int i, float x, uint32_t limit) {
+  const bool ok = abs_bits(x) <= limit;
   atomicAdd(&sums[i], to_fx<kFxVenue>(ok ? x : 0.0f));
   if (__builtin_expect(!ok, 0)) atomicOr(&flags[i >> 5], 1u << (i & 31));
 }
@@ -1194,11 +1198,11 @@ __global__ __launch_bounds__(kTileThreads) void k_tile_presum(const TilePArgs P)
                 const int lv = (int)((w[j] >> (16 * c)) & 0xFFFF) - v0;
                 const bool in = ((unsigned)lv < (unsigned)nv) && (j < n_ok);
                 if (!T.leisure) {
-                  fx_add_or_poison(lds_p, flags, in ? lv : dummy, in ? xv[j] : 0.0f);
+                  fx_add_or_poison(lds_p, flags, in ? lv : dummy, in ? xv[j] : 0.0f, T.term_limit);
                 } else {
                   const int cj = class_byte(B.cl[u], j);
                   for (int k = 0; k < nk; ++k)
-                    fx_add_or_poison(lds_p, flags, in ? lv * nk + k : dummy, in ? wtab[k * 200 + cj] * xv[j] : 0.0f);
+                    fx_add_or_poison(lds_p, flags, in ? lv * nk + k : dummy, in ? wtab[k * 200 + cj] * xv[j] : 0.0f, T.term_limit);
                 }
               }
             }

@@ -843,6 +843,22 @@ static inline bool classes_by_dword(const gj_plan* plan) {
   return plan->agent_class && (uintptr_t)plan->agent_class % 4 == 0;
 }
 
+// Bit pattern of the largest |term| a venue sum of this set takes: 2^14 (the window of the 2^-36 fixed point) while the
+// largest venue has at most 4 096 edges, else 2^26 / next_pow2(edges) - terms x edges then stays below 2^62 fixed-point
+// units and no sum can wrap.  A term beyond it saturates its venue (gj_tiled.h).  0 edges = not stated: 2^14.
+static uint32_t venue_term_limit(int32_t max_venue_edges) {
+  int e = 14;
+  int64_t p2 = 4096;
+  while (p2 < (int64_t)max_venue_edges && e > -20) {
+    p2 <<= 1;
+    --e;
+  }
+  const float lim = ldexpf(1.0f, e);
+  uint32_t bits;
+  memcpy(&bits, &lim, sizeof(bits));
+  return bits;
+}
+
 // pass 1 of the sets in its direct form: LDS tables of fixed-point sums per workgroup (k_tile_presum)
 static int presum_fill(const gj_plan* plan, const gj_step_params* p, const Groups& G, int g, TPSet* X) {
   const gj_tiled* T = plan->tiled;
@@ -860,7 +876,7 @@ static int presum_fill(const gj_plan* plan, const gj_step_params* p, const Group
   X->nk = C.nk;
   X->raw = C.raw;
   X->leisure = C.leisure;
-  X->_pad = 0;
+  X->term_limit = venue_term_limit(S.max_venue_edges);
   memcpy(X->table, C.table, sizeof(X->table));
   memcpy(X->age75, C.age75, sizeof(X->age75));
   if (C.leisure && !classes_by_dword(plan)) return GJ_E_PLAN;
@@ -957,22 +973,6 @@ static int tiled_scatter(const gj_plan* plan, const gj_agent_state* st, const gj
   rc = launch(k_tile_scatter, T->n_slices, kTileThreads, lds, stream, A);
   if (rc) return rc;
   return tiled_presum(plan, st, p, G, stream);
-}
-
-// Bit pattern of the largest |term| a venue sum of this set takes: 2^14 (the window of the 2^-36 fixed point) while the
-// largest venue has at most 4 096 edges, else 2^26 / next_pow2(edges) - terms x edges then stays below 2^62 fixed-point
-// units and no sum can wrap.  A term beyond it saturates its venue (gj_tiled.h).  0 edges = not stated: 2^14.
-static uint32_t venue_term_limit(int32_t max_venue_edges) {
-  int e = 14;
-  int64_t p2 = 4096;
-  while (p2 < (int64_t)max_venue_edges && e > -20) {
-    p2 <<= 1;
-    --e;
-  }
-  const float lim = ldexpf(1.0f, e);
-  uint32_t bits;
-  memcpy(&bits, &lim, sizeof(bits));
-  return bits;
 }
 
 static int tiled_venues(const gj_plan* plan, const gj_agent_state* st, const gj_step_params* p, const Groups& G, int mode,

@@ -321,7 +321,10 @@ def compile_plan(n_agents: int, edge_sets: Dict[str, dict], age=None, sex=None,
     single-network set whose agents are so ordered, that is not in the direct form and where it pays; False = none;
     or a collection of set names (must be possible; takes precedence over the direct form).
     presum: True = a set in the direct form whose edges all belong to owned agents takes pass 1 in the direct form too
-    (its ELL rows + per-workgroup LDS tables of fixed-point sums, k_tile_presum; bit-identical results).  Off by
+    (its ELL rows + per-workgroup LDS tables of fixed-point sums, k_tile_presum).  Finite terms inside the set's window
+    (2^14, smaller for a set with a venue of more than 4 096 edges: gj_tiled_set.max_venue_edges) give bit-identical
+    results; a value that cannot be summed - beyond the window, an infinity, a NaN - reads back NaN (one flag per sum),
+    where phases A + B saturate to +-1e30.  Off by
     default: measured on C3 (round 3, tools/ab.py) it moves 0.2 GB less per step and is 15 % SLOWER - the 64-bit LDS
     atomics it takes out of the venue launch (115 M per step) cost the same there, and its own launch pays a memory
     round trip per batch (one workgroup per CU: the tables fill the LDS).  A second attempt in the same round (batches

@@ -1,7 +1,8 @@
 """GPU: pass 2 of the tiled step per agent - phase C + phase D of csrc/gj_tiled.h (k_tile_venues mode 0 / 2,
 k_tile_agents, k_tile_epilogue) - BIT FOR BIT against the numpy restatement tests/gj_pass2_ref.py, in every form.
 
-Pass 1 is pinned to its arithmetic by test_gpu_venue_multinet.py / test_gpu_venue_lv8.py; pass 2 was compared with
+Pass 1 is pinned to its arithmetic by test_gpu_pass1_kernels.py (every form, against tests/gj_pass1_ref.py) and, for a
+leisure set in the workspace form, by test_gpu_venue_multinet.py / test_gpu_venue_lv8.py; pass 2 was compared with
 other things only (the oracle at rtol 2e-5, float64 sums within a bound, itself across geometries).  Here `agent_sums`
 and `trans_susc` of EVERY agent are compared as uint32 (NaN by position) with the restatement, which works from the edge
 lists alone and which tests/test_pass2_ref.py checks on the CPU.

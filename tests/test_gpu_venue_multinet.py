@@ -23,6 +23,7 @@ import numpy as np
 import pytest
 import torch
 
+import gj_pass1_ref as R1
 from grad_june_amd import _native as N
 from grad_june_amd.engine import AgentBuffers, InfectionEngine
 from grad_june_amd.plan import DevicePlan, NetworkSpec, _host, compile_plan
@@ -108,39 +109,21 @@ def engine_of(kind, nk, device):
 # ---- the restatement ---------------------------------------------------------------------------------------------------
 def term_limit_bits(max_venue_edges):
     """The set's window: 2^14 while its largest venue has at most 4 096 edges, else the power of two
-    that keeps edges x window below 2^26."""
-    e, p2 = 14, 4096
-    while p2 < max_venue_edges:
-        p2, e = 2 * p2, e - 1
-    return int(np.float32(2.0 ** e).view(np.uint32))
+    that keeps edges x window below 2^26.  (tests/gj_pass1_ref.py holds the rule.)"""
+    return R1.term_limit_bits(max_venue_edges)
 
 
 def restate(w, nk, day_type, transpose, x):
-    """{network index: cum [V] float32}, and the venues with a flagged sum, per network."""
+    """{network index: cum [V] float32}, and the venues with a flagged sum, per network: tests/gj_pass1_ref.py on this
+    file's one set (every network of it active)."""
     names, kinds, tables, betas = networks_of(nk)
-    a, v, V = w["agent"], w["venue"], w["V"]
     with np.errstate(all="ignore"):
         pc = np.clip(np.float32(1.0) / (w["people"] - 1).astype(np.float32), np.float32(0.0), np.float32(1.0))
-    limit = term_limit_bits(int(np.bincount(v).max()))
-    cum, flagged = [], []
-    for k in range(nk):
-        wk = tables[k][day_type, w["sex"], w["age"]]
-        if transpose and kinds[k] == N.MASK_QL_AGE75:
-            wk = wk * (w["age"] > 75).astype(np.float32)
-        with np.errstate(all="ignore"):
-            term = (wk[a] * x[a]).astype(np.float32)
-            ok = (term.view(np.uint32) & 0x7FFFFFFF) <= limit
-            fx = np.rint(term[ok].astype(np.float64) * 2.0 ** 36).astype(np.int64)
-            sums = np.zeros(V, dtype=np.int64)
-            np.add.at(sums, v[ok], fx)
-            pos, neg = np.zeros(V, dtype=bool), np.zeros(V, dtype=bool)
-            pos[v[~ok & ~(term < 0)]] = True          # positive, +inf or NaN
-            neg[v[~ok & ~(term > 0)]] = True          # negative, -inf or NaN
-            s = (sums.astype(np.float64) * 2.0 ** -36).astype(np.float32)
-            s = np.where(pos & neg, np.float32(np.nan), np.where(pos, SATURATED, np.where(neg, -SATURATED, s)))
-            cum.append(((np.float32(betas[names[k]]) * pc).astype(np.float32) * s).astype(np.float32))
-        flagged.append(pos | neg)
-    return cum, flagged
+    nets = [(betas[n], t, k == N.MASK_QL_AGE75, False) for n, k, t in zip(names, kinds, tables)]
+    cum, flagged = R1.restate_set(w["agent"], w["venue"], pc, nets, x, age=w["age"], sex=w["sex"], day_type=day_type,
+                                  transpose=transpose)
+    return ([np.ascontiguousarray(cum[:, k]).view(np.float32) for k in range(nk)],
+            [np.ascontiguousarray(flagged[:, k]) for k in range(nk)])
 
 
 def launch(engine, nk, day_type, transpose, x, device, phase=8):
