@@ -15,12 +15,15 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <algorithm>
+
 #include "../../include/gradjune_hip.h"
 #include "gj_device.h"
 #include "gj_tiled.h"
 #include "gj_agent.h"
 #include "gj_location.h"
 #include "gj_infector.h"
+#include "gj_tree.h"
 
 namespace gj {
 
@@ -1935,6 +1938,84 @@ int gj_infection_matrix_clear(const gj_plan* plan, const gj_location_rows* rows,
                               int64_t* const* UG, int32_t n_groups, void* stream) {
   if (n_groups < 1 || n_groups > GJ_MATRIX_MAX_GROUPS) return plan ? GJ_E_RANGE : GJ_E_NULL;
   return infector_clear(plan, rows, new_infected, UG, n_groups, stream);
+}
+
+int gj_infection_tree(const gj_plan* plan, const gj_step_params* params, const gj_location_rows* rows,
+                      const gj_venue_rows* venue_rows, const float* new_infected, const float* susceptibility0,
+                      const float* current_stage, const float* transmission, const int32_t* cols, int32_t n_cols,
+                      int32_t background_col, uint64_t seed, uint64_t step, int64_t agent_offset, int32_t* infector,
+                      int32_t* via, int32_t* venue, int32_t* row_of, int32_t row_value, int64_t* counts,
+                      int64_t* unresolved, uint32_t* err, void* stream) {
+  int rc = gj::check_plan(plan);
+  if (rc) return rc;
+  gj::Groups G;
+  rc = gj::group_networks(plan, params, &G);
+  if (rc) return rc;
+  if (!new_infected || !susceptibility0 || !infector || !via || !venue || !row_of || !counts || !unresolved || !err)
+    return GJ_E_NULL;
+  if ((plan->n_sets > 0 && !rows) || (params->n_nets > 0 && (!cols || !transmission || !venue_rows))) return GJ_E_NULL;
+  if (params->has_quarantine && !current_stage) return GJ_E_NULL;
+  if (n_cols < 1 || n_cols > GJ_LOC_MAX_COLS || background_col < 0 || background_col >= n_cols) return GJ_E_RANGE;
+  for (int i = 0; i < params->n_nets; ++i)
+    if (cols[i] < 0 || cols[i] >= n_cols) return GJ_E_RANGE;
+  if (agent_offset < 0 || agent_offset > (int64_t)INT32_MAX - plan->n_agents) return GJ_E_RANGE;
+  static_assert(sizeof(gj::TreeArgs) <= 4096, "kernel arguments");
+  gj::TreeArgs A = {};
+  // the sets in the order of plan->sets - the canonical order of the pairs - whatever the order of the networks
+  int order[GJ_MAX_SETS];
+  for (int g = 0; g < G.n; ++g) order[g] = g;
+  std::sort(order, order + G.n, [&](int x, int y) { return G.set[x] < G.set[y]; });
+  for (int j = 0; j < G.n; ++j) {
+    const int g = order[j];
+    const gj_edge_set& E = plan->sets[G.set[g]];
+    const gj_location_rows& R = rows[G.set[g]];
+    const gj_venue_rows& V = venue_rows[G.set[g]];
+    if (R.a_rowptr && !R.a_venue && E.n_edges > 0) return GJ_E_NULL;
+    if (V.v_rowptr && !V.v_agent && E.n_edges > 0) return GJ_E_NULL;
+    const gj::NetGroup C = gj::classify_group(params, G, g);
+    gj::TreeSet& S = A.sets[j];
+    S.rowptr = R.a_rowptr;
+    S.venue = R.a_venue;
+    S.cum = E.cum;
+    S.n_edges = (int32_t)E.n_edges;
+    S.n_venues = (int32_t)E.n_venues;
+    S.stride = E.cum_stride;
+    S.nk = C.nk;
+    S.first = G.first[g];
+    memcpy(S.mask, C.mask, sizeof(S.mask));
+    memcpy(S.table, C.table, sizeof(S.table));
+    S.v_rowptr = V.v_rowptr;
+    S.v_agent = V.v_agent;
+  }
+  if (plan->n_agents == 0) return GJ_OK;
+  A.n = plan->n_agents;
+  A.flag = new_infected;
+  A.s0 = susceptibility0;
+  A.stage = params->has_quarantine ? current_stage : nullptr;
+  A.tr = transmission;
+  A.cls = plan->agent_class;
+  A.tables = plan->tables;
+  A.infector = infector;
+  A.via = via;
+  A.venue = venue;
+  A.row_of = row_of;
+  A.counts = (unsigned long long*)counts;
+  A.unresolved = (unsigned long long*)unresolved;
+  A.err = err;
+  A.seed = seed;
+  A.step = step;
+  A.agent_offset = agent_offset;
+  A.n_cols = n_cols;
+  A.n_nets = params->n_nets;
+  A.n_sets = G.n;
+  A.has_q = params->has_quarantine ? 1 : 0;
+  A.day_type = params->day_type;
+  A.background = background_col;
+  A.row_value = row_value;
+  A.q_thr = params->q_threshold;
+  for (int i = 0; i < params->n_nets; ++i) A.cols[i] = cols[i];
+  return gj::launch(gj::k_infection_tree, gj::grid_for(A.n, gj::kLocBlocks, gj::kLocLoads * gj::kWave), gj::kThreads, 0,
+                    (hipStream_t)stream, A);
 }
 
 int gj_step(const gj_plan* plan, const gj_agent_state* state, const gj_step_params* params, const gj_step_io* io,

@@ -33,6 +33,8 @@ GJ_LOC_ERR_LABEL, GJ_LOC_ERR_VALUE, GJ_LOC_ERR_ROWS = 1, 2, 4
 GJ_LOC_MAX_COLS, GJ_LOC_LDS_BINS, GJ_LOC_BLOCKS = 64, 4096, 2048
 # gj_infection_matrix_*: the largest labelling that gets a who-infects-whom matrix (G * G <= GJ_LOC_LDS_BINS)
 GJ_MATRIX_MAX_GROUPS = 64
+# gj_infection_tree: the longest by-venue row it takes (2^18 members of at most 2^46 each sum below 2^64)
+GJ_TREE_MAX_VENUE_ROW = 1 << 18
 
 MASK_RAW, MASK_Q, MASK_QL, MASK_QL_AGE75 = 0, 1, 2, 3
 
@@ -210,6 +212,13 @@ class LocationRows(C.Structure):
     ]
 
 
+class VenueRows(C.Structure):
+    _fields_ = [
+        ("v_rowptr", _vp),
+        ("v_agent", _vp),
+    ]
+
+
 class SeedPlan(C.Structure):
     _fields_ = [
         ("n_sorted", C.c_int64),
@@ -313,6 +322,12 @@ SYMBOLS = {
     ),
     "gj_infection_matrix_clear": (
         C.c_int, [C.POINTER(Plan), C.POINTER(LocationRows), _vp, C.POINTER(_vp), C.c_int32, _vp]),
+    "gj_infection_tree": (
+        C.c_int,
+        [C.POINTER(Plan), C.POINTER(StepParams), C.POINTER(LocationRows), C.POINTER(VenueRows), _vp, _vp, _vp, _vp,
+         C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_uint64, C.c_uint64, C.c_int64, _vp, _vp, _vp, _vp, C.c_int32,
+         _vp, _vp, _vp, _vp],
+    ),
     "gj_step": (C.c_int, [C.POINTER(Plan), C.POINTER(AgentState), C.POINTER(StepParams), C.POINTER(StepIO), _vp]),
     "gj_step_phase": (
         C.c_int,

@@ -175,6 +175,7 @@ class DistributedRunner(Runner):
         cls._refuse_locations(params.get("locations_to_save"))
         cls._refuse_infectors(params.get("infectors_to_save"))
         cls._refuse_matrices(params.get("infection_matrices_to_save"))
+        cls._refuse_tree(params.get("infection_tree_to_save"))
         model = DistributedGradJune.from_parameters(params)
         full = Runner.get_data(params)                # the whole world, identical on every rank (same torch seed)
         n_total = len(full["agent"]["id"])

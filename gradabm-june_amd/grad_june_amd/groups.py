@@ -600,6 +600,95 @@ class InfectorStats:
             raise InfectorError(f"{what}: " + " and ".join(why))
 
 
+class InfectionTreeError(RuntimeError):
+    """gj_infection_tree met a new_infected that is neither 0 nor 1, a NaN or negative term, a saturated weight, or a
+    row outside its edge set."""
+
+
+def infection_tree_to_save(spec) -> bool:
+    """The YAML key ``infection_tree_to_save`` / the Runner's ``tree=``: true or false (absent: false)."""
+    if spec is None:
+        return False
+    if isinstance(spec, (bool, np.bool_)):
+        return bool(spec)
+    raise ValueError(f"infection_tree_to_save: expected true or false, not {spec!r}")
+
+
+class InfectionTree:
+    """``gj_infection_tree`` for a world of ``n_agents``: one sampled infector per infection.  Owns what the launches
+    write over a run - per agent, int32: ``infector`` (global id; -1 never infected, -2 nobody transmitted, -3
+    unresolved), ``via`` (the index into ``columns`` of the location it came through), ``venue`` (in its edge set's
+    numbering, -1 with -2) and ``infected_row`` (-1: never) - and per row ``counts`` [rows, L] (exact, by location
+    column) and ``unresolved`` [rows], and the sticky error word."""
+
+    def __init__(self, n_agents: int, columns, device=None, n_rows: int = 1):
+        self.columns = [str(c) for c in columns]
+        if not 1 <= len(self.columns) <= N.GJ_LOC_MAX_COLS or len(set(self.columns)) != len(self.columns):
+            raise ValueError(f"columns: 1 .. {N.GJ_LOC_MAX_COLS} distinct names, not {self.columns}")
+        self.n, self.device = int(n_agents), torch.device(device)
+        self.err = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self.reset(n_rows)
+
+    def reset(self, n_rows: int = 1) -> None:
+        dev = self.device
+        self.infector = torch.full((self.n,), -1, dtype=torch.int32, device=dev)
+        self.via = torch.full((self.n,), -1, dtype=torch.int32, device=dev)
+        self.venue = torch.full((self.n,), -1, dtype=torch.int32, device=dev)
+        self.infected_row = torch.full((self.n,), -1, dtype=torch.int32, device=dev)
+        self.counts = torch.zeros(int(n_rows), len(self.columns), dtype=torch.int64, device=dev)
+        self.unresolved = torch.zeros(int(n_rows), dtype=torch.int64, device=dev)
+
+    def record(self, plan, params, new_infected, susceptibility0, current_stage, transmission, active=(),
+               background="background", row: int = 0, edges=None, seed: int = 0, step: int = 0,
+               agent_offset: int = 0) -> None:
+        """One step: the tree's entries of the agents with new_infected == 1, counts[row] and unresolved[row].
+        ``active``: the column name of each of the step's networks, in the order of ``params.nets``; ``seed``, ``step``:
+        the Philox key and stream of the draw; ``edges``: see ``DevicePlan.location_rows`` / ``venue_rows``."""
+        import ctypes as C
+
+        if plan.host.n_agents != self.n:
+            raise ValueError(f"a plan of {plan.host.n_agents} agents for {self.n}")
+        for t in (new_infected, susceptibility0, current_stage):
+            if t is not None and (t.numel() != self.n or t.dtype != torch.float32 or not t.is_contiguous()
+                                  or t.device != self.device):
+                raise ValueError(f"per-agent arguments: contiguous float32[{self.n}] on {self.device}")
+        n_ext = plan.host.n_ext_agents
+        if transmission is not None and (transmission.numel() != n_ext or transmission.dtype != torch.float32
+                                         or not transmission.is_contiguous() or transmission.device != self.device):
+            raise ValueError(f"transmission: contiguous float32[{n_ext}] on {self.device}")
+        if len(active) != params.n_nets:
+            raise ValueError(f"{len(active)} columns for {params.n_nets} active networks")
+        if not 0 <= row < self.unresolved.numel():
+            raise IndexError(f"row {row} of {self.unresolved.numel()}")
+        cols = (C.c_int32 * max(1, len(active)))(*[self.columns.index(str(c)) for c in active])
+        venue_rows = plan.venue_rows(edges) if params.n_nets > 0 else None      # (the seeding step reads no venue)
+        N.check(N.load().gj_infection_tree(
+            C.byref(plan.c), C.byref(params), plan.location_rows(edges), venue_rows, N.ptr(new_infected),
+            N.ptr(susceptibility0), N.ptr(current_stage), N.ptr(transmission), cols, len(self.columns),
+            self.columns.index(background), int(seed) & 0xFFFFFFFFFFFFFFFF, int(step), int(agent_offset),
+            N.ptr(self.infector), N.ptr(self.via), N.ptr(self.venue), N.ptr(self.infected_row), int(row),
+            N.ptr(self.counts[row]), N.ptr(self.unresolved[row:]), N.ptr(self.err), N.current_stream()),
+            "gj_infection_tree")
+
+    def offspring(self) -> torch.Tensor:
+        """int64 [n]: the infections every agent was drawn as the infector of (agent_offset 0)."""
+        drawn = self.infector[self.infector >= 0].long()
+        return torch.bincount(drawn, minlength=self.n)[: self.n]
+
+    def check(self, what: str = "gj_infection_tree") -> None:
+        """Raise if a launch since the last check met bad input (one device read)."""
+        err = int(self.err.item()) & 0xFFFFFFFF
+        if err:
+            self.err.zero_()
+            why = []
+            if err & N.GJ_LOC_ERR_VALUE:
+                why.append("a new_infected that is neither 0 nor 1 (skipped), a NaN / negative term (counted as 0) or a "
+                           "transmitter's weight above 2^10 (saturated)")
+            if err & N.GJ_LOC_ERR_ROWS:
+                why.append("a row pointer, venue id or member outside its edge set (skipped)")
+            raise InfectionTreeError(f"{what}: " + " and ".join(why))
+
+
 class SeedPlan:
     """One labelling as ``gj_adjoint_seed`` wants it (include/gradjune_hip.h, gj_seed_plan): the agents with a label in
     [0, n_groups) sorted by label (stable), every group's segment cut into chunks of GJ_SEED_CHUNK agents.  Built once per

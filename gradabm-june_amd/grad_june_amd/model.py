@@ -34,6 +34,7 @@ class GradJune(torch.nn.Module):
         self.step_stats = None      # see forward()
         self.location_stats = None  # see forward()
         self.infector_stats = None  # see forward()
+        self.tree_stats = None      # see forward()
 
     @classmethod
     def from_file(cls, fpath=None):
@@ -81,10 +82,12 @@ class GradJune(torch.nn.Module):
         exp_noise = self._exp_noise(engine, exp_noise)
         # infection-location series: what forward() launches gj_location_stats with after the step (s0 and stage are
         # filled in by the path taken)
-        # ... and gj_infector_scatter / gj_infector_gather: the two series share one record (and one clone of s0)
-        wanted = getattr(self, "location_stats", None) is not None or getattr(self, "infector_stats", None) is not None
+        # ... and gj_infector_scatter / gj_infector_gather, and gj_infection_tree: the three series share one record (and
+        # one clone of s0)
+        wanted = any(getattr(self, sink, None) is not None for sink in ("location_stats", "infector_stats", "tree_stats"))
         self._location_step = (None if not wanted else
-                               {"engine": engine, "params": where["params"], "active": [n.name for n in active]})
+                               {"engine": engine, "params": where["params"], "active": [n.name for n in active],
+                                "seed": self.rng_seed, "step": step})
         if differentiable:
             return self._hot_path_differentiable(data, engine, where, active, betas, has_q, exp_noise, want_probs)
         return self._hot_path_in_place(data, engine, where, has_q, exp_noise, want_probs)
@@ -136,7 +139,8 @@ class GradJune(torch.nn.Module):
         fixed = {k: f(ip[k]) for k in ("max_infectiousness", "shape", "rate", "shift")}
         stage = f(ag["symptoms"]["current_stage"]).clone() if has_q else None
         env = dict(where, fixed=fixed, stage=stage, exp_noise=exp_noise, nets=list(active), betas=betas)
-        if getattr(self, "infector_stats", None) is not None:      # the node leaves its transmission array here
+        if getattr(self, "infector_stats", None) is not None or getattr(self, "tree_stats", None) is not None:
+            # the node leaves its transmission array here
             env["keep_transmission"] = self._location_step
         state = [ag[k] if ag[k].dtype == torch.float32 else ag[k].to(torch.float32) for k in
                  ("susceptibility", "is_infected", "infection_time")]
@@ -175,6 +179,24 @@ class GradJune(torch.nn.Module):
         sink["stats"].record(plan, step["params"], nu, step["s0"], step["stage"], step["transmission"].detach(),
                              row=sink["row"], edges=self.location_edges(data, plan))
 
+    def _record_tree(self, sink, data, new_infected):
+        """gj_infection_tree on the step just run, for the ``groups.InfectionTree`` of the sink: the infector series'
+        launch point, record and transmissions, and the step's own Philox key and stream.  No gradient."""
+        step = self._location_step
+        plan = step["engine"].plan
+        nu = new_infected.detach().to(device=plan.device, dtype=torch.float32).contiguous()
+        edges = self.location_edges(data, plan) or self.venue_edges(data, plan)
+        sink["stats"].record(plan, step["params"], nu, step["s0"], step["stage"], step["transmission"].detach(),
+                             active=step["active"], background="background", row=sink["row"], edges=edges,
+                             seed=step["seed"], step=step["step"])
+
+    @staticmethod
+    def venue_edges(data, plan):
+        """``location_edges`` for ``DevicePlan.venue_rows``: the COO edge lists, or None once the plan holds the rows."""
+        if getattr(plan, "_venue_rows", None) is not None:
+            return None
+        return {s: data["attends_" + s].edge_index for s in plan.host.set_index if "attends_" + s in data}
+
     def _vaccination_env(self):
         """(global id of local agent 0, sum over the ranks of the efficacy's gradient or None): a rank of a partitioned
         world overrides it (distributed_api.DistributedGradJune)."""
@@ -202,6 +224,10 @@ class GradJune(torch.nn.Module):
         sink = getattr(self, "infector_stats", None)
         if sink is not None:
             self._record_infectors(sink, data, new_infected)
+        # tree_stats: the same for the transmission tree (groups.InfectionTree), at the same point
+        sink = getattr(self, "tree_stats", None)
+        if sink is not None:
+            self._record_tree(sink, data, new_infected)
         # in grad mode new_infected stays on the graph: the symptoms update is then an autograd node too
         # (autograd.SymptomsStep), which is what makes the deaths series differentiable (runner.py:198-215)
         # step_stats: set by the Runner for the duration of its time loop - the per-step result reductions

@@ -514,6 +514,32 @@ def _finish_runs(rf, t, n_agents: int, slice_agents: int, device):
     return TL.finish_run_form(rf, _host(t.blk_v0), n_agents, slice_agents)
 
 
+def longest_venue_row(name: str, rowptr: torch.Tensor) -> int:
+    """The longest row of a by-venue CSR; ValueError naming the set if it exceeds GJ_TREE_MAX_VENUE_ROW."""
+    longest = int(torch.diff(rowptr).max()) if rowptr.numel() > 1 else 0
+    if longest > N.GJ_TREE_MAX_VENUE_ROW:
+        raise ValueError(f"edge set {name}: a venue with {longest} members; the transmission tree takes at most "
+                         f"{N.GJ_TREE_MAX_VENUE_ROW} (GJ_TREE_MAX_VENUE_ROW)")
+    return longest
+
+
+def venue_rows_of(name: str, agent: torch.Tensor, venue: torch.Tensor, n_agents: int, n_venues: int):
+    """(v_rowptr int32 [n_venues + 1], v_agent int32 [owned edges]) of one edge set's COO lists, with torch ops on the
+    lists' device: the owned agents' edges (agent < n_agents; a halo agent is no member of an owned row), sorted by
+    venue - a stable sort, so that the COO order stays inside a row.  What ``DevicePlan.venue_rows`` builds per set."""
+    agent, venue = agent.long(), venue.long()
+    own = agent < n_agents
+    if not bool(own.all()):
+        agent, venue = agent[own], venue[own]
+    if agent.numel() and (int(agent.min()) < 0 or int(venue.min()) < 0 or int(venue.max()) >= n_venues):
+        raise ValueError(f"edge set {name}: an agent or venue index outside the plan")
+    order = torch.argsort(venue, stable=True)
+    zero = torch.zeros(1, dtype=torch.int64, device=venue.device)
+    rowptr = torch.cat((zero, torch.cumsum(torch.bincount(venue, minlength=n_venues), 0))).to(torch.int32).contiguous()
+    longest_venue_row(name, rowptr)
+    return rowptr, agent[order].to(torch.int32).contiguous()
+
+
 class DevicePlan:
     """The plan resident in HBM + the ctypes ``gj_plan`` that points at it."""
 
@@ -719,6 +745,38 @@ class DevicePlan:
             rows[i].a_rowptr, rows[i].a_venue = rowptr.data_ptr(), venue.data_ptr()
         self._location_rows_keep = keep
         self._location_rows = rows
+        return rows
+
+    def venue_rows(self, edges=None):
+        """The ``gj_venue_rows`` array of ``gj_infection_tree``: every set's edges as CSR by venue - the mirror of
+        ``location_rows`` - built on first use and kept with the plan (only the transmission trees ask for it): int32,
+        4 B per edge and 4 B per venue.
+
+        A plan that holds the CSR arrays (layout "csr" / "both") reuses them.  Otherwise ``edges`` supplies the COO lists
+        as for ``location_rows``: a stable sort by venue keeps the COO order inside a row.  A row of more than
+        GJ_TREE_MAX_VENUE_ROW members is refused (the kernel's 64-bit sum of weights could wrap).  ``venue_rows_max``
+        holds the longest row of every set afterwards."""
+        if getattr(self, "_venue_rows", None) is not None:
+            return self._venue_rows
+        dev, n = self.device, self.host.n_agents
+        rows = (N.VenueRows * N.GJ_MAX_SETS)()
+        keep, longest = [], {}
+        for i, s in enumerate(self.host.sets):
+            t = self.keep[i]
+            if t.get("v_rowptr") is not None:
+                rowptr, agent = t["v_rowptr"], t["v_agent"]
+            elif edges is not None and s.name in edges:
+                e = edges[s.name]
+                to = lambda a: (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))).to(dev)
+                rowptr, agent = venue_rows_of(s.name, to(e[0]), to(e[1]), n, s.n_venues)
+            else:
+                continue
+            longest[s.name] = longest_venue_row(s.name, rowptr)
+            keep.append((rowptr, agent))
+            rows[i].v_rowptr, rows[i].v_agent = rowptr.data_ptr(), agent.data_ptr()
+        self._venue_rows_keep = keep
+        self.venue_rows_max = longest
+        self._venue_rows = rows
         return rows
 
     def infector_units(self):

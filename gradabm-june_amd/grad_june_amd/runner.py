@@ -51,11 +51,12 @@ def world_from_npz(path) -> HeteroData:
 class Runner(torch.nn.Module):
     def __init__(self, model, data, timer, log_fraction_initial_cases, save_path, parameters,
                  age_bins=(0, 18, 65, 100), groups=None, seed_group=None, stages=None, locations=None, infectors=None,
-                 matrices=None):
+                 matrices=None, tree=None):
         super().__init__()
         self._refuse_locations(locations)
         self._refuse_infectors(infectors)
         self._refuse_matrices(matrices)
+        self._refuse_tree(tree)
         self.model = model
         self.data = data
         self.data_backup = self.backup_infection_data(data)
@@ -108,6 +109,15 @@ class Runner(torch.nn.Module):
         # ``infection_matrices_to_save``): for each of these labellings the infector series by PAIRS of groups - a step's
         # infections caused by group g in group g' - and the unattributed infections by the infected agent's group
         self.matrices_saved = self._check_matrices(matrices)
+        # transmission tree (not in the reference): ``tree=True`` (the YAML key ``infection_tree_to_save``): ONE sampled
+        # infector per infection - who infected whom, through which location and venue, and in which row - with the
+        # exact counts by location and the mean generation interval per row
+        from .groups import infection_tree_to_save
+
+        self.tree_saved = infection_tree_to_save(tree)
+        if self.tree_saved and not self.location_keys:
+            self.location_keys = location_keys(model.infection_networks.networks)
+        self._tree_stats = None
         self.restore_initial_data()
 
     _supports_locations = True
@@ -134,6 +144,14 @@ class Runner(torch.nn.Module):
         if infection_matrices_to_save(spec) and not cls._supports_locations:      # they are sums of the infector series' terms
             raise NotImplementedError("infection_matrices_to_save: the infection matrices are not available in a "
                                       "partitioned run")
+
+    @classmethod
+    def _refuse_tree(cls, spec):
+        from .groups import infection_tree_to_save
+
+        if infection_tree_to_save(spec) and not cls._supports_locations:      # a venue's members live on other ranks
+            raise NotImplementedError("infection_tree_to_save: the transmission tree is not available in a partitioned "
+                                      "run")
 
     def _check_matrices(self, spec):
         """The labellings that get an infection matrix: each a labelling with result series (``groups_to_save``) of at
@@ -182,6 +200,7 @@ class Runner(torch.nn.Module):
             locations=params.get("locations_to_save"),
             infectors=params.get("infectors_to_save"),
             matrices=params.get("infection_matrices_to_save"),
+            tree=params.get("infection_tree_to_save"),
         )
 
     @staticmethod
@@ -297,7 +316,7 @@ class Runner(torch.nn.Module):
                 data=self.data, timer=self.timer, symptoms_updater=self.model.symptoms_updater,
                 fractions=fractions, labels=labels, device=self.device,
                 agent_offset=getattr(self, "agent_offset", 0), plan=plan, all_reduce=self._seed_all_reduce())
-        if self.locations_saved or self.infectors_saved:      # row 0 of the infection-location and infector series
+        if self.locations_saved or self.infectors_saved or self.tree_saved:      # row 0 of these series
             self._seed_new_infected = new_infected.detach()
         self.model.symptoms_updater(data=self.data, timer=self.timer, new_infected=new_infected)
 
@@ -403,7 +422,7 @@ class Runner(torch.nn.Module):
                     self._location_stats[name] = LocationStats(st.labels, st.n_groups, self.location_keys, device=dev)
         return self._location_stats
 
-    def _record_seed_locations(self, locations, infectors=None):
+    def _record_seed_locations(self, locations, infectors=None, tree=None):
         """Row 0: the seeding step.  No network is active, so every seeded agent lands in the column ``seed``."""
         dev = require_hip(self.device)
         engine = self.model._engine(self.data, dev)
@@ -417,6 +436,9 @@ class Runner(torch.nn.Module):
             infectors.clear(engine.plan)      # (U is zero between steps; a run that was interrupted may have left some)
             infectors.record(engine.plan, params, nu, s0, None, None, row=0,
                              edges=self.model.location_edges(self.data, engine.plan))
+        if tree is not None:      # nobody transmitted a seed: every seeded agent gets -2 and the column ``seed``
+            tree.record(engine.plan, params, nu, s0, None, None, active=(), background="seed", row=0,
+                        edges=self.model.location_edges(self.data, engine.plan))
         self._seed_new_infected = None
 
     # per-step infector series: gj_infector_scatter once, gj_infector_gather for the nation and once per labelling -------
@@ -430,6 +452,27 @@ class Runner(torch.nn.Module):
                 self.n_agents, {name: (st.labels, st.n_groups) for name, st in self._groups().items()},
                 device=require_hip(self.device), matrices=self.matrices_saved)
         return self._infector_stats
+
+    # transmission tree: one gj_infection_tree launch per step ---------------------------------------------------------------
+    def _tree(self):
+        """The run's ``groups.InfectionTree``, or None without ``infection_tree_to_save`` (nothing is allocated, cloned or
+        launched)."""
+        if self._tree_stats is None and self.tree_saved:
+            from .groups import InfectionTree
+
+            self._tree_stats = InfectionTree(self.n_agents, self.location_keys, device=require_hip(self.device))
+        return self._tree_stats
+
+    def _generation_interval(self, tree, dates):
+        """float32 [T]: the mean, over the agents infected in row r with a sampled infector, of the days between the
+        infector's row date and row r; NaN for a row without one.  Torch ops on the tree's arrays."""
+        T, dev = len(dates), tree.device
+        days = torch.tensor([(d - dates[0]).total_seconds() / 86400.0 for d in dates], dtype=torch.float64, device=dev)
+        has = tree.infector >= 0
+        row = tree.infected_row[has].long()
+        parent_row = tree.infected_row[tree.infector[has].long()].long()
+        sums = torch.zeros(T, dtype=torch.float64, device=dev).index_add_(0, row, days[row] - days[parent_row])
+        return (sums / torch.bincount(row, minlength=T).to(torch.float64)).to(torch.float32)
 
     # vaccination series: the launches' own counts, and one gj_group_stats pass per labelling on a launch's mask ----------
     def _campaigns(self):
@@ -490,8 +533,11 @@ class Runner(torch.nn.Module):
         infectors = self._infectors()
         if infectors is not None:
             infectors.reset(n_rows)
-        if locations or infectors is not None:
-            self._record_seed_locations(locations, infectors)
+        tree = self._tree()
+        if tree is not None:
+            tree.reset(n_rows)
+        if locations or infectors is not None or tree is not None:
+            self._record_seed_locations(locations, infectors, tree)
         # vaccination series (not in the reference), whenever the model has a Vaccination policy: the doses given so far,
         # by campaign (the launches' own counts) and by every labelling (gj_group_stats on a launch's mask of the newly
         # vaccinated).  Integer counts, so a by-group row sums to the national row exactly; row 0 is zero; no gradient
@@ -535,6 +581,8 @@ class Runner(torch.nn.Module):
                 model.location_stats = {"stats": list(locations.values()), "row": row}
             if infectors is not None:
                 model.infector_stats = {"stats": infectors, "row": row}
+            if tree is not None:
+                model.tree_stats = {"stats": tree, "row": row}
             if campaigns is not None:      # cumulative: a row starts from the one before it
                 for series in self._vaccine_group_series.values():
                     series[row].copy_(series[row - 1])
@@ -546,6 +594,7 @@ class Runner(torch.nn.Module):
                 model.step_stats = None
                 model.location_stats = None
                 model.infector_stats = None
+                model.tree_stats = None
                 if campaigns is not None:
                     campaigns.on_newly = None
             if campaigns is not None and campaigns.doses is not None:
@@ -614,6 +663,25 @@ class Runner(torch.nn.Module):
                 caused, infected_row = torch.empty_like(caused), torch.empty_like(infected_row)
                 caused[index], infected_row[index] = infectors.caused, infectors.infected_row
             data["agent"]["infections_caused"], data["agent"]["infected_row"] = caused, infected_row
+        if tree is not None:      # exact counts as float64; the per-agent arrays in the file's order; no gradient
+            tree.check("transmission tree")
+            T = row + 1
+            results["infections_sampled_by_location"] = tree.counts[:T].to(torch.float64)
+            results["infections_unresolved_per_timestep"] = tree.unresolved[:T].to(torch.float64)
+            results["generation_interval_per_timestep"] = self._generation_interval(tree, dates)
+            per_agent = {"infector": tree.infector, "infection_location": tree.via, "infection_venue": tree.venue,
+                         "infected_row": tree.infected_row, "offspring": tree.offspring()}
+            if "original_index" in data["agent"]:      # positions and the ids held in ``infector``: the file's numbering
+                index = data["agent"].original_index.to(tree.device).long()
+                named = torch.where(tree.infector >= 0, index[tree.infector.clamp(min=0).long()].to(torch.int32),
+                                    tree.infector)
+                per_agent["infector"] = named
+                for key, values in per_agent.items():
+                    moved = torch.empty_like(values)
+                    moved[index] = values
+                    per_agent[key] = moved
+            for key, values in per_agent.items():
+                data["agent"][key] = values
         if campaigns is not None:      # counts as float64: exact (float32 holds integers up to 2^24 only)
             by_campaign = self._vaccine_series[: row + 1].to(torch.float64)
             results["vaccine_doses_per_timestep"] = by_campaign.sum(1)
@@ -693,6 +761,17 @@ class Runner(torch.nn.Module):
                     pd.DataFrame({"date": np.repeat(dates, G * G), "infector": np.tile(np.repeat(np.asarray(keys), G), len(dates)),
                                   "infected": np.tile(keys, len(dates) * G), "infections": flat(f"infection_matrix_by_{name}")}
                                  ).to_csv(self.save_path / f"results_infection_matrix_by_{name}.csv", index=False)
+        if "infections_sampled_by_location" in results:      # one line per infected agent
+            ag = self.data["agent"]
+            row_of = ag["infected_row"].detach().cpu().numpy()
+            infected = np.nonzero(row_of >= 0)[0]
+            dates = np.asarray(results["dates"], dtype=object)
+            pd.DataFrame({"infected": infected, "infector": ag["infector"].detach().cpu().numpy()[infected],
+                          "date": dates[row_of[infected]],
+                          "location": np.asarray(self.location_keys, dtype=object)[
+                              ag["infection_location"].detach().cpu().numpy()[infected]],
+                          "venue": ag["infection_venue"].detach().cpu().numpy()[infected]}
+                         ).to_csv(self.save_path / "results_infection_tree.csv", index=False)
         pd.DataFrame({"is_infected": is_infected.detach().cpu().numpy()}).to_csv(
             self.save_path / "results_is_infected.csv")
 

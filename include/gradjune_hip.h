@@ -654,6 +654,69 @@ int gj_infection_matrix_clear(const gj_plan* plan, const gj_location_rows* rows 
                               const float* new_infected, int64_t* const* UG /* host [plan->n_sets] */, int32_t n_groups,
                               void* stream);
 
+/* ---- row f2 as a tree: one sampled infector per new infection ------------------------------------------------------------
+ * A pure addition to ABI 7: where gj_infector_gather gives every infectious agent its EXPECTED share of the step's new
+ * infections, gj_infection_tree draws ONE infector for each of them - who infected whom, where, and when.  Run at the
+ * point where gj_infector_scatter runs - AFTER a step, with its `params`, while plan->sets[s].cum holds the step's sums,
+ * current_stage is the stage the quarantine mask was formed from and `transmission` is the step's.  Notation as above.
+ * For every agent a with new_infected[a] == 1:
+ *
+ * The draw.  One Philox4x32-10 block, counter (agent_offset + a, step | 1 << 60), key `seed` (bit 60 is a stream of its
+ * own: bits 61, 62, 63 and the 1 << 40 counter are taken): r1 = word 0 & (2^30 - 1), R = word 2 | word 3 << 32.
+ *
+ * The (venue, network) pair.  t_i, T, t_{i,e} and u_{i,e} = min(floor(t_{i,e} / T * GJ_LOC_UNIT), GJ_LOC_UNIT) are exactly
+ * gj_infector_scatter's values (the same device functions form them), and so is the best pair: the largest t_{i,e}, the
+ * lowest i on a tie, then the lowest position in the row.  T not finite or not > 0: nobody transmitted - infector[a] =
+ * -2, via[a] = background_col, venue[a] = -1.  Otherwise the pairs are ordered by edge set (the order of plan->sets), then
+ * by position in a's row of that set, then by the network's column k_i; given = sum of u over all pairs; if r1 < given
+ * the pair is the first whose inclusive prefix sum of u exceeds r1, otherwise it is the best pair - which is therefore
+ * drawn with probability (u + GJ_LOC_UNIT - given) / GJ_LOC_UNIT: its cell of U.  All integers: no arrangement of the
+ * lanes changes the choice.  via[a] = cols[i], venue[a] = v_e in the set's own numbering.
+ *
+ * The infector.  venue_rows[s] (s < plan->n_sets): the set's edges as CSR by venue - v_rowptr device int32
+ * [n_venues + 1], v_agent device int32 [n_edges], OWNED agents, in a fixed order (DevicePlan.venue_rows: COO order inside
+ * a row) - supplied by the caller like `rows`; a CSR plan may pass gj_edge_set's.  Over the members b of venue v, in row
+ * order: b == a has weight 0; otherwise w_b = m_i[b] * transmission[b] in fp64 (the product of two fp32 values: exact),
+ * NaN or <= 0: weight 0; W_b = min(floor(w_b * 2^36), 2^46) - 2^36 is the hot path's venue resolution; a saturated weight
+ * sets GJ_LOC_ERR_VALUE.  S = sum of W_b in unsigned 64 bits: a venue row holds at most GJ_TREE_MAX_VENUE_ROW = 2^18
+ * members (a longer one is refused where the rows are built, and counts as a bad row here), so S cannot wrap.  S == 0:
+ * unresolved - infector[a] = -3, via and venue keep the pair, *unresolved (device int64; the call ADDS) counts it; it
+ * happens only where every transmitter's weight is below 2^-36, or the set has no venue rows (v_rowptr == NULL).
+ * Otherwise target = (R * S) >> 64 (the 128-bit product) and infector[a] = agent_offset + the first member whose
+ * inclusive prefix sum of W exceeds target.  W_b / S is m_i[b] * transmission[b] over the venue's sum of them up to the
+ * 2^-36 floor - b's share in gj_infector_gather's credit - so the expectation of the sample is the infector series.
+ *
+ * counts[via[a]] += 1 (device int64 [n_cols], exact; the call ADDS) and row_of[a] = row_value.  infector, via, venue,
+ * row_of: device int32 [n_agents]; an agent with new_infected[a] == 0 is untouched (the caller starts infector at -1,
+ * "never infected").  n_nets == 0 is valid (the seeding step): every infection gets -2 and background_col, venue_rows is
+ * not read.  n_agents == 0 launches nothing.
+ * Bad input never becomes an index: a new_infected that is neither 0 nor 1 is skipped and sets GJ_LOC_ERR_VALUE; a row
+ * pointer or venue id of `rows` outside its set is skipped and sets GJ_LOC_ERR_ROWS; a venue row outside its set or
+ * longer than GJ_TREE_MAX_VENUE_ROW counts as empty, a member outside [0, n_agents) has weight 0, and both set
+ * GJ_LOC_ERR_ROWS.  *err (device uint32) is sticky until the caller clears it.
+ * One launch, the launch shape of gj_location_stats: a group of 16 lanes per newly infected agent; the pairs are walked
+ * once, in chunks of 16 positions with an exclusive scan over the group; the venue row twice (sum, then select), in
+ * batches of 4 members per lane whose transmissions are loaded together - the mask's inputs are read for the members
+ * that transmit only - by the agent's group, or, a row of more than 256 members, by the whole wave (one such row after
+ * the other: a launch ends with its longest row); a row of one batch is not loaded again.  counts go through an LDS
+ * histogram of n_cols bins.
+ * Errors, returned before any device work: what gj_location_stats returns for a bad plan, params, rows, cols, n_cols or
+ * background_col; GJ_E_NULL for a NULL new_infected, susceptibility0, infector, via, venue, row_of, counts, unresolved
+ * or err, a NULL current_stage with has_quarantine, a NULL transmission or venue_rows with n_nets > 0, v_rowptr without
+ * v_agent; GJ_E_RANGE for agent_offset < 0 or agent_offset + n_agents > INT32_MAX.                                        */
+#define GJ_TREE_MAX_VENUE_ROW (1 << 18)
+typedef struct gj_venue_rows {
+  const int32_t* v_rowptr;  /* device [n_venues+1] or NULL: no rows, an infection through this set stays unresolved */
+  const int32_t* v_agent;   /* device [n_edges]                                                                     */
+} gj_venue_rows;
+int gj_infection_tree(const gj_plan* plan, const gj_step_params* params, const gj_location_rows* rows /* [plan->n_sets] */,
+                      const gj_venue_rows* venue_rows /* [plan->n_sets] */, const float* new_infected,
+                      const float* susceptibility0, const float* current_stage, const float* transmission,
+                      const int32_t* cols /* host [n_nets] */, int32_t n_cols, int32_t background_col, uint64_t seed,
+                      uint64_t step, int64_t agent_offset, int32_t* infector, int32_t* via, int32_t* venue,
+                      int32_t* row_of, int32_t row_value, int64_t* counts, int64_t* unresolved, uint32_t* err,
+                      void* stream);
+
 /* ---- row f3: adjoint (backward) of one hot-path step, forward-only kernels reused ---------------
  * The aggregation ts = susc * sum_n w_n * (M_n^T diag(beta_n p_contact) M_n)(m_n * transmission) is
  * self-adjoint up to the exchange of the masks m_n <-> w_n, so its backward is the same four tiled
