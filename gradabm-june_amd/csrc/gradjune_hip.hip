@@ -24,6 +24,7 @@
 #include "gj_location.h"
 #include "gj_infector.h"
 #include "gj_tree.h"
+#include "gj_contact.h"
 
 namespace gj {
 
@@ -1458,6 +1459,67 @@ int gj_adjoint_vaccinate(int64_t n, const uint8_t* agent_class, const gj_vaccina
     if (rc) return rc;
   }
   return gj::seed_sum_launch(R, (hipStream_t)hip_stream);
+}
+
+namespace gj {
+// the sets of gj_contact_mark / gj_contact_mask, checked and copied into the launch's arguments (the caller's array may
+// change after the call returns); `marking`: the release time is read, and must be a non-negative number
+static int contact_sets(const gj_contact_set* sets, int32_t n_sets, bool marking, ContactSet* out) {
+  if (n_sets < 1 || n_sets > GJ_MAX_SETS) return GJ_E_RANGE;
+  if (!sets) return GJ_E_NULL;
+  for (int s = 0; s < GJ_MAX_SETS; ++s) out[s] = ContactSet{};
+  for (int s = 0; s < n_sets; ++s) {
+    const gj_contact_set& S = sets[s];
+    if (S.n_venues < 0 || S.n_venues > INT32_MAX) return GJ_E_RANGE;
+    if (marking && !(S.release >= 0.0f)) return GJ_E_RANGE;                  // (a NaN too)
+    if (!S.a_rowptr || !S.a_venue || !S.until) return GJ_E_NULL;
+    uint32_t bits = 0;
+    if (marking) memcpy(&bits, &S.release, sizeof bits);
+    out[s] = ContactSet{S.a_rowptr, S.a_venue, S.until, (int32_t)S.n_venues, bits & 0x7fffffffu};   // (-0 marks as +0)
+  }
+  return GJ_OK;
+}
+}  // namespace gj
+
+int gj_contact_mark(int64_t n, const float* current_stage, float stage_threshold, const gj_contact_set* sets,
+                    int32_t n_sets, uint32_t* err, void* stream) {
+  if (n < 0) return GJ_E_RANGE;
+  gj::ContactMarkArgs A;
+  if (const int rc = gj::contact_sets(sets, n_sets, true, A.sets)) return rc;
+  if (!err || (n > 0 && !current_stage)) return GJ_E_NULL;
+  if (n == 0) return GJ_OK;
+  A.n = n;
+  A.stage = current_stage;
+  A.err = err;
+  A.threshold = stage_threshold;
+  A.n_sets = n_sets;
+  A.vec4 = gj::aligned16(current_stage) ? 1 : 0;
+  return gj::launch(gj::k_contact_mark, gj::grid_for(gj::vec4_lanes(n, A.vec4), gj::kContactBlocks), gj::kThreads, 0,
+                    (hipStream_t)stream, A);
+}
+
+int gj_contact_mask(int64_t n, const float* current_stage, float q_threshold, const gj_contact_set* sets,
+                    int32_t n_sets, float now, float compliance, uint64_t seed, uint64_t stream, int64_t agent_offset,
+                    float* qstate, uint32_t* err, void* hip_stream) {
+  if (n < 0 || agent_offset < 0) return GJ_E_RANGE;
+  gj::ContactMaskArgs A;
+  if (const int rc = gj::contact_sets(sets, n_sets, false, A.sets)) return rc;
+  if (!err || (n > 0 && (!current_stage || !qstate))) return GJ_E_NULL;
+  if (n == 0) return GJ_OK;
+  A.n = n;
+  A.stage = current_stage;
+  A.qstate = qstate;
+  A.err = err;
+  A.seed = seed;
+  A.stream = stream;
+  A.agent_offset = agent_offset;
+  A.threshold = q_threshold;
+  A.now = now;
+  A.compliance = compliance;
+  A.n_sets = n_sets;
+  A.vec4 = (agent_offset % 4 == 0 && gj::aligned16(current_stage, qstate)) ? 1 : 0;
+  return gj::launch(gj::k_contact_mask, gj::grid_for(gj::vec4_lanes(n, A.vec4), gj::kContactBlocks), gj::kThreads, 0,
+                    (hipStream_t)hip_stream, A);
 }
 
 int gj_adjoint_transmission(int64_t n, const gj_agent_state* st, float now, const float* trans_bar,

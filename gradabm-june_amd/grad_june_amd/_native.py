@@ -30,6 +30,7 @@ GJ_STAGE_MAX_AGENTS = 1 << 40
 # gj_location_stats: the fixed-point unit of one infection, error bits, limits and the launch shape
 GJ_LOC_UNIT = 1 << 30
 GJ_LOC_ERR_LABEL, GJ_LOC_ERR_VALUE, GJ_LOC_ERR_ROWS = 1, 2, 4
+GJ_CONTACT_ERR_ROWS = 4
 GJ_LOC_MAX_COLS, GJ_LOC_LDS_BINS, GJ_LOC_BLOCKS = 64, 4096, 2048
 # gj_infection_matrix_*: the largest labelling that gets a who-infects-whom matrix (G * G <= GJ_LOC_LDS_BINS)
 GJ_MATRIX_MAX_GROUPS = 64
@@ -238,6 +239,16 @@ class VaccinateTables(C.Structure):
     ]
 
 
+class ContactSet(C.Structure):
+    _fields_ = [
+        ("a_rowptr", _vp),
+        ("a_venue", _vp),
+        ("until", _vp),
+        ("n_venues", C.c_int64),
+        ("release", C.c_float),
+    ]
+
+
 #: every symbol include/gradjune_hip.h declares: (restype, argtypes)
 SYMBOLS = {
     "gj_version": (C.c_int, []),
@@ -275,6 +286,13 @@ SYMBOLS = {
         C.c_int,
         [C.c_int64, _vp, C.POINTER(VaccinateTables), C.c_uint64, C.c_uint64, C.c_int64, _vp, _vp, _vp, C.c_int32,
          C.POINTER(SeedPlan), _vp, _vp, _vp, _vp, _vp],
+    ),
+    "gj_contact_mark": (
+        C.c_int, [C.c_int64, _vp, C.c_float, C.POINTER(ContactSet), C.c_int32, _vp, _vp]),
+    "gj_contact_mask": (
+        C.c_int,
+        [C.c_int64, _vp, C.c_float, C.POINTER(ContactSet), C.c_int32, C.c_float, C.c_float, C.c_uint64, C.c_uint64,
+         C.c_int64, _vp, _vp, _vp],
     ),
     "gj_adjoint_beta_partial": (
         C.c_int,

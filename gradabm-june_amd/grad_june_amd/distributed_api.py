@@ -38,6 +38,13 @@ from .timer import Timer
 from .world import require_hip
 
 
+def _refuse_contact_quarantine(policies):
+    """A ``ContactQuarantine`` marks venues whose members live on other ranks."""
+    if getattr(getattr(policies, "quarantine_policies", None), "contact_policies", None):
+        raise NotImplementedError("contact_quarantine: the ContactQuarantine policy is not available in a partitioned "
+                                  "run")
+
+
 class DistributedGradJune(GradJune):
     """``GradJune`` whose hot path runs one rank's part of the world (``partition`` first)."""
 
@@ -48,6 +55,7 @@ class DistributedGradJune(GradJune):
         plan holds them)."""
         import torch.distributed as dist
 
+        _refuse_contact_quarantine(self.policies)
         device = require_hip(self.device)
         if rank is None:
             rank, world_size = dist.get_rank(group), dist.get_world_size(group)
@@ -102,6 +110,9 @@ class DistributedGradJune(GradJune):
 
     def _engine(self, data, device):
         return self._hp.engine
+
+    def _contact_quarantine(self, data, timer, engine):
+        _refuse_contact_quarantine(self.policies)
 
     def _betas(self, engine, active, timer):
         betas = super()._betas(engine, active, timer)
@@ -177,6 +188,7 @@ class DistributedRunner(Runner):
         cls._refuse_matrices(params.get("infection_matrices_to_save"))
         cls._refuse_tree(params.get("infection_tree_to_save"))
         model = DistributedGradJune.from_parameters(params)
+        _refuse_contact_quarantine(model.policies)
         full = Runner.get_data(params)                # the whole world, identical on every rank (same torch seed)
         n_total = len(full["agent"]["id"])
         seed_group, log_fraction = Runner.seed_parameters(params, full)      # (keys of the whole world's labelling)

@@ -210,18 +210,26 @@ def _step_inputs(active_networks, all_networks, data, timer, policies, device):
     for n in active_networks:
         if n.name not in engine.plan.networks:
             raise KeyError(f"network '{n.name}': edge set 'attends_{n.edge_set}' is not in the world")
+    # a ContactQuarantine's mark and mask, as GradJune.hot_path runs them (the key defaults as the model's does); the
+    # launch then takes the mask in the place of the stage
+    qstate = None
+    if has_q and getattr(qp, "contact_policies", None):
+        plan = engine.plan
+        qstate = qp.contact_step(plan, timer, torch.initial_seed() & 0xFFFFFFFFFFFFFFFF, edges=lambda: {
+            s: data["attends_" + s].edge_index for s in plan.host.set_index if "attends_" + s in data})
     params = engine.params(
         now=timer.now, delta_time=timer.duration, day_type=0 if timer.day_type == "weekday" else 1,
         active=[n.name for n in active_networks], betas=betas, has_quarantine=has_q,
-        q_threshold=qp.threshold if has_q else math.inf)
-    return engine, params, has_q
+        q_threshold=getattr(qp, "launch_threshold", qp.threshold) if has_q else math.inf)
+    return engine, params, has_q, qstate
 
 
 def _run_networks(active_networks, data, timer, policies, device, want="probs", all_networks=None):
     device = require_hip(device)
     if hasattr(policies, "apply"):
         policies.apply(timer=timer, data=data)
-    engine, params, has_q = _step_inputs(active_networks, all_networks or active_networks, data, timer, policies, device)
+    engine, params, has_q, qstate = _step_inputs(active_networks, all_networks or active_networks, data, timer, policies,
+                                                 device)
     ag = data["agent"]
     if torch.is_grad_enabled() and (
             any(isinstance(n.log_beta, torch.Tensor) and n.log_beta.requires_grad for n in active_networks)
@@ -230,14 +238,16 @@ def _run_networks(active_networks, data, timer, policies, device, want="probs", 
         from .autograd import NetworksForward
 
         stage = None
-        if has_q:
+        if qstate is not None:
+            stage = qstate.clone()
+        elif has_q:
             stage = ag["symptoms"]["current_stage"].detach().to(device=device, dtype=torch.float32).contiguous()
         env = {"engine": engine, "params": params, "want": want, "nets": list(active_networks), "stage": stage,
                "betas": {n.name: float(params.nets[i].beta) for i, n in enumerate(active_networks)}}
         f = lambda t: t if t.dtype == torch.float32 else t.to(torch.float32)
         return NetworksForward.apply(env, f(ag["transmission"]).to(device), f(ag["susceptibility"]).to(device),
                                      *[n.log_beta for n in active_networks])
-    bufs = agent_buffers(engine, data, need_params=False, need_stage=has_q, need_infection_state=False)
+    bufs = agent_buffers(engine, data, need_params=False, need_stage=has_q, need_infection_state=False, stage=qstate)
     n = engine.plan.host.n_agents
     out = torch.empty(n, dtype=torch.float32, device=device)
     # q*transmission is normally produced by the transmission kernel; callers of this entry set

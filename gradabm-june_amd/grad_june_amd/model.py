@@ -78,6 +78,10 @@ class GradJune(torch.nn.Module):
         step = self.n_steps
         self.n_steps += 1
         betas = self._betas(engine, active, timer)
+        # contact quarantine: mark, then mask, on the stage the step starts from; the step then takes the mask in the
+        # place of the stage (None while no ContactQuarantine is active: nothing launched, the threshold path as it was)
+        if has_q:
+            self._contact_quarantine(data, timer, engine)
         where = self._launch_env(engine, timer, active, betas, has_q, step)
         exp_noise = self._exp_noise(engine, exp_noise)
         # infection-location series: what forward() launches gj_location_stats with after the step (s0 and stage are
@@ -99,13 +103,26 @@ class GradJune(torch.nn.Module):
     def _betas(self, engine, active, timer):
         return {n.name: n.beta_value(self.policies, timer) for n in active}
 
+    def _contact_quarantine(self, data, timer, engine):
+        """``QuarantinePolicies.contact_step`` on this step's plan: it leaves the mask of the active ``ContactQuarantine``
+        in ``quarantine_policies.qstate`` (None without one), where ``_launch_env`` and the two paths below read it."""
+        qp = self.policies.quarantine_policies
+        if getattr(qp, "contact_policies", None):
+            plan = engine.plan
+            qp.contact_step(plan, timer, self.rng_seed, edges=lambda: {
+                s: data["attends_" + s].edge_index for s in plan.host.set_index if "attends_" + s in data})
+
+    def _qstate(self):
+        return getattr(self.policies.quarantine_policies, "qstate", None)
+
     def _launch_env(self, engine, timer, active, betas, has_q, step):
         """Where the step runs and with which launch parameters, as ``autograd.HotPathStep`` takes it in its ``env``."""
         qp = self.policies.quarantine_policies
         return {"engine": engine, "params": engine.params(
             now=timer.now, delta_time=timer.duration, day_type=0 if timer.day_type == "weekday" else 1,
             active=[n.name for n in active], betas=betas, has_quarantine=has_q,
-            q_threshold=qp.threshold if has_q else math.inf, seed=self.rng_seed, step=step)}
+            q_threshold=getattr(qp, "launch_threshold", qp.threshold) if has_q else math.inf, seed=self.rng_seed,
+            step=step)}
 
     def _exp_noise(self, engine, exp_noise):
         if exp_noise is None:
@@ -114,7 +131,7 @@ class GradJune(torch.nn.Module):
 
     def _hot_path_in_place(self, data, engine, where, has_q, exp_noise, want_probs):
         """The step that updates ``data["agent"]``'s state tensors in place (nothing requires a gradient)."""
-        bufs = agent_buffers(engine, data, need_params=True, need_stage=has_q)
+        bufs = agent_buffers(engine, data, need_params=True, need_stage=has_q, stage=self._qstate())
         n, device = engine.plan.host.n_agents, engine.plan.device
         new_infected = torch.empty(n, dtype=torch.float32, device=device)
         probs = torch.empty(n, dtype=torch.float32, device=device) if want_probs else None
@@ -137,7 +154,8 @@ class GradJune(torch.nn.Module):
         f = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
         ip = ag["infection_parameters"]
         fixed = {k: f(ip[k]) for k in ("max_infectiousness", "shape", "rate", "shift")}
-        stage = f(ag["symptoms"]["current_stage"]).clone() if has_q else None
+        # (the mask of a ContactQuarantine too is copied: the policy rewrites its buffer in the next step)
+        stage = (self._qstate() if self._qstate() is not None else f(ag["symptoms"]["current_stage"])).clone() if has_q else None
         env = dict(where, fixed=fixed, stage=stage, exp_noise=exp_noise, nets=list(active), betas=betas)
         if getattr(self, "infector_stats", None) is not None or getattr(self, "tree_stats", None) is not None:
             # the node leaves its transmission array here

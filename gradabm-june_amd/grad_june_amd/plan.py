@@ -707,45 +707,76 @@ class DevicePlan:
         stride = self.c.sets[i].cum_stride
         return self.cum[i][: self.host.sets[i].n_venues * stride].view(self.host.sets[i].n_venues, stride)
 
-    def location_rows(self, edges=None):
-        """The ``gj_location_rows`` array of ``gj_location_stats``: every set's edges as CSR by owned agent, built on
-        first use and kept with the plan (only the infection-location series asks for it).
+    def _agent_rows(self, i: int, edges=None):
+        """``(rowptr, venue)`` of set ``i``: its edges as CSR by owned agent, int32 on the device, or None for a set that
+        is neither held by the plan nor in ``edges``.  ONE definition for ``location_rows`` and ``contact_rows``; what is
+        built is kept with the plan, so either reuses the other's arrays.
 
         A plan that holds the CSR arrays (layout "csr" / "both") reuses them.  Otherwise ``edges`` supplies the COO
         lists, ``{set name: edge_index [2, E]}`` or ``{set name: (agent, venue)}`` in the agent order of this plan: a
-        stable sort by agent keeps the COO order inside a row (torch ops on the device, 4 B per edge).  A set that is
-        in neither gets no rows (it contributes nothing)."""
+        stable sort by agent keeps the COO order inside a row (torch ops on the device, 4 B per edge)."""
+        held = getattr(self, "_agent_rows_held", None)
+        if held is None:
+            held = self._agent_rows_held = {}
+        if i in held:
+            return held[i]
+        dev, n, s, t = self.device, self.host.n_agents, self.host.sets[i], self.keep[i]
+        if t.get("a_rowptr") is not None:
+            rowptr, venue = t["a_rowptr"], t["a_venue"]
+        elif edges is not None and s.name in edges:
+            e = edges[s.name]
+            agent, venue = (e[0], e[1])
+            to = lambda a: (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))).to(dev)
+            agent, venue = to(agent).long(), to(venue)
+            if self.host.n_ext_agents > n:                       # halo agents' edges belong to another rank's rows
+                own = agent < n
+                agent, venue = agent[own], venue[own]
+            if agent.numel() and (int(agent.min()) < 0 or int(agent.max()) >= n or int(venue.min()) < 0
+                                  or int(venue.max()) >= s.n_venues):
+                raise ValueError(f"edge set {s.name}: an agent or venue index outside the plan")
+            order = torch.argsort(agent, stable=True)
+            venue = venue[order].to(torch.int32).contiguous()
+            zero = torch.zeros(1, dtype=torch.int64, device=dev)
+            rowptr = torch.cat((zero, torch.cumsum(torch.bincount(agent, minlength=n), 0))).to(torch.int32).contiguous()
+        else:
+            return None
+        held[i] = (rowptr, venue)
+        return held[i]
+
+    def location_rows(self, edges=None):
+        """The ``gj_location_rows`` array of ``gj_location_stats``: every set's edges as CSR by owned agent
+        (``_agent_rows``), built on first use and kept with the plan (only the infection-location series asks for it).
+        A set that is neither held by the plan nor in ``edges`` gets no rows (it contributes nothing)."""
         if getattr(self, "_location_rows", None) is not None:
             return self._location_rows
-        dev, n = self.device, self.host.n_agents
         rows = (N.LocationRows * N.GJ_MAX_SETS)()
         keep = []
-        for i, s in enumerate(self.host.sets):
-            t = self.keep[i]
-            if t.get("a_rowptr") is not None:
-                rowptr, venue = t["a_rowptr"], t["a_venue"]
-            elif edges is not None and s.name in edges:
-                e = edges[s.name]
-                agent, venue = (e[0], e[1])
-                to = lambda a: (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))).to(dev)
-                agent, venue = to(agent).long(), to(venue)
-                if self.host.n_ext_agents > n:                       # halo agents' edges belong to another rank's rows
-                    own = agent < n
-                    agent, venue = agent[own], venue[own]
-                if agent.numel() and (int(agent.min()) < 0 or int(agent.max()) >= n or int(venue.min()) < 0
-                                      or int(venue.max()) >= s.n_venues):
-                    raise ValueError(f"edge set {s.name}: an agent or venue index outside the plan")
-                order = torch.argsort(agent, stable=True)
-                venue = venue[order].to(torch.int32).contiguous()
-                zero = torch.zeros(1, dtype=torch.int64, device=dev)
-                rowptr = torch.cat((zero, torch.cumsum(torch.bincount(agent, minlength=n), 0))).to(torch.int32).contiguous()
-            else:
+        for i in range(len(self.host.sets)):
+            built = self._agent_rows(i, edges)
+            if built is None:
                 continue
-            keep.append((rowptr, venue))
-            rows[i].a_rowptr, rows[i].a_venue = rowptr.data_ptr(), venue.data_ptr()
+            keep.append(built)
+            rows[i].a_rowptr, rows[i].a_venue = built[0].data_ptr(), built[1].data_ptr()
         self._location_rows_keep = keep
         self._location_rows = rows
         return rows
+
+    def contact_rows(self, names, edges=None):
+        """``[(rowptr, venue, n_venues), ...]`` of the edge sets ``names``, in that order: the by-agent rows that
+        ``gj_contact_mark`` / ``gj_contact_mask`` walk (``_agent_rows``: the arrays ``location_rows`` holds where they
+        exist, otherwise only the sets asked for are built, 4 B per edge of those sets).  A name that is no edge set of
+        the plan is a KeyError; a set whose edges are neither held nor in ``edges`` a ValueError."""
+        out = []
+        for name in names:
+            if name not in self.host.set_index:
+                raise KeyError(f"contact_quarantine: '{name}' is no edge set of the plan "
+                               f"(present: {sorted(self.host.set_index)})")
+            i = self.host.set_index[name]
+            built = self._agent_rows(i, edges)
+            if built is None:
+                raise ValueError(f"contact_quarantine: no edge list for the set '{name}'")
+            out.append((built[0], built[1], int(self.host.sets[i].n_venues)))
+        return out
 
     def venue_rows(self, edges=None):
         """The ``gj_venue_rows`` array of ``gj_infection_tree``: every set's edges as CSR by venue - the mirror of

@@ -8,6 +8,9 @@ arguments, YAML schema and ``apply`` signatures.  What reaches the kernels per s
                          kernels take one threshold (+inf when no policy is active)
   * CloseVenue        -> networks dropped from the step's list     (close_venue_policies.py:11-22)
 Not in the reference:
+  * ContactQuarantine -> a per-agent mask ``qstate`` (index cases and the complying members of the venues they marked,
+                         ``gj_contact_mark`` / ``gj_contact_mask``) that the step takes in the place of the stage, with
+                         the threshold 0.5
   * Vaccination       -> ``susceptibility[a] *= 1 - efficacy[band]`` for the agents a campaign's age-banded rollout
                          reaches in the step (``gj_vaccinate``); differentiable in the efficacy
 """
@@ -91,11 +94,64 @@ class Quarantine(Policy):
         return torch.ones(symptom_stages.shape, device=symptom_stages.device)
 
 
+#: Philox stream of ContactQuarantine policy c: bit 59 set, c below (bits 60 to 63 are the tree's, the vaccination's,
+#: the sampler's and the symptoms')
+QUARANTINE_STREAM = 1 << 59
+
+
+class ContactQuarantine(Quarantine):
+    """Not in the reference: a ``Quarantine`` that also keeps the contacts of its index cases away.  While it is active,
+    an agent with ``!(stage < stage_threshold)`` marks the venues it belongs to in the edge sets of ``contacts``
+    (``{edge set: days}``, e.g. ``{"household": 14}``) for ``days`` days from the step's ``timer.now`` - a venue stays
+    marked for ``days`` after the last step in which a member was symptomatic - and every complying member of a marked
+    venue is quarantined with the index cases.  ``compliance``: the share of agents who comply, a plain number in
+    [0, 1]; who complies is one Philox uniform per agent for the whole run (``u < fp32(compliance)``), not
+    differentiable.  The launches and their state live in ``QuarantinePolicies``."""
+
+    def __init__(self, start_date, end_date, stage_threshold, contacts, compliance=1.0, device="cpu"):
+        super().__init__(start_date, end_date, stage_threshold, device)
+        if not isinstance(contacts, dict) or not contacts:
+            raise ValueError("contact_quarantine: contacts is a non-empty mapping {edge set: days}")
+        self.contacts = {}
+        for name, days in contacts.items():
+            days = float(days)
+            if not days > 0.0:
+                raise ValueError(f"contact_quarantine: contacts['{name}'] = {days}, expected days > 0")
+            self.contacts[str(name)] = days
+        if isinstance(compliance, torch.Tensor) and compliance.requires_grad:
+            raise NotImplementedError("contact_quarantine: gradients w.r.t. the compliance are not implemented (pass a "
+                                      "plain number)")
+        self.compliance = float(compliance)
+        if not 0.0 <= self.compliance <= 1.0:
+            raise ValueError(f"contact_quarantine: compliance = {self.compliance}, expected a share in [0, 1]")
+
+    def window(self) -> str:
+        return f"[{self.start_date:%Y-%m-%d}, {self.end_date:%Y-%m-%d})"
+
+
+class ContactQuarantineError(RuntimeError):
+    """gj_contact_mark / gj_contact_mask met a row pointer or venue id outside its edge set."""
+
+
 class QuarantinePolicies(PolicyCollection):
+    """``apply`` records the step's threshold; ``contact_step`` - called next, by whoever launches the step - runs the
+    active ``ContactQuarantine`` (at most one: their windows must not overlap) and leaves the step's mask in
+    ``qstate`` (fp32 per agent: 0 free, 1 index case, 2 contact; None while no ``ContactQuarantine`` is active).  The
+    step then runs with ``launch_stage`` / ``launch_threshold`` in the place of the symptom stage and ``threshold``."""
+
     def __init__(self, policies):
         super().__init__(policies)
         self._stages = None
         self.threshold = math.inf
+        self.qstate = None
+        self.contact_policies = [p for p in self.policies if isinstance(p, ContactQuarantine)]
+        for i, a in enumerate(self.contact_policies):
+            for b in self.contact_policies[i + 1:]:
+                if a.start_date < b.end_date and b.start_date < a.end_date:
+                    raise ValueError(f"contact_quarantine: the windows {a.window()} and {b.window()} overlap")
+        self._contact = {}          # policy index -> what its launches need, allocated at its first active step
+        self._qstate_buffer = None
+        self._err = None
 
     def apply(self, symptom_stages, timer):
         """Records the step's threshold; the per-agent mask itself is formed inside the kernels
@@ -103,11 +159,90 @@ class QuarantinePolicies(PolicyCollection):
         self._stages = symptom_stages
         active = [float(p.stage_threshold) for p in self.policies if p.is_active(timer.date)]
         self.threshold = min(active) if active else math.inf
+        self.qstate = None
+
+    @property
+    def launch_threshold(self) -> float:
+        """The step's ``q_threshold``: 0.5 on ``qstate`` while a ``ContactQuarantine`` is active, else ``threshold``."""
+        return 0.5 if self.qstate is not None else self.threshold
+
+    def reset(self):
+        """Forget what a run marked: every ``until`` back to zero (never marked)."""
+        for held in self._contact.values():
+            for until in held["until"]:
+                until.zero_()
+        self.qstate = None
+
+    def _contact_state(self, c, policy, plan, edges):
+        held = self._contact.get(c)
+        if held is None or held["plan"] is not plan:
+            from . import _native as N
+
+            rows = plan.contact_rows(list(policy.contacts), edges() if callable(edges) else edges)
+            until = [torch.zeros(max(1, n_venues), dtype=torch.int32, device=plan.device) for _, _, n_venues in rows]
+            sets = (N.ContactSet * len(rows))()
+            for k, ((rowptr, venue, n_venues), u) in enumerate(zip(rows, until)):
+                sets[k].a_rowptr, sets[k].a_venue, sets[k].until = rowptr.data_ptr(), venue.data_ptr(), u.data_ptr()
+                sets[k].n_venues = n_venues
+            held = self._contact[c] = {"plan": plan, "rows": rows, "until": until, "sets": sets,
+                                       "days": list(policy.contacts.values())}
+        return held
+
+    def contact_step(self, plan, timer, seed, agent_offset=0, edges=None):
+        """Mark, then mask, for the ``ContactQuarantine`` active at ``timer.date``: returns ``qstate`` (and keeps it
+        until the next ``apply``), or None - nothing launched, nothing allocated - when none is active.  Call it after
+        ``apply``, on the ``current_stage`` the step starts from.  ``plan``: the step's ``DevicePlan``; ``seed``: the
+        run's Philox key; ``agent_offset``: the global id of local agent 0; ``edges``: the world's COO edge lists by set
+        name, or a callable that returns them (asked for only when the policy's by-agent rows have to be built)."""
+        self.qstate = None
+        for c, policy in enumerate(self.contact_policies):
+            if policy.is_active(timer.date):
+                break
+        else:
+            return None
+        from . import _native as N
+
+        now = float(timer.now)
+        if now < 0.0:
+            raise ValueError(f"contact_quarantine: timer.now = {now}, expected a time >= 0")
+        held = self._contact_state(c, policy, plan, edges)
+        dev, n = plan.device, plan.host.n_agents
+        stage = self._stages
+        if stage.dtype != torch.float32 or stage.device != dev or not stage.is_contiguous() or stage.requires_grad:
+            stage = stage.detach().to(device=dev, dtype=torch.float32).contiguous()
+        if stage.numel() != n:
+            raise ValueError(f"contact_quarantine: {stage.numel()} stages for {n} agents")
+        if self._qstate_buffer is None or self._qstate_buffer.numel() != n or self._qstate_buffer.device != dev:
+            self._qstate_buffer = torch.empty(n, dtype=torch.float32, device=dev)
+        if self._err is None or self._err.device != dev:
+            self._err = torch.zeros(1, dtype=torch.int32, device=dev)
+        sets = held["sets"]
+        for k, days in enumerate(held["days"]):
+            sets[k].release = now + days          # (ctypes rounds the double to fp32: once)
+        lib, stream = N.load(), N.current_stream()
+        N.check(lib.gj_contact_mark(n, N.ptr(stage), float(policy.stage_threshold), sets, len(sets), N.ptr(self._err),
+                                    stream), "gj_contact_mark")
+        N.check(lib.gj_contact_mask(n, N.ptr(stage), float(self.threshold), sets, len(sets), now, policy.compliance,
+                                    int(seed) & 0xFFFFFFFFFFFFFFFF, QUARANTINE_STREAM | c, int(agent_offset),
+                                    N.ptr(self._qstate_buffer), N.ptr(self._err), stream), "gj_contact_mask")
+        self.qstate = self._qstate_buffer
+        return self.qstate
+
+    def check(self, what: str = "contact quarantine") -> None:
+        """Raise if a launch since the last check met a row outside its edge set (one device read)."""
+        if self._err is None:
+            return
+        err = int(self._err.item()) & 0xFFFFFFFF
+        if err:
+            self._err.zero_()
+            raise ContactQuarantineError(f"{what}: a row pointer or venue id outside its edge set (it was skipped)")
 
     @property
     def quarantine_mask(self):
         if self._stages is None:
             return 1.0
+        if self.qstate is not None:
+            return (self.qstate < 0.5).to(torch.float)
         if math.isinf(self.threshold):
             return torch.ones(self._stages.shape, device=self._stages.device)
         return (self._stages < self.threshold).to(torch.float)
@@ -374,10 +509,12 @@ class Policies(torch.nn.Module):
             )
 
     def reset(self):
-        """Forget what a run applied (the vaccination ramps and dose counts): ``Runner.forward`` calls it next to
-        ``timer.reset()``."""
+        """Forget what a run applied (the vaccination ramps and dose counts, the venues a ``ContactQuarantine`` marked):
+        ``Runner.forward`` calls it next to ``timer.reset()``."""
         if self.vaccination_policies is not None:
             self.vaccination_policies.reset()
+        if self.quarantine_policies is not None and hasattr(self.quarantine_policies, "reset"):
+            self.quarantine_policies.reset()
 
     def vaccinate(self, data, timer, seed, agent_offset=0, all_reduce=None):
         """Move ``data["agent"].susceptibility`` for every campaign whose ramp rose since it was last applied

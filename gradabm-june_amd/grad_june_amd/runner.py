@@ -486,6 +486,31 @@ class Runner(torch.nn.Module):
         for name, stats in self._groups().items():
             stats.add(newly, newly, 2, self._vaccine_group_series[name][self._vaccine_row])
 
+    # contact-quarantine series: one gj_stage_stats pass on the step's mask for the nation and one per labelling ----------
+    def _contact_quarantine(self):
+        """The model's ``policies.QuarantinePolicies`` if it holds a ``ContactQuarantine``, else None (nothing is
+        recorded, nothing is allocated)."""
+        qp = getattr(self.model.policies, "quarantine_policies", None)
+        return qp if getattr(qp, "contact_policies", None) else None
+
+    def _quarantine_stats(self):
+        """{None or labelling name: groups.StageStats} over the mask's three values (0 free, 1 index case, 2 contact)."""
+        if getattr(self, "_q_stats", None) is None:
+            from .groups import StageStats
+
+            dev = require_hip(self.device)
+            self._q_stats = {None: StageStats(None, 1, 3, device=dev)}
+            for name, st in self._groups().items():
+                self._q_stats[name] = StageStats(st.labels, st.n_groups, 3, device=dev)
+        return self._q_stats
+
+    def _record_quarantined(self, qstate, row):
+        """The occupancy plane of gj_stage_stats on ``qstate``: exact int64 counts, so a by-group row sums to the national
+        row exactly.  A step in which no ``ContactQuarantine`` is active (``qstate`` None) leaves its row zero."""
+        if qstate is not None:
+            for key, stats in self._quarantine_stats().items():
+                stats.add(qstate, None, self._quarantine_series[key][row])
+
     # time loop --------------------------------------------------------------------------------------
     def forward(self):
         timer, model, data = self.timer, self.model, self.data
@@ -551,6 +576,17 @@ class Runner(torch.nn.Module):
                                                             device=require_hip(self.device))
                                           for name, st in groups.items()}
 
+        # contact-quarantine series (not in the reference), whenever the model has a ContactQuarantine policy: the agents
+        # the step's mask holds as index cases and as contacts, nationally and by every labelling.  Integer counts; row 0
+        # and the rows of steps without an active ContactQuarantine are zero (a plain Quarantine is not counted); no
+        # gradient
+        contact_quarantine = self._contact_quarantine()
+        self._quarantine_series = {}
+        if contact_quarantine is not None:
+            self._quarantine_series = {
+                key: torch.zeros(n_rows, 2, st.n_groups, 3, dtype=torch.int64, device=st.device)
+                for key, st in self._quarantine_stats().items()}
+
         def record(row, done=False):
             if not done:
                 self._record(data, row)
@@ -599,6 +635,8 @@ class Runner(torch.nn.Module):
                     campaigns.on_newly = None
             if campaigns is not None and campaigns.doses is not None:
                 self._vaccine_series[row].copy_(campaigns.doses)
+            if contact_quarantine is not None:      # the mask the step just ran with
+                self._record_quarantined(contact_quarantine.qstate, row)
             record(row, done=bool(sink and sink.get("done")))
             dates.append(timer.date)
         self._finalize_series(row + 1)
@@ -688,6 +726,14 @@ class Runner(torch.nn.Module):
             results["vaccine_doses_by_campaign"] = by_campaign
             for name, st in groups.items():
                 results[f"vaccine_doses_by_{name}"] = self._vaccine_group_series[name][: row + 1, : st.n_groups].clone()
+        if contact_quarantine is not None:      # int64 counts: [T] nationally, [T, G] by labelling
+            contact_quarantine.check("contact quarantine")
+            for key, st in self._quarantine_stats().items():
+                st.check("contact-quarantine series" + (f" by {key}" if key else ""))
+                counts = self._quarantine_series[key][: row + 1, 0]      # the occupancy plane, [T, G, 3]
+                tail = "per_timestep" if key is None else f"by_{key}"
+                results[f"quarantined_index_{tail}"] = counts[:, 0, 1] if key is None else counts[:, :, 1]
+                results[f"quarantined_contacts_{tail}"] = counts[:, 0, 2] if key is None else counts[:, :, 2]
         is_infected = data["agent"].is_infected
         if "original_index" in data["agent"]:
             out = torch.empty_like(is_infected)
@@ -722,6 +768,8 @@ class Runner(torch.nn.Module):
             saved = [c for st in self.stages_saved for c in (st, "new_" + st)]
             if f"vaccine_doses_by_{name}" in results:
                 saved.append("vaccine_doses")
+            if f"quarantined_index_by_{name}" in results:
+                saved += ["quarantined_index", "quarantined_contacts"]
             cols = {c: results[f"{c}_by_{name}"].detach().cpu().numpy().reshape(-1)
                     for c in ("cases", "daily_cases", "deaths", *saved)}
             pd.DataFrame({"date": np.repeat(np.asarray(results["dates"], dtype=object), len(keys)),

@@ -213,8 +213,10 @@ def _f32(store, key, device, n):
 
 
 def agent_buffers(engine: InfectionEngine, data, *, need_params: bool, need_stage: bool,
-                  need_infection_state: bool = True) -> AgentBuffers:
-    """Device views of ``data['agent']`` for one launch.  State tensors are used IN PLACE."""
+                  need_infection_state: bool = True, stage=None) -> AgentBuffers:
+    """Device views of ``data['agent']`` for one launch.  State tensors are used IN PLACE.  ``stage``: what the launch
+    takes as ``current_stage`` in the place of the symptom stage (a ``ContactQuarantine``'s mask), contiguous float32 on
+    the plan's device."""
     dev = engine.plan.device
     ag = data["agent"]
     n = engine.plan.host.n_agents
@@ -231,7 +233,11 @@ def agent_buffers(engine: InfectionEngine, data, *, need_params: bool, need_stag
     if "transmission" not in ag:
         ag["transmission"] = torch.zeros(n, dtype=torch.float32, device=dev)
     kw["transmission"] = _f32(ag, "transmission", dev, n)
-    if need_stage:
+    if stage is not None:
+        if stage.dtype != torch.float32 or stage.device != dev or not stage.is_contiguous() or stage.numel() != n:
+            raise ValueError(f"stage: expected {n} contiguous float32 values on {dev}")
+        kw["current_stage"] = stage
+    elif need_stage:
         stage = ag["symptoms"]["current_stage"]
         if stage.dtype != torch.float32 or stage.device != dev or not stage.is_contiguous():
             stage = stage.detach().to(device=dev, dtype=torch.float32).contiguous()   # copy for this call

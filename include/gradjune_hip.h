@@ -846,6 +846,47 @@ int gj_adjoint_vaccinate(int64_t n, const uint8_t* agent_class, const gj_vaccina
                          double* contrib_workspace, double* partial_workspace, double* grad_efficacy, float* g_in,
                          void* hip_stream);
 
+/* ---- contact quarantine: the household and venue contacts of symptomatic agents stay away ----------------------------
+ * A pure addition to ABI 7 (not in the reference, whose Quarantine isolates the symptomatic agent alone).  Two launches
+ * BEFORE a step turn its current_stage into a per-agent mask `qstate` that the step then takes in the place of the stage,
+ * with q_threshold = 0.5; the step's kernels do not change.  Per traced edge set the caller keeps one uint32 per venue,
+ * `until`: the fp32 bit pattern of the time up to which the venue's members are held, 0 = never marked.  The values are
+ * non-negative, so their order as unsigned integers is their order as floats.
+ *   gj_contact_mark:  for every agent a with !(current_stage[a] < stage_threshold)  (a NaN stage is an index case, as in
+ *                     the step), every set s and every venue v of a in s:  until_s[v] = max(until_s[v], bits(release_s))
+ *                     - an unsigned integer atomic max: exact, and no order of the agents shows.  release_s =
+ *                     fp32(now + days_s) is formed once by the host; only index agents walk their rows.
+ *   gj_contact_mask:  qstate[a] = 1   if !(current_stage[a] < q_threshold)                              (index case)
+ *                               = 2   else if u < compliance and float(until_s[v]) > now for a venue v of a in a set s
+ *                               = 0   otherwise                                                         (free)
+ *                     u = infection_uniform(seed, stream, agent_offset + a): ONE uniform per agent for the whole run, as
+ *                     gj_vaccinate draws it; the caller keeps `stream` apart from the other streams (policies.py: bit 59
+ *                     set, the policy's index below).  Index agents and agents that do not comply walk no row.
+ * The kernels only compare, so a numpy restatement gives their bits (tests/gj_contact_ref.py).  The stage is read
+ * coalesced, four agents per lane where the per-agent arrays are 16-byte aligned (mask: and agent_offset is a multiple of
+ * 4, the quad then shares one Philox block), one per lane otherwise; both forms give the same bits.
+ * a_rowptr / a_venue: the set's edges as CSR by owned agent (gj_location_rows' arrays); a_venue holds a_rowptr[n]
+ * entries.  Bad input never becomes an index: a row that is negative, decreasing or beyond a_rowptr[n], and a venue id
+ * outside [0, n_venues), is skipped and sets GJ_CONTACT_ERR_ROWS.  *err (device uint32) is sticky until the caller
+ * clears it.
+ * Returns GJ_E_RANGE for n < 0, agent_offset < 0, n_sets outside 1 .. GJ_MAX_SETS, an n_venues outside 0 .. INT32_MAX
+ * and (mark) a release that is negative or NaN; GJ_E_NULL for a NULL `sets`, `err`, array of a set, or per-agent array
+ * with n > 0 - all before any device work.  n == 0 launches nothing.                                                    */
+#define GJ_CONTACT_ERR_ROWS 4u
+typedef struct gj_contact_set {
+  const int32_t* a_rowptr;     /* device [n + 1]: the set's edges as CSR by owned agent (gj_location_rows' arrays) */
+  const int32_t* a_venue;      /* device [edges]                                                                  */
+  uint32_t* until;             /* device [n_venues]                                                               */
+  int64_t n_venues;
+  float release;               /* fp32(now + days) of this launch (gj_contact_mask does not read it)              */
+} gj_contact_set;
+int gj_contact_mark(int64_t n, const float* current_stage, float stage_threshold,
+                    const gj_contact_set* sets /* host */, int32_t n_sets, uint32_t* err, void* stream);
+int gj_contact_mask(int64_t n, const float* current_stage, float q_threshold,
+                    const gj_contact_set* sets /* host */, int32_t n_sets, float now, float compliance,
+                    uint64_t seed, uint64_t stream, int64_t agent_offset, float* qstate, uint32_t* err,
+                    void* hip_stream);
+
 /* d loss / d log_beta of the networks on ONE edge set, from the forward's and the transposed passes' per-venue sums:
  *   col0 + k :  ln(10) * scale * sum_v [p_contact[v] > 0]  cum_fwd[v][k] * cum_bwd[v][k] / (beta[k] * p_contact[v]) * weight[v]
  * (reference: autograd through base.py:36-42,78-83; `weights` - fp64 [n_venues] or NULL = 1 - is a rank's share of
