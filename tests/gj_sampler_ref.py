@@ -44,6 +44,10 @@ error of the fp32 D bounded in (1), 10 u (5.25 L + rp (1 + q) + 1), or at the ex
 rows go through the same operations: not infected).  On the other points the reference takes the decision it is given.
 A point is LOOSE where B exceeds 1 % of |ts_bar|: still held to K * B, to the sign and to the NaN and zero rules, but it
 says little about the kernel.
+
+The step's own a7 - a9 (tests/test_gpu_epilogue_kernels.py) take from here: ``prob_reference`` (p in fp64 and the bound
+an fp32 evaluation is allowed), ``step_points`` (the forward points as the ts an agent of the step must be given, and the
+in-step edges), ``forward_decision`` on the p the device wrote, and ``infect_unfused``.
 """
 import functools
 
@@ -317,3 +321,90 @@ def infect_time_fused(st, nu):
     values is exact in fp64, and the fp64 sum is rounded to fp32 once."""
     d = (F32(st["now"]) - st["time"]).astype(F32)
     return (st["time"].astype(np.float64) + np.asarray(nu, dtype=np.float64) * d.astype(np.float64)).astype(F32)
+
+
+# ---- the step's own a7 - a9: not_infected_prob, and the points of the in-step drive -----------------------------------------
+STEP_DTS = (0.25, 1.0, 2.0)              # the in-step drive's full point sets; EDGE_DTS[0] = 0.01 takes the edges only
+EXPF_ULP = 1.0                           # expf's maximum error in ulp, as the HIP math API documentation states it
+SUBNORMAL = 2.0 ** -149
+
+
+def prob_reference(ts, dt):
+    """(p64, bound) of a7 per agent.  p64 = clip(exp(-clip(ts, 1e-6f, 100f) * dt), 0, 1) in fp64 from the fp32 ``ts`` and
+    the fp32 ``dt`` (a NaN stays NaN, as clamp_keep_nan keeps it; the clamp of ts is exact in every precision).  What an
+    fp32 evaluation is allowed, from the number formats, with x = clip(ts) * dt:
+      the product x rounds once: an absolute error u x of the exponent, which moves exp(-x) by x u relative;
+      expf is EXPF_ULP ulp off, an ulp being at most 2 u of the value;  one final rounding, u (the clamp to [0, 1] is exact);
+      below 2^-126 the result is a subnormal number with a quantum of 2^-149.
+        bound = u p64 (x + 2 EXPF_ULP + 1) + 2^-149
+    (rp of the adjoint's bound above is the same count without the final rounding: there p is an intermediate.)"""
+    ts = np.asarray(ts, dtype=F32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        c = np.where(np.isnan(ts), ts, np.minimum(np.maximum(ts, TS_LO), TS_HI)).astype(np.float64)
+        x = c * float(F32(dt))
+        p = np.exp(-x)
+        p = np.where(np.isnan(p), p, np.minimum(np.maximum(p, 0.0), 1.0))
+        bound = U * p * (x + 2.0 * EXPF_ULP + 1.0) + SUBNORMAL
+    return p, np.nan_to_num(bound, nan=0.0)
+
+
+def prob_f32(ts, dt):
+    """a7 op for op in fp32: not_infected_prob of csrc/gj_device.h, with expf the correctly rounded one - the fp64
+    exponential of the fp32 product, rounded once.  (numpy's own float32 exp is measured up to 2.1 ulp off on [0.01, 5]:
+    more than the one ulp the bound grants the device's expf, so it cannot stand in for it.)"""
+    ts = np.asarray(ts, dtype=F32)
+    with np.errstate(invalid="ignore", over="ignore", under="ignore"):
+        c = np.where(np.isnan(ts), ts, np.minimum(np.maximum(ts, TS_LO), TS_HI)).astype(F32)
+        p = np.exp(-(c * F32(dt)).astype(F32).astype(np.float64)).astype(F32)
+        return np.where(np.isnan(p), p, np.minimum(np.maximum(p, F32(0.0)), F32(1.0))).astype(F32)
+
+
+def step_edges():
+    """The in-step edges as (kind, ts, e0, e1): ts at and beyond both clamp bounds (p == 0 at dt = 2, a subnormal p at
+    dt = 1, p == 1 at dt = 0.01), a NaN ts, the tiled sums' saturation value with both signs, -0.0 and a negative ts
+    (both clamp to 1e-6); draws of 0 and a subnormal draw on a ts in the core (placed by step_points: ts * dt = 1)."""
+    rows = []
+    for kind, values in (("ts_hi", (TS_HI, _na(TS_HI, True), F32(150.0))), ("ts_lo", (TS_LO, _na(TS_LO, False), F32(5e-7))),
+                         ("ts_nan", (F32(np.nan),)), ("ts_sat", (F32(1e30), F32(-1e30))),
+                         ("ts_neg", (F32(-0.0), F32(-1.0)))):
+        for ts in values:
+            for e0, e1 in ((1.0, 1.0), (0.5, 2.0), (2.0, 0.5)):
+                rows.append((kind, ts, e0, e1))
+    return rows
+
+
+@functools.lru_cache(maxsize=None)
+def step_points(dt, grid=True, n_random=1500, seed=5):
+    """The points of forward_points - the grid's p's x DRAWS, the random rows, the ties and the named draws - as the
+    TARGET ts = -ln(p) / dt an agent of the step must be given at this ``dt`` (fp32; p == 0 asks for +inf, which the
+    clamp takes as 100), when ``grid``; then the in-step edges.  Cached: callers leave the arrays unchanged."""
+    rows = []
+    dt32 = float(F32(dt))
+    if grid:
+        fp = forward_points(n_random, seed)
+        with np.errstate(divide="ignore"):
+            ts = (-np.log(fp["p"].astype(np.float64)) / dt32).astype(F32)
+        for k, t, e0, e1 in zip(fp["kinds"], ts, fp["e0"], fp["e1"]):
+            if k != "p_edge":                       # p in {0, 1, NaN} as an input: the in-step edges below take their place
+                rows.append((k, t, e0, e1))
+    rows += step_edges()
+    mid = F32(1.0 / dt32)
+    rows += [("draw0", mid, 0.0, 1.0), ("draw0", mid, 1.0, 0.0), ("draw0", mid, 0.0, 0.0),
+             ("draw_sub", mid, 1e-40, 1.0), ("draw_sub", mid, 1.0, 1e-40), ("draw_sub", mid, 1e-40, 2e-40)]
+    col = lambda i: np.array([r[i] for r in rows], dtype=F32)
+    return {"kinds": [r[0] for r in rows], "n": len(rows), "dt": dt32, "ts": col(1), "e0": col(2), "e1": col(3)}
+
+
+def moved(p, ulps):
+    """p moved by ``ulps`` units in the last place, inside [0, 1]; a NaN stays"""
+    p = np.asarray(p, dtype=F32).copy()
+    for _ in range(abs(ulps)):
+        p = np.nextafter(p, F32(np.inf if ulps > 0 else -np.inf), dtype=F32)
+    return np.where(np.isnan(p), p, np.minimum(np.maximum(p, F32(0.0)), F32(1.0))).astype(F32)
+
+
+def unsafe_share(p, e0, e1):
+    """(share, unsafe, safe, ruled, nu64) of forward_decision on the probabilities ``p``"""
+    nu64, safe, ruled = forward_decision({"p": np.asarray(p, dtype=F32), "e0": e0, "e1": e1})
+    unsafe = ~safe & ~ruled
+    return float(unsafe.mean()), unsafe, safe, ruled, nu64

@@ -251,11 +251,16 @@ def outputs(engine, w, p, device, x=None, susc=None, stage=None, want=("trans_su
     return bufs, io, out
 
 
-def drive_a(engine, w, cums, device, *, day_type, transpose, has_q, **kw):
+def write_cums(engine, cums):
+    """The chosen arrays into plan.cum_of(set), in place."""
     for name, c in cums.items():
         dst = engine.plan.cum_of(name)
         assert tuple(dst.shape) == c.shape
         dst.copy_(torch.from_numpy(c))
+
+
+def drive_a(engine, w, cums, device, *, day_type, transpose, has_q, **kw):
+    write_cums(engine, cums)
     p = params_of(engine, day_type, transpose, has_q)
     bufs, io, out = outputs(engine, w, p, device, **kw)
     engine.step_phase(bufs, p, io, 6)

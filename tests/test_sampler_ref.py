@@ -7,7 +7,10 @@ grad_susc_out 0.47 (ts * dt = 0.1, draws (0.3, 0.31)), grad_time_out 0 (exact). 
 constant taken from a measurement, and the measurement is of the restatement, not of a kernel.  The loose points (B
 above 1 % of |ts_bar|) are 24 %, 31 %, 30 % and 23 % of the grids' points with a non-zero reference, all of them at
 ts * dt < 1e-3, above 10, or with a draw pair whose softmax term y0 * y1 is below 1e-33; the cap is 35 %.  The
-decision is unsafe on 4 of the 3294 points (ts = 100 and +inf at dt = 2: p is below fp32's range altogether)."""
+decision is unsafe on 4 of the 3294 points (ts = 100 and +inf at dt = 2: p is below fp32's range altogether).
+
+The step's a7 (prob_reference / prob_f32) and the in-step points (step_points) are checked at the end of the file: the
+fp32 restatement of p reaches 0.453 of its bound, and 0.27 % of the step points are unsafe once p is 2 ulp off."""
 import math
 
 import numpy as np
@@ -207,3 +210,92 @@ def test_state_update_restatement(fwd):
     assert moved.mean() > 0.25
     frac = np.full(fp["n"], 0.7, dtype=np.float32)
     assert (R.infect_time_fused(st, frac) != R.infect_unfused(st, frac)[2]).mean() > 0.1
+
+
+# ---- the step's own a7 - a9 ------------------------------------------------------------------------------------------
+ALL_STEP_DTS = R.STEP_DTS + R.EDGE_DTS[:1]
+
+
+def prob_excess(ts, dt):
+    p64, bound = R.prob_reference(ts, dt)
+    p32 = R.prob_f32(ts, dt)
+    q, ok = R.excess(p32, p64, bound)
+    assert ok.all(), (dt, np.nonzero(~ok)[0].tolist())
+    assert np.array_equal(np.isnan(p32), np.isnan(ts))
+    v, i = R.worst(q)
+    print(f"dt {dt:.4g}: {len(ts)} points, max err / bound = {v:.3f} at ts = {float(ts[i]):.6g} (p = {float(p64[i]):.9g})")
+    return v
+
+
+def test_prob_restatement_within_k_ref_of_its_bound():
+    """not_infected_prob restated in fp32 stays within K_REF x the bound of prob_reference on every in-step point, at
+    every dt of the in-step drive; NaN exactly where ts is NaN; the edges give the values they are named for.
+    Measured: max err / bound 0.453 (ts = 100 at dt = 1: the subnormal p), 0.38 on the normal numbers.
+    On the sampler grid's own ts (clamp edges, core, absolute) at its dts it is held to the bound itself, K: a correctly
+    rounded evaluation errs by at most u p (x + r / 2), r = ulp(p) / (u p) in (1, 2], that is up to (x + 1) / (x + 3) of
+    the bound - below 1 everywhere, but above K_REF from x = 2 on where the product rounds badly (the step points' targets
+    at dt = 1 / 24, which is no dt of the in-step drive, reach 0.501 at ts * dt = 2.04).  Measured on the grid: 0.453."""
+    top = (0.0, None)
+    for dt in ALL_STEP_DTS:
+        sp = R.step_points(dt)
+        assert np.isnan(sp["ts"]).sum() == 3
+        v = prob_excess(sp["ts"], dt)
+        if v > top[0]:
+            top = (v, dt)
+        assert v <= R.K_REF, dt
+    grid_top = 0.0
+    for dt in R.DTS:
+        grid = [R.F32(c / R.F32(dt)) for c in R.CORE] + R.clamp_edges() + [R.F32(t) for t in R.ABSOLUTE]
+        grid_top = max(grid_top, prob_excess(np.array(grid, dtype=np.float32), dt))
+    assert grid_top <= R.K
+    print(f"sampler grid: max err / bound {grid_top:.3f}; asserted {R.K}")
+    print(f"not_infected_prob, fp32 restatement: max err / bound {top[0]:.3f} at dt {top[1]:.4g}; asserted {R.K_REF}")
+    # the in-step edges
+    at = lambda dt, kind: R.prob_f32(R.step_points(dt)["ts"][kind_mask(R.step_points(dt), kind)], dt)
+    assert (at(2.0, "ts_hi") == 0).all() and (at(0.01, "ts_lo") == 1).all()
+    sub = at(1.0, "ts_hi")
+    assert ((sub > 0) & (sub < R.FLT_MIN)).all()
+    assert np.isnan(at(1.0, "ts_nan")).all()
+    for dt in ALL_STEP_DTS:
+        lo = R.prob_f32(np.array([R.TS_LO]), dt)[0]
+        assert (at(dt, "ts_neg") == lo).all()                              # -0.0 and a negative ts clamp to 1e-6
+        sat = at(dt, "ts_sat")                                             # +1e30 clamps to 100, -1e30 to 1e-6
+        assert (sat[:3] == R.prob_f32(np.array([R.TS_HI]), dt)[0]).all() and (sat[3:] == lo).all()
+
+
+def test_step_points_are_the_forward_points_as_target_ts():
+    fp = R.forward_points()
+    keep = np.array([k != "p_edge" for k in fp["kinds"]])
+    for dt in R.STEP_DTS:
+        sp = R.step_points(dt)
+        n = int(keep.sum())
+        assert sp["kinds"][:n] == [k for k in fp["kinds"] if k != "p_edge"]
+        assert np.array_equal(sp["e0"][:n], fp["e0"][keep]) and np.array_equal(sp["e1"][:n], fp["e1"][keep])
+        # the target gives the p back to a few ulp: |d ln p| = dt * ts * 2^-24 from the rounding of ts, and exp's own
+        p = R.prob_f32(sp["ts"][:n], dt).astype(np.float64)
+        want = fp["p"][keep].astype(np.float64)
+        inside = (sp["ts"][:n] >= R.TS_LO) & (sp["ts"][:n] <= R.TS_HI)
+        assert inside.mean() > 0.95
+        assert (np.abs(p - want)[inside] <= 4 * R.U * want[inside] * (3.0 - np.log(want[inside]))).all()
+        kinds = set(sp["kinds"])
+        assert {"grid", "random", "tie", "draw0", "draw_sub", "ts_hi", "ts_lo", "ts_nan", "ts_sat", "ts_neg"} <= kinds
+        d0 = kind_mask(sp, "draw0") | kind_mask(sp, "draw_sub")
+        assert ((sp["e0"][d0] == 0) | (sp["e1"][d0] == 0)).sum() >= 6 and (sp["e0"][d0] == np.float32(1e-40)).any()
+    assert R.step_points(0.01, False)["n"] < 60
+
+
+def test_unsafe_share_of_the_step_points_is_a_condition_of_the_inputs():
+    """MAX_UNSAFE_SHARE holds for the step points whatever the last bits of the device's p: with p rebuilt from the target
+    ts through fp32 exp and moved by -2, 0 and +2 ulp the unsafe share stays under the cap at every dt of the in-step
+    drive (the exact tie p == 0.5, e0 == e1 survives the detour through ts at dt = 1 only: elsewhere those rows are
+    unsafe, and they are most of what is)."""
+    for dt in R.STEP_DTS:
+        sp = R.step_points(dt)
+        p = R.prob_f32(sp["ts"], dt)
+        shares = []
+        for ulps in (-2, 0, 2):
+            share, unsafe, safe, ruled, _ = R.unsafe_share(R.moved(p, ulps), sp["e0"], sp["e1"])
+            shares.append(share)
+            assert share <= R.MAX_UNSAFE_SHARE, (dt, ulps, share)
+            assert ruled.sum() >= 15 and safe.mean() > 0.95
+        print(f"dt {dt:.4g}: {sp['n']} points, unsafe share at -2 / 0 / +2 ulp: " + " / ".join(f"{s:.4%}" for s in shares))
