@@ -450,6 +450,230 @@ __global__ __launch_bounds__(kThreads) void k_adjoint_vaccinate_agents(const Vac
   }
 }
 
+// Waning immunity (include/gradjune_hip.h, gj_immunity_step / gj_adjoint_immunity): streaming, per agent, after a step.
+// ONE definition of the rule, shared by the update and the numpy restatement the tests hold it to; the adjoint replays
+// the update's decisions from its flags.
+constexpr int kImmunityTable = 2 * kVaccineAges;
+static_assert(sizeof(gj_immunity_tables) == kImmunityTable * sizeof(float), "gj_immunity_tables: two packed tables");
+constexpr uint32_t kImmunityWaned = 1, kImmunityReinfected = 2;
+
+// tab = cap | keep; ends with a barrier
+__device__ __forceinline__ void immunity_stage_tables(const gj_immunity_tables& T, float* tab) {
+  const float* src = reinterpret_cast<const float*>(&T);
+  for (int i = threadIdx.x; i < kImmunityTable; i += blockDim.x) tab[i] = src[i];
+  __syncthreads();
+}
+__device__ __forceinline__ bool immunity_wanes(const float* tab, int cls, float stage, float recovered, float nw) {
+  return stage == recovered && !(nw != 0.0f) && tab[kVaccineAges + cls % kVaccineAges] != 1.0f;
+}
+// s' = cap - (cap - s) * keep: three fp32 operations (the build keeps them apart: -ffp-contract=off)
+__device__ __forceinline__ float immunity_relax(const float* tab, int cls, float s) {
+  const int age = cls % kVaccineAges;
+  const float cap = tab[age];
+  const float gap = cap - s;
+  return cap - gap * tab[kVaccineAges + age];
+}
+// a newly infected agent that had an infection before: the step's increment is undone
+__device__ __forceinline__ bool immunity_reinfected(float nw, float& inf) {
+  const float before = inf - nw;
+  if (!(before >= 1.0f)) return false;
+  inf = before;
+  return true;
+}
+// the agent's term of susc_sum_out: exact scaling and truncation; a NaN counts 0 (fmaxf returns the number)
+__device__ __forceinline__ uint64_t immunity_fixed(float s) {
+  return (uint64_t)(int64_t)(fminf(fmaxf(s, 0.0f), 4.0f) * 1073741824.0f);
+}
+
+struct ImmunityArgs {
+  gj_immunity_tables T;
+  int64_t n;
+  const uint8_t* cls;
+  const float* stage;
+  float recovered;
+  const float* new_inf;        // [n] or NULL (nobody)
+  float* susc;
+  float* inf;
+  uint8_t* flags;              // [n] or NULL
+  float* reinf;                // [n] or NULL
+  unsigned long long* count;   // [1] or NULL
+  unsigned long long* susc_sum;  // [1] or NULL
+  int32_t vec4;                // the fp32 arrays given 16-byte, cls and flags 4-byte aligned
+};
+
+// k_vaccinate's shape: workgroups of 1024 lanes, at most 512 of them, one integer atomic per output and workgroup.
+__global__ __launch_bounds__(kVaccineThreads) void k_immunity(const ImmunityArgs S) {
+  __shared__ float tab[kImmunityTable];
+  __shared__ uint32_t part_cnt[kVaccineThreads / kWave];
+  __shared__ uint64_t part_sum[kVaccineThreads / kWave];
+  immunity_stage_tables(S.T, tab);
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const bool want_sum = S.susc_sum != nullptr;
+  uint32_t cnt = 0;            // (a lane meets n / (lanes of the grid) agents: far below 2^32)
+  uint64_t sum = 0;            // (at most 2^32 an agent)
+  int64_t first_scalar = 0;
+  if (S.vec4) {
+    const int64_t n4 = S.n >> 2;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+      const uint32_t cl = reinterpret_cast<const uint32_t*>(S.cls)[i];
+      const float4 st = reinterpret_cast<const float4*>(S.stage)[i];
+      const float4 nw = S.new_inf ? reinterpret_cast<const float4*>(S.new_inf)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+      const int c0 = (int)(cl & 0xFF), c1 = (int)((cl >> 8) & 0xFF), c2 = (int)((cl >> 16) & 0xFF), c3 = (int)(cl >> 24);
+      const bool w0 = immunity_wanes(tab, c0, st.x, S.recovered, nw.x), w1 = immunity_wanes(tab, c1, st.y, S.recovered, nw.y);
+      const bool w2 = immunity_wanes(tab, c2, st.z, S.recovered, nw.z), w3 = immunity_wanes(tab, c3, st.w, S.recovered, nw.w);
+      const bool any_w = w0 || w1 || w2 || w3;
+      if (any_w || want_sum) {      // most agents are not recovered: their susceptibility is not read
+        float4 s = reinterpret_cast<const float4*>(S.susc)[i];
+        if (any_w) {
+          if (w0) s.x = immunity_relax(tab, c0, s.x);
+          if (w1) s.y = immunity_relax(tab, c1, s.y);
+          if (w2) s.z = immunity_relax(tab, c2, s.z);
+          if (w3) s.w = immunity_relax(tab, c3, s.w);
+          reinterpret_cast<float4*>(S.susc)[i] = s;
+        }
+        if (want_sum) sum += immunity_fixed(s.x) + immunity_fixed(s.y) + immunity_fixed(s.z) + immunity_fixed(s.w);
+      }
+      bool r0 = false, r1 = false, r2 = false, r3 = false;
+      if (nw.x != 0.0f || nw.y != 0.0f || nw.z != 0.0f || nw.w != 0.0f) {      // few lanes hold a new infection
+        float4 f = reinterpret_cast<const float4*>(S.inf)[i];
+        if (nw.x != 0.0f) r0 = immunity_reinfected(nw.x, f.x);
+        if (nw.y != 0.0f) r1 = immunity_reinfected(nw.y, f.y);
+        if (nw.z != 0.0f) r2 = immunity_reinfected(nw.z, f.z);
+        if (nw.w != 0.0f) r3 = immunity_reinfected(nw.w, f.w);
+        if (r0 || r1 || r2 || r3) reinterpret_cast<float4*>(S.inf)[i] = f;
+      }
+      if (S.flags)
+        reinterpret_cast<uint32_t*>(S.flags)[i] =
+            ((uint32_t)w0 | (uint32_t)r0 << 1) | ((uint32_t)w1 | (uint32_t)r1 << 1) << 8 |
+            ((uint32_t)w2 | (uint32_t)r2 << 1) << 16 | ((uint32_t)w3 | (uint32_t)r3 << 1) << 24;
+      if (S.reinf)
+        reinterpret_cast<float4*>(S.reinf)[i] =
+            make_float4(r0 ? 1.0f : 0.0f, r1 ? 1.0f : 0.0f, r2 ? 1.0f : 0.0f, r3 ? 1.0f : 0.0f);
+      cnt += (uint32_t)r0 + (uint32_t)r1 + (uint32_t)r2 + (uint32_t)r3;
+    }
+    first_scalar = n4 << 2;
+  }
+  for (int64_t a = first_scalar + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; a < S.n; a += stride) {
+    const int cls = (int)S.cls[a];
+    const float nw = S.new_inf ? S.new_inf[a] : 0.0f;
+    const bool w = immunity_wanes(tab, cls, S.stage[a], S.recovered, nw);
+    if (w || want_sum) {
+      float s = S.susc[a];
+      if (w) S.susc[a] = s = immunity_relax(tab, cls, s);
+      if (want_sum) sum += immunity_fixed(s);
+    }
+    bool r = false;
+    if (nw != 0.0f) {
+      float f = S.inf[a];
+      r = immunity_reinfected(nw, f);
+      if (r) S.inf[a] = f;
+    }
+    if (S.flags) S.flags[a] = (uint8_t)((uint32_t)w | (uint32_t)r << 1);
+    if (S.reinf) S.reinf[a] = r ? 1.0f : 0.0f;
+    cnt += (uint32_t)r;
+  }
+  // the workgroup's sums: a wave sum, the waves' sums through LDS, one integer atomic per output where it is not zero
+  cnt = wave_sum(cnt);
+  sum = wave_sum(sum);
+  if (threadIdx.x % kWave == 0) {
+    part_cnt[threadIdx.x / kWave] = cnt;
+    part_sum[threadIdx.x / kWave] = sum;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long c = 0, v = 0;
+    for (int w = 0; w < kVaccineThreads / kWave; ++w) {
+      c += part_cnt[w];
+      v += part_sum[w];
+    }
+    if (S.count && c) atomicAdd(S.count, c);
+    if (S.susc_sum && v) atomicAdd(S.susc_sum, v);
+  }
+}
+
+// The adjoint's per-agent launch: the three per-agent gradients and the agent's terms of sum_A and sum_B into the
+// workspace that the seed's two summing kernels then reduce, each in the order of the band's gj_seed_plan.
+struct ImmunityAdjArgs {
+  gj_immunity_tables T;
+  int64_t n;
+  const uint8_t* flags;
+  const uint8_t* cls;
+  const float* susc0;
+  const float* g_susc;         // [n] or NULL (zeros)
+  const float* g_inf;          // [n] or NULL (zeros)
+  const int32_t* band;         // [n]
+  int32_t n_bands;
+  int32_t vec4;                // every array given 16-byte (flags, cls: 4-byte) aligned, contrib_b too
+  double* contrib_a;           // [n]
+  double* contrib_b;           // [n]
+  float* g_susc_in;            // [n] or NULL
+  float* g_inf_in;             // [n] or NULL
+  float* g_new;                // [n] or NULL
+};
+
+// s' = cap - (cap - s0) * keep where waned: d / d s0 = keep, d / d keep = -(cap - s0), d / d cap = 1 - keep.
+// cap - s0 is the forward's fp32 difference; its product with g is exact in fp64.  A label outside [0, n_bands) is no
+// band: no term, never an index.
+__device__ __forceinline__ void immunity_adjoint_agent(const float* tab, uint32_t flag, int cls, float s0, float gs,
+                                                       float gi, int32_t band, int32_t n_bands, double& ca, double& cb,
+                                                       float& gs_in, float& gn) {
+  const int age = cls % kVaccineAges;
+  const bool waned = (flag & kImmunityWaned) != 0;
+  gs_in = waned ? gs * tab[kVaccineAges + age] : gs;
+  gn = (flag & kImmunityReinfected) ? -gi : 0.0f;
+  const bool term = waned && (uint32_t)band < (uint32_t)n_bands;
+  const float gap = tab[age] - s0;
+  ca = term ? (double)gs * (double)gap : 0.0;
+  cb = term ? (double)gs : 0.0;
+}
+
+__global__ __launch_bounds__(kThreads) void k_adjoint_immunity_agents(const ImmunityAdjArgs S) {
+  __shared__ float tab[kImmunityTable];
+  immunity_stage_tables(S.T, tab);
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  int64_t first_scalar = 0;
+  if (S.vec4) {
+    const int64_t n4 = S.n >> 2;
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+      const uint32_t fl = reinterpret_cast<const uint32_t*>(S.flags)[i];
+      const uint32_t cl = reinterpret_cast<const uint32_t*>(S.cls)[i];
+      const float4 s = reinterpret_cast<const float4*>(S.susc0)[i];
+      const float4 gs = S.g_susc ? reinterpret_cast<const float4*>(S.g_susc)[i] : zero;
+      const float4 gi = S.g_inf ? reinterpret_cast<const float4*>(S.g_inf)[i] : zero;
+      const int4 b = reinterpret_cast<const int4*>(S.band)[i];
+      double a0, a1, a2, a3, b0, b1, b2, b3;
+      float4 go, gn;
+      immunity_adjoint_agent(tab, fl & 0xFF, (int)(cl & 0xFF), s.x, gs.x, gi.x, b.x, S.n_bands, a0, b0, go.x, gn.x);
+      immunity_adjoint_agent(tab, (fl >> 8) & 0xFF, (int)((cl >> 8) & 0xFF), s.y, gs.y, gi.y, b.y, S.n_bands, a1, b1,
+                             go.y, gn.y);
+      immunity_adjoint_agent(tab, (fl >> 16) & 0xFF, (int)((cl >> 16) & 0xFF), s.z, gs.z, gi.z, b.z, S.n_bands, a2, b2,
+                             go.z, gn.z);
+      immunity_adjoint_agent(tab, fl >> 24, (int)(cl >> 24), s.w, gs.w, gi.w, b.w, S.n_bands, a3, b3, go.w, gn.w);
+      reinterpret_cast<double2*>(S.contrib_a)[2 * i] = make_double2(a0, a1);
+      reinterpret_cast<double2*>(S.contrib_a)[2 * i + 1] = make_double2(a2, a3);
+      reinterpret_cast<double2*>(S.contrib_b)[2 * i] = make_double2(b0, b1);
+      reinterpret_cast<double2*>(S.contrib_b)[2 * i + 1] = make_double2(b2, b3);
+      if (S.g_susc_in) reinterpret_cast<float4*>(S.g_susc_in)[i] = go;
+      if (S.g_inf_in) reinterpret_cast<float4*>(S.g_inf_in)[i] = gi;
+      if (S.g_new) reinterpret_cast<float4*>(S.g_new)[i] = gn;
+    }
+    first_scalar = n4 << 2;
+  }
+  for (int64_t a = first_scalar + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; a < S.n; a += stride) {
+    double ca, cb;
+    float go, gn;
+    const float gi = S.g_inf ? S.g_inf[a] : 0.0f;
+    immunity_adjoint_agent(tab, S.flags[a], (int)S.cls[a], S.susc0[a], S.g_susc ? S.g_susc[a] : 0.0f, gi, S.band[a],
+                           S.n_bands, ca, cb, go, gn);
+    S.contrib_a[a] = ca;
+    S.contrib_b[a] = cb;
+    if (S.g_susc_in) S.g_susc_in[a] = go;
+    if (S.g_inf_in) S.g_inf_in[a] = gi;
+    if (S.g_new) S.g_new[a] = gn;
+  }
+}
+
 // psi(x) = d lgamma / dx (torch.digamma, the derivative torch's autograd gives lgamma), for the adjoint of the profile's
 // 1 / Gamma(shape).  x < 0: reflection psi(x) = psi(1 - x) - pi / tan(pi x), NaN at the poles; x == 0: -inf (torch:
 // copysign(inf, -x)).  x > 0: the recurrence psi(x) = psi(x + 1) - 1/x up to x >= 6, then the asymptotic series to

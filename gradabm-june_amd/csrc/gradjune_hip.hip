@@ -1461,6 +1461,73 @@ int gj_adjoint_vaccinate(int64_t n, const uint8_t* agent_class, const gj_vaccina
   return gj::seed_sum_launch(R, (hipStream_t)hip_stream);
 }
 
+// waning immunity: the tables are copied into the launch's arguments, as gj_vaccinate's are
+int gj_immunity_step(int64_t n, const uint8_t* agent_class, const gj_immunity_tables* tables, const float* current_stage,
+                     int32_t recovered_stage, const float* new_infected, float* susceptibility, float* is_infected,
+                     uint8_t* flags_out, float* reinfected_out, int64_t* count_out, int64_t* susc_sum_out,
+                     void* hip_stream) {
+  if (n < 0 || recovered_stage < 0 || recovered_stage >= GJ_MAX_STAGES) return GJ_E_RANGE;
+  if (n == 0) return GJ_OK;
+  if (!agent_class || !tables || !current_stage || !susceptibility || !is_infected) return GJ_E_NULL;
+  gj::ImmunityArgs A;
+  A.T = *tables;
+  A.n = n;
+  A.cls = agent_class;
+  A.stage = current_stage;
+  A.recovered = (float)recovered_stage;
+  A.new_inf = new_infected;
+  A.susc = susceptibility;
+  A.inf = is_infected;
+  A.flags = flags_out;
+  A.reinf = reinfected_out;
+  A.count = reinterpret_cast<unsigned long long*>(count_out);
+  A.susc_sum = reinterpret_cast<unsigned long long*>(susc_sum_out);
+  A.vec4 = (gj::aligned16(current_stage, new_infected, susceptibility, is_infected, reinfected_out) &&
+            (uintptr_t)agent_class % 4 == 0 && (uintptr_t)flags_out % 4 == 0) ? 1 : 0;
+  return gj::launch(gj::k_immunity, gj::grid_for(gj::vec4_lanes(n, A.vec4), gj::kVaccineBlocks, gj::kVaccineThreads),
+                    gj::kVaccineThreads, 0, (hipStream_t)hip_stream, A);
+}
+
+int gj_adjoint_immunity(int64_t n, const uint8_t* flags, const uint8_t* agent_class, const gj_immunity_tables* tables,
+                        const float* susceptibility0, const float* g_susc, const float* g_inf, const int32_t* band,
+                        int32_t n_bands, const gj_seed_plan* plan, double* contrib_workspace, double* partial_workspace,
+                        double* sum_A, double* sum_B, float* g_susc_in, float* g_inf_in, float* g_new,
+                        void* hip_stream) {
+  if (n < 0 || n_bands < 1 || n_bands > GJ_MAX_GROUPS) return GJ_E_RANGE;
+  if (!sum_A || !sum_B || !plan) return GJ_E_NULL;
+  gj::SeedSumArgs RA, RB;
+  if (const int rc = gj::seed_sum_args(plan, n, n_bands, contrib_workspace, partial_workspace, sum_A, RA)) return rc;
+  if (const int rc = gj::seed_sum_args(plan, n, n_bands, contrib_workspace ? contrib_workspace + n : nullptr,
+                                       partial_workspace ? partial_workspace + RA.n_chunks : nullptr, sum_B, RB))
+    return rc;
+  if (n > 0) {
+    if (!flags || !agent_class || !tables || !susceptibility0 || !band) return GJ_E_NULL;
+    gj::ImmunityAdjArgs A;
+    A.T = *tables;
+    A.n = n;
+    A.flags = flags;
+    A.cls = agent_class;
+    A.susc0 = susceptibility0;
+    A.g_susc = g_susc;
+    A.g_inf = g_inf;
+    A.band = band;
+    A.n_bands = n_bands;
+    A.contrib_a = contrib_workspace;
+    A.contrib_b = contrib_workspace + n;
+    A.g_susc_in = g_susc_in;
+    A.g_inf_in = g_inf_in;
+    A.g_new = g_new;
+    A.vec4 = (gj::aligned16(susceptibility0, g_susc, g_inf, g_susc_in, g_inf_in, g_new) && gj::aligned16(band) &&
+              gj::aligned16(A.contrib_a, A.contrib_b) && (uintptr_t)agent_class % 4 == 0 && (uintptr_t)flags % 4 == 0)
+                 ? 1 : 0;
+    const int rc = gj::launch(gj::k_adjoint_immunity_agents, gj::grid_for(gj::vec4_lanes(n, A.vec4), 2048), gj::kThreads,
+                              0, (hipStream_t)hip_stream, A);
+    if (rc) return rc;
+  }
+  if (const int rc = gj::seed_sum_launch(RA, (hipStream_t)hip_stream)) return rc;
+  return gj::seed_sum_launch(RB, (hipStream_t)hip_stream);
+}
+
 namespace gj {
 // the sets of gj_contact_mark / gj_contact_mask, checked and copied into the launch's arguments (the caller's array may
 // change after the call returns); `marking`: the release time is read, and must be a non-negative number

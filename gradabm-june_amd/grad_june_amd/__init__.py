@@ -6,6 +6,7 @@ Exports the reference package's names (grad_june/__init__.py:1-9) so that
 HDF5 file (vectorised; needs ``h5py`` for ``.h5`` input).
 """
 from .graph import HeteroData, ToUndirected, load_world, save_world  # noqa: F401
+from .immunity import Immunity  # noqa: F401
 from .infection import IsInfectedSampler  # noqa: F401
 from .june_world_loader import AgentDataLoader, GraphLoader  # noqa: F401
 from .infection_networks import InfectionNetworks  # noqa: F401

@@ -239,6 +239,13 @@ class VaccinateTables(C.Structure):
     ]
 
 
+class ImmunityTables(C.Structure):
+    _fields_ = [
+        ("cap", C.c_float * 100),
+        ("keep", C.c_float * 100),
+    ]
+
+
 class ContactSet(C.Structure):
     _fields_ = [
         ("a_rowptr", _vp),
@@ -286,6 +293,15 @@ SYMBOLS = {
         C.c_int,
         [C.c_int64, _vp, C.POINTER(VaccinateTables), C.c_uint64, C.c_uint64, C.c_int64, _vp, _vp, _vp, C.c_int32,
          C.POINTER(SeedPlan), _vp, _vp, _vp, _vp, _vp],
+    ),
+    "gj_immunity_step": (
+        C.c_int,
+        [C.c_int64, _vp, C.POINTER(ImmunityTables), _vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    ),
+    "gj_adjoint_immunity": (
+        C.c_int,
+        [C.c_int64, _vp, _vp, C.POINTER(ImmunityTables), _vp, _vp, _vp, _vp, C.c_int32, C.POINTER(SeedPlan), _vp, _vp,
+         _vp, _vp, _vp, _vp, _vp, _vp],
     ),
     "gj_contact_mark": (
         C.c_int, [C.c_int64, _vp, C.c_float, C.POINTER(ContactSet), C.c_int32, _vp, _vp]),

@@ -568,6 +568,69 @@ class VaccinationStep(torch.autograd.Function):
         return None, grad_eff, (None if g_in is None else g_in.to(ctx.susc_device))
 
 
+class ImmunityStep(torch.autograd.Function):
+    """One launch of the waning-immunity rule as an autograd node (``immunity.Immunity.step``): (half_life [B],
+    residual_protection [B], susceptibility, is_infected, new_infected) -> (susceptibility', is_infected').  Forward =
+    ``gj_immunity_step`` on fresh tensors, keeping its ``flags`` and the incoming susceptibility (5 B per agent and step);
+    backward = ``gj_adjoint_immunity``, which sums ``sum_A`` / ``sum_B`` per band in fp64 in the order of the bands'
+    ``SeedPlan``; the host turns them into the two gradients in doubles.  ``env``: agent classes, per-age tables, the stage
+    and the index of ``recovered``, ``dt``, the optional outputs ``reinfected`` / ``count`` / ``susc_sum``, ``band`` with
+    its ``plan`` and - on a rank of a partitioned world - ``all_reduce`` (as ``VaccinationStep``)."""
+
+    @staticmethod
+    def forward(ctx, env, half_life, residual, susc, inf, new_infected):
+        dev = env["cls"].device
+        susc0, nw = _f32(susc, dev), _f32(new_infected, dev)
+        out_s, out_i = susc0.clone(), _f32(inf, dev).clone()
+        flags = torch.empty(out_s.numel(), dtype=torch.uint8, device=dev)
+        N.check(N.load().gj_immunity_step(out_s.numel(), N.ptr(env["cls"]), env["tables"], N.ptr(env["stage"]),
+                                          env["recovered"], N.ptr(nw), N.ptr(out_s), N.ptr(out_i), N.ptr(flags),
+                                          N.ptr(env["reinfected"]), N.ptr(env["count"]), N.ptr(env["susc_sum"]),
+                                          N.current_stream()), "gj_immunity_step")
+        ctx.env = {k: env[k] for k in ("cls", "tables", "dt", "band", "plan", "all_reduce")}
+        ctx.values = (half_life.detach().to(torch.float32).cpu().tolist(), residual.detach().to(torch.float32).cpu().tolist())
+        ctx.like = [(t.device, t.dtype, t.shape) for t in (half_life, residual)]
+        ctx.devices = (susc.device, inf.device, new_infected.device)
+        ctx.save_for_backward(susc0, flags)
+        return out_s, out_i
+
+    @staticmethod
+    def backward(ctx, g_susc, g_inf):
+        import math
+
+        env = ctx.env
+        susc0, flags = ctx.saved_tensors
+        plan, dev, n = env["plan"], susc0.device, susc0.numel()
+        g_susc, g_inf = _f32(g_susc, dev), _f32(g_inf, dev)
+        B = plan.n_groups
+        contrib = torch.empty(max(1, 2 * n), dtype=torch.float64, device=dev)
+        partial = torch.empty(max(1, 2 * plan.n_chunks), dtype=torch.float64, device=dev)
+        sums = torch.empty(2, B, dtype=torch.float64, device=dev)
+        want_s, want_i, want_n = ctx.needs_input_grad[3:6]
+        gs_in = torch.empty(n, dtype=torch.float32, device=dev) if want_s else None
+        gn = torch.empty(n, dtype=torch.float32, device=dev) if want_n else None
+        N.check(N.load().gj_adjoint_immunity(n, N.ptr(flags), N.ptr(env["cls"]), env["tables"], N.ptr(susc0),
+                                             N.ptr(g_susc), N.ptr(g_inf), N.ptr(env["band"]), B, C.byref(plan.c),
+                                             N.ptr(contrib), N.ptr(partial), N.ptr(sums[0]), N.ptr(sums[1]),
+                                             N.ptr(gs_in), None, N.ptr(gn), N.current_stream()), "gj_adjoint_immunity")
+        grads = [None, None]
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            if env.get("all_reduce") is not None:
+                sums = env["all_reduce"](sums.reshape(-1)).reshape(2, B)      # fp64: the world's sums on every rank
+            sum_a, sum_b = sums.cpu().tolist()
+            dt, (hs, _) = env["dt"], ctx.values
+            keep = [2.0 ** (-dt / h) for h in hs]
+            d_h = [0.0 if math.isinf(h) else -a * k * math.log(2.0) * dt / (h * h) for a, k, h in zip(sum_a, keep, hs)]
+            d_r = [-b * (1.0 - k) for b, k in zip(sum_b, keep)]
+            for i, d in enumerate((d_h, d_r)):
+                if ctx.needs_input_grad[1 + i]:
+                    like_dev, like_dtype, like_shape = ctx.like[i]
+                    grads[i] = torch.tensor(d, dtype=torch.float64).to(device=like_dev, dtype=like_dtype).reshape(like_shape)
+        if want_i and g_inf is None:
+            g_inf = torch.zeros(n, dtype=torch.float32, device=dev)
+        return (None, *grads, *_to_devices((gs_in, g_inf if want_i else None, gn), ctx.devices))
+
+
 class SymptomsStep(torch.autograd.Function):
     """(new_infected, current_stage, next_stage, time_to_next_stage) -> the three updated arrays, with the
     reference's gradient paths (symptoms.py:98,105-124,231-236): a loss on the stages - the deaths series of

@@ -225,10 +225,14 @@ class DistributedRunner(Runner):
         # (the series by agent group too: the labels were encoded on the whole world before the partition cut it, so the
         # columns are the same on every rank; the symptom-stage counts are int64 and go the same way)
         # (the vaccination doses too: every rank counted its own agents' - int64 by campaign, fp64 by group)
+        # (and the immunity series: int64 [rows, 2] reinfections and susceptibility sums, fp64 reinfections by group)
         vaccine = getattr(self, "_vaccine_series", None)
+        immunity = getattr(self, "_immunity_series", None)
         for series in [self._series, *getattr(self, "_group_series", {}).values(),
                        *getattr(self, "_stage_series", {}).values(), *([vaccine] if vaccine is not None else []),
-                       *getattr(self, "_vaccine_group_series", {}).values()]:
+                       *getattr(self, "_vaccine_group_series", {}).values(),
+                       *([immunity] if immunity is not None else []),
+                       *getattr(self, "_reinfection_group_series", {}).values()]:
             if dist.get_backend(self.group) == "gloo":            # tests: staged through the host
                 host = series[:n_rows].cpu()
                 dist.all_reduce(host, group=self.group)

@@ -11,6 +11,7 @@ import math
 import torch
 import yaml
 
+from .immunity import Immunity
 from .infection import IsInfectedSampler
 from .infection_networks import InfectionNetworks
 from .policies import Policies
@@ -20,12 +21,13 @@ from .world import agent_buffers, engine_for, require_hip
 
 
 class GradJune(torch.nn.Module):
-    def __init__(self, symptoms_updater=None, policies=None, infection_networks=None, device="cuda:0"):
+    def __init__(self, symptoms_updater=None, policies=None, infection_networks=None, device="cuda:0", immunity=None):
         super().__init__()
         self.symptoms_updater = symptoms_updater if symptoms_updater is not None else SymptomsUpdater.from_file()
         self.policies = policies if policies is not None else Policies.from_file()
         self.infection_networks = (infection_networks if infection_networks is not None
                                    else InfectionNetworks.from_file())
+        self.immunity = immunity    # immunity.Immunity, or None: nothing wanes, nothing is launched
         self.transmission_updater = TransmissionUpdater()
         self.is_infected_sampler = IsInfectedSampler()
         self.device = device
@@ -35,6 +37,7 @@ class GradJune(torch.nn.Module):
         self.location_stats = None  # see forward()
         self.infector_stats = None  # see forward()
         self.tree_stats = None      # see forward()
+        self.immunity_stats = None  # see forward()
 
     @classmethod
     def from_file(cls, fpath=None):
@@ -52,6 +55,7 @@ class GradJune(torch.nn.Module):
             policies=Policies.from_parameters(params),
             infection_networks=InfectionNetworks.from_parameters(params),
             device=params["system"]["device"],
+            immunity=Immunity.from_parameters(params),
         )
 
     def infect_people(self, data, timer, new_infected):
@@ -246,6 +250,15 @@ class GradJune(torch.nn.Module):
         sink = getattr(self, "tree_stats", None)
         if sink is not None:
             self._record_tree(sink, data, new_infected)
+        # waning immunity: after the records above (they read the step's own outcome) and before the symptoms update,
+        # so the stage is still the one the step started from.  immunity_stats: set by the Runner for its time loop -
+        # the launch's optional outputs.  Without an Immunity nothing is launched
+        immunity = getattr(self, "immunity", None)
+        if immunity is not None:
+            sink = getattr(self, "immunity_stats", None) or {}
+            immunity.step(data, timer.duration, new_infected, reinfected_out=sink.get("reinfected"),
+                          count_out=sink.get("count"), susc_sum_out=sink.get("susc_sum"),
+                          all_reduce=self._vaccination_env()[1])
         # in grad mode new_infected stays on the graph: the symptoms update is then an autograd node too
         # (autograd.SymptomsStep), which is what makes the deaths series differentiable (runner.py:198-215)
         # step_stats: set by the Runner for the duration of its time loop - the per-step result reductions

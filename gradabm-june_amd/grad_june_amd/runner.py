@@ -480,6 +480,10 @@ class Runner(torch.nn.Module):
         vp = getattr(self.model.policies, "vaccination_policies", None)
         return vp if vp is not None and len(vp.policies) else None
 
+    def _immunity(self):
+        """The model's ``immunity.Immunity``, or None without the ``immunity`` key (nothing is recorded)."""
+        return getattr(self.model, "immunity", None)
+
     def _record_newly(self, campaign, newly):
         """``VaccinationPolicies.on_newly``: this launch's newly vaccinated, added by group to the current row (the
         cases half of gj_group_stats' output; no stage equals the ``dead`` given, so the other half stays zero)."""
@@ -529,14 +533,15 @@ class Runner(torch.nn.Module):
         else:
             n_rows = 4096
         self._series = torch.zeros(n_rows, 2 + n_bins, dtype=torch.float64, device=require_hip(self.device))
-        # differentiable run (a log_beta is an nn.Parameter, a profile tensor, the seed or a vaccination efficacy requires
-        # a gradient, grad mode on): the case series must stay on the autograd graph, so they are formed with tensor ops
+        # differentiable run (a log_beta is an nn.Parameter, a profile tensor, the seed, a vaccination efficacy or an
+        # immunity parameter requires a gradient, grad mode on): the case series must stay on the autograd graph, so they are formed with tensor ops
         # instead of the fused reduction kernel
         campaigns = self._campaigns()
         differentiable = torch.is_grad_enabled() and (any(
             isinstance(n.log_beta, torch.Tensor) and n.log_beta.requires_grad
             for n in model.infection_networks.networks.values()) or profile_requires_grad(data)
-            or self._seed_requires_grad() or (campaigns is not None and campaigns.requires_grad()))
+            or self._seed_requires_grad() or (campaigns is not None and campaigns.requires_grad())
+            or (self._immunity() is not None and self._immunity().requires_grad()))
         diff_rows = []
         groups = self._groups()
         self._group_series = {name: torch.zeros(n_rows, 2 * st.n_groups, dtype=torch.float64,
@@ -587,6 +592,22 @@ class Runner(torch.nn.Module):
                 key: torch.zeros(n_rows, 2, st.n_groups, 3, dtype=torch.int64, device=st.device)
                 for key, st in self._quarantine_stats().items()}
 
+        # waning-immunity series (not in the reference), whenever the model has an Immunity: each step's reinfections -
+        # the launch's own count, and by every labelling gj_group_stats on its 0 / 1 mask - and the population's
+        # susceptibility after the launch as an exact fixed-point sum.  Integer counts, so a by-group row sums to the
+        # national row exactly; row 0 of the reinfections is zero, that of the susceptibility comes from one launch that
+        # moves nobody; no gradient
+        immunity = self._immunity()
+        self._immunity_series, self._reinfection_group_series, reinfected = None, {}, None
+        if immunity is not None:
+            dev = require_hip(self.device)
+            self._immunity_series = torch.zeros(n_rows, 2, dtype=torch.int64, device=dev)      # reinfections, susc_sum
+            self._reinfection_group_series = {name: torch.zeros(n_rows, 2 * st.n_groups, dtype=torch.float64, device=dev)
+                                              for name, st in groups.items()}
+            if groups:
+                reinfected = torch.empty(self.n_agents, dtype=torch.float32, device=dev)
+            immunity.measure(data, self._immunity_series[0, 1:2])
+
         def record(row, done=False):
             if not done:
                 self._record(data, row)
@@ -624,9 +645,13 @@ class Runner(torch.nn.Module):
                     series[row].copy_(series[row - 1])
                 self._vaccine_row = row
                 campaigns.on_newly = self._record_newly if groups else None
+            if immunity is not None:
+                model.immunity_stats = {"reinfected": reinfected, "count": self._immunity_series[row, 0:1],
+                                        "susc_sum": self._immunity_series[row, 1:2]}
             try:
                 data = model(data, timer)
             finally:
+                model.immunity_stats = None
                 model.step_stats = None
                 model.location_stats = None
                 model.infector_stats = None
@@ -635,6 +660,9 @@ class Runner(torch.nn.Module):
                     campaigns.on_newly = None
             if campaigns is not None and campaigns.doses is not None:
                 self._vaccine_series[row].copy_(campaigns.doses)
+            if reinfected is not None:      # this step's mask, by group (the cases half of gj_group_stats' output)
+                for name, stats in groups.items():
+                    stats.add(reinfected, reinfected, 2, self._reinfection_group_series[name][row])
             if contact_quarantine is not None:      # the mask the step just ran with
                 self._record_quarantined(contact_quarantine.qstate, row)
             record(row, done=bool(sink and sink.get("done")))
@@ -726,6 +754,12 @@ class Runner(torch.nn.Module):
             results["vaccine_doses_by_campaign"] = by_campaign
             for name, st in groups.items():
                 results[f"vaccine_doses_by_{name}"] = self._vaccine_group_series[name][: row + 1, : st.n_groups].clone()
+        if immunity is not None:      # counts as float64: exact; the susceptibility: sum / 2^30 in fp64, then float32
+            counts = self._immunity_series[: row + 1].t()
+            results["reinfections_per_timestep"] = counts[0].to(torch.float64)
+            results["susceptibility_per_timestep"] = (counts[1].to(torch.float64) / float(1 << 30)).to(torch.float32)
+            for name, st in groups.items():
+                results[f"reinfections_by_{name}"] = self._reinfection_group_series[name][: row + 1, : st.n_groups].clone()
         if contact_quarantine is not None:      # int64 counts: [T] nationally, [T, G] by labelling
             contact_quarantine.check("contact quarantine")
             for key, st in self._quarantine_stats().items():
@@ -768,6 +802,8 @@ class Runner(torch.nn.Module):
             saved = [c for st in self.stages_saved for c in (st, "new_" + st)]
             if f"vaccine_doses_by_{name}" in results:
                 saved.append("vaccine_doses")
+            if f"reinfections_by_{name}" in results:
+                saved.append("reinfections")
             if f"quarantined_index_by_{name}" in results:
                 saved += ["quarantined_index", "quarantined_contacts"]
             cols = {c: results[f"{c}_by_{name}"].detach().cpu().numpy().reshape(-1)

@@ -846,6 +846,60 @@ int gj_adjoint_vaccinate(int64_t n, const uint8_t* agent_class, const gj_vaccina
                          double* contrib_workspace, double* partial_workspace, double* grad_efficacy, float* g_in,
                          void* hip_stream);
 
+/* ---- waning immunity: recovered agents become susceptible again, differentiable in half-life and residual ----------
+ * A pure addition to ABI 7 (not in the reference, where an infected agent's susceptibility stays 0 for good).  One
+ * launch AFTER a step and BEFORE the symptoms update, on the stage the step started from.  Per agent, with
+ * age = agent_class % 100 and nu = new_infected[a] != 0 (new_infected NULL: nobody):
+ *   reinfected = nu && is_infected[a] - new_infected[a] >= 1          (the agent had an infection before this one)
+ *       is_infected[a] -= new_infected[a]      the step's increment is undone (exact in fp32), so is_infected stays the
+ *                                               0 / 1 flag the transmission profile multiplies by
+ *   waned = current_stage[a] == recovered_stage && !nu && keep[age] != 1
+ *       susceptibility[a] = cap[age] - (cap[age] - susceptibility[a]) * keep[age]      three fp32 operations, no contraction
+ *   everybody else: nothing is written.  A NaN stage is not recovered; a NaN susceptibility stays NaN; a value above cap
+ *   relaxes downward; there is no clamp.
+ * The two per-age tables are formed by the host, each value rounded once: keep = fp32(2^(-dt / half_life)) (1 for an
+ * infinite half-life and for an age in no band) and cap = fp32(1 - fp64(fp32(residual_protection))).  From 0 at recovery
+ * the susceptibility is cap * (1 - 2^(-(t - t_rec) / half_life)) whatever the step lengths.  The kernel only subtracts and
+ * multiplies, so a numpy float32 restatement gives its bits (tests/gj_immunity_ref.py).
+ * Optional outputs (each may be NULL: not written):
+ *   flags_out       device uint8 [n]: bit 0 waned, bit 1 reinfected (what gj_adjoint_immunity replays)
+ *   reinfected_out  device fp32 [n], 0 / 1
+ *   count_out       device int64 [1]: the launch ADDS its number of reinfected agents
+ *   susc_sum_out    device int64 [1]: the launch ADDS sum over agents of (int64)(fmin(fmax(s', 0), 4) * 2^30), s' the
+ *                   susceptibility after the launch (NaN counts 0).  Scaling and truncation are exact and the sum is an
+ *                   integer one: no order shows.  With it every agent's susceptibility is read.
+ * susceptibility is loaded only where a lane holds a waning agent (or susc_sum_out is given) and stored only where a lane
+ * changed it; is_infected is loaded only by lanes that hold a new infection.  Four agents per lane where the fp32 arrays
+ * are 16-byte and agent_class / flags_out 4-byte aligned, one per lane otherwise; both forms give the same bits.      */
+typedef struct gj_immunity_tables {
+  float cap[100];              /* per age: 1 - residual_protection of the age's band (1 for an age in no band)      */
+  float keep[100];             /* per age: 2^(-dt / half_life) (1: the age does not wane)                          */
+} gj_immunity_tables;
+int gj_immunity_step(int64_t n, const uint8_t* agent_class, const gj_immunity_tables* tables /* host */,
+                     const float* current_stage, int32_t recovered_stage, const float* new_infected,
+                     float* susceptibility, float* is_infected, uint8_t* flags_out, float* reinfected_out,
+                     int64_t* count_out, int64_t* susc_sum_out, void* hip_stream);
+
+/* gj_adjoint_immunity: adjoint of gj_immunity_step w.r.t. its three per-agent inputs and, per band, the two sums the
+ * host turns into d loss / d half_life and d loss / d residual_protection.  flags: the forward's flags_out;
+ * susceptibility0: the PRE-update values; g_susc / g_inf: the cotangents of the updated arrays (device fp32 [n], NULL =
+ * zeros); band: device int32 [n], or a label outside [0, n_bands) for none.
+ *   g_susc_in[a] = waned ? g_susc[a] * keep[age] : g_susc[a]       g_inf_in[a] = g_inf[a]
+ *   g_new[a]     = reinfected ? -g_inf[a] : 0                       (fp32; each of the three may be NULL: not written)
+ *   sum_A[b] = sum over waned agents of band b of g_susc[a] * (cap[age] - susceptibility0[a])     (device double [n_bands])
+ *   sum_B[b] = sum over waned agents of band b of g_susc[a]                                      (device double [n_bands])
+ * so that, with keep = 2^(-dt / h):  d loss / d h = -sum_A * keep * ln 2 * dt / h^2,  d loss / d r = -sum_B * (1 - keep).
+ * cap - susceptibility0 is the forward's fp32 difference; its product with g_susc is formed in fp64, where the product
+ * of two fp32 values is exact.  The terms are summed without atomics in the order `plan` fixes, through gj_adjoint_seed's
+ * two summing kernels, once for each sum: two launches on the same inputs give the same bits.  An agent with no band
+ * contributes nothing and its label is never used as an index.  contrib_workspace: device double [2 * n] (A's terms,
+ * then B's); partial_workspace: device double [2 * plan->n_chunks].                                                   */
+int gj_adjoint_immunity(int64_t n, const uint8_t* flags, const uint8_t* agent_class,
+                        const gj_immunity_tables* tables /* host */, const float* susceptibility0, const float* g_susc,
+                        const float* g_inf, const int32_t* band, int32_t n_bands, const gj_seed_plan* plan,
+                        double* contrib_workspace, double* partial_workspace, double* sum_A, double* sum_B,
+                        float* g_susc_in, float* g_inf_in, float* g_new, void* hip_stream);
+
 /* ---- contact quarantine: the household and venue contacts of symptomatic agents stay away ----------------------------
  * A pure addition to ABI 7 (not in the reference, whose Quarantine isolates the symptomatic agent alone).  Two launches
  * BEFORE a step turn its current_stage into a per-agent mask `qstate` that the step then takes in the place of the stage,
