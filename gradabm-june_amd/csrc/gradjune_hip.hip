@@ -25,6 +25,7 @@
 #include "gj_infector.h"
 #include "gj_tree.h"
 #include "gj_contact.h"
+#include "gj_testing.h"
 
 namespace gj {
 
@@ -1587,6 +1588,82 @@ int gj_contact_mask(int64_t n, const float* current_stage, float q_threshold, co
   A.vec4 = (agent_offset % 4 == 0 && gj::aligned16(current_stage, qstate)) ? 1 : 0;
   return gj::launch(gj::k_contact_mask, gj::grid_for(gj::vec4_lanes(n, A.vec4), gj::kContactBlocks), gj::kThreads, 0,
                     (hipStream_t)hip_stream, A);
+}
+
+// testing: the tables are copied into the launch's arguments, as gj_vaccinate's are
+int gj_testing_step(int64_t n, const uint8_t* agent_class, const gj_testing_tables* tables, const float* current_stage,
+                    const float* infection_time, float stage_threshold, int32_t active, float now, float q_threshold,
+                    float isolate_release, float compliance, uint64_t seed, uint64_t decide_stream,
+                    uint64_t comply_stream, int64_t agent_offset, uint32_t* decided, float* result_time, float* positive,
+                    float* isolate_until, float* confirmed_time, float* newly_confirmed_out, float* qstate_out,
+                    uint8_t* flags_out, int64_t* counts_out, void* hip_stream) {
+  if (n < 0 || agent_offset < 0 || !(now >= 0.0f) || (decide_stream & 0xFFFFFFFFull)) return GJ_E_RANGE;
+  if (n == 0) return GJ_OK;
+  if (!tables) return GJ_E_NULL;
+  if (tables->n_delays < 1 || tables->n_delays > GJ_TESTING_MAX_DELAYS) return GJ_E_RANGE;
+  if (qstate_out && !isolate_until) return GJ_E_NULL;
+  if (!agent_class || !current_stage || !infection_time || !decided || !result_time || !positive || !confirmed_time)
+    return GJ_E_NULL;
+  gj::TestingArgs A;
+  A.T = *tables;
+  A.n = n;
+  A.cls = agent_class;
+  A.stage = current_stage;
+  A.inf_time = infection_time;
+  A.decided = decided;
+  A.result_time = result_time;
+  A.positive = positive;
+  A.isolate_until = isolate_until;
+  A.confirmed_time = confirmed_time;
+  A.newly = newly_confirmed_out;
+  A.qstate = qstate_out;
+  A.flags = flags_out;
+  A.counts = reinterpret_cast<unsigned long long*>(counts_out);
+  A.seed = seed;
+  A.decide_stream = decide_stream;
+  A.comply_stream = comply_stream;
+  A.agent_offset = agent_offset;
+  A.threshold = stage_threshold;
+  A.q_threshold = q_threshold;
+  A.now = now;
+  A.release = isolate_release;
+  A.compliance = compliance;
+  A.active = active ? 1 : 0;
+  A.vec4 = (gj::aligned16(current_stage, infection_time, result_time, isolate_until, newly_confirmed_out, qstate_out) &&
+            (uintptr_t)decided % 16 == 0 && (uintptr_t)agent_class % 4 == 0 && (uintptr_t)flags_out % 4 == 0) ? 1 : 0;
+  return gj::launch(gj::k_testing_step, gj::grid_for(gj::vec4_lanes(n, A.vec4), gj::kVaccineBlocks, gj::kVaccineThreads),
+                    gj::kVaccineThreads, 0, (hipStream_t)hip_stream, A);
+}
+
+int gj_adjoint_testing(int64_t n, const uint8_t* flags, const float* current_stage, const float* g_y, const float* g_row,
+                       const int32_t* band, int32_t n_bands, const gj_seed_plan* plan, double* contrib_workspace,
+                       double* partial_workspace, double* grad_probability, float* g_stage, float* g_y_in,
+                       void* hip_stream) {
+  if (n < 0 || n_bands < 1 || n_bands > GJ_MAX_GROUPS) return GJ_E_RANGE;
+  if (!grad_probability || !plan) return GJ_E_NULL;
+  gj::SeedSumArgs R;
+  if (const int rc = gj::seed_sum_args(plan, n, n_bands, contrib_workspace, partial_workspace, grad_probability, R))
+    return rc;
+  if (n > 0) {
+    if (!flags || !current_stage || !band) return GJ_E_NULL;
+    gj::TestingAdjArgs A;
+    A.n = n;
+    A.flags = flags;
+    A.stage = current_stage;
+    A.g_y = g_y;
+    A.g_row = g_row;
+    A.band = band;
+    A.n_bands = n_bands;
+    A.vec4 = (gj::aligned16(current_stage, g_y, g_stage, g_y_in) && gj::aligned16(band) &&
+              gj::aligned16(contrib_workspace) && (uintptr_t)flags % 4 == 0) ? 1 : 0;
+    A.contrib = contrib_workspace;
+    A.g_stage = g_stage;
+    A.g_y_in = g_y_in;
+    const int rc = gj::launch(gj::k_adjoint_testing, gj::grid_for(gj::vec4_lanes(n, A.vec4), 2048), gj::kThreads, 0,
+                              (hipStream_t)hip_stream, A);
+    if (rc) return rc;
+  }
+  return gj::seed_sum_launch(R, (hipStream_t)hip_stream);
 }
 
 int gj_adjoint_transmission(int64_t n, const gj_agent_state* st, float now, const float* trans_bar,

@@ -11,7 +11,7 @@ from .infection import IsInfectedSampler  # noqa: F401
 from .june_world_loader import AgentDataLoader, GraphLoader  # noqa: F401
 from .infection_networks import InfectionNetworks  # noqa: F401
 from .model import GradJune  # noqa: F401
-from .policies import Policies  # noqa: F401
+from .policies import Policies, Testing, TestingPolicies  # noqa: F401
 from .runner import Runner  # noqa: F401
 from .symptoms import SymptomsUpdater  # noqa: F401
 from .timer import Timer  # noqa: F401

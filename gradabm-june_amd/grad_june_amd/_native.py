@@ -256,6 +256,20 @@ class ContactSet(C.Structure):
     ]
 
 
+GJ_TESTING_MAX_DELAYS = 16
+GJ_TESTING_DECIDED, GJ_TESTING_POSITIVE, GJ_TESTING_DUE = 1, 2, 4
+
+
+class TestingTables(C.Structure):
+    _fields_ = [
+        ("probability", C.c_float * 100),
+        ("delay_cum", C.c_float * GJ_TESTING_MAX_DELAYS),
+        ("delay_days", C.c_float * GJ_TESTING_MAX_DELAYS),
+        ("n_delays", C.c_int32),
+        ("_pad", C.c_int32),
+    ]
+
+
 #: every symbol include/gradjune_hip.h declares: (restype, argtypes)
 SYMBOLS = {
     "gj_version": (C.c_int, []),
@@ -309,6 +323,15 @@ SYMBOLS = {
         C.c_int,
         [C.c_int64, _vp, C.c_float, C.POINTER(ContactSet), C.c_int32, C.c_float, C.c_float, C.c_uint64, C.c_uint64,
          C.c_int64, _vp, _vp, _vp],
+    ),
+    "gj_testing_step": (
+        C.c_int,
+        [C.c_int64, _vp, C.POINTER(TestingTables), _vp, _vp, C.c_float, C.c_int32, C.c_float, C.c_float, C.c_float,
+         C.c_float, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    ),
+    "gj_adjoint_testing": (
+        C.c_int,
+        [C.c_int64, _vp, _vp, _vp, _vp, _vp, C.c_int32, C.POINTER(SeedPlan), _vp, _vp, _vp, _vp, _vp, _vp],
     ),
     "gj_adjoint_beta_partial": (
         C.c_int,

@@ -631,6 +631,58 @@ class ImmunityStep(torch.autograd.Function):
         return (None, *grads, *_to_devices((gs_in, g_inf if want_i else None, gn), ctx.devices))
 
 
+class TestingStep(torch.autograd.Function):
+    """One launch of a ``Testing`` policy as an autograd node (``policies.TestingPolicies.step``): (probability [B],
+    current_stage, y) -> (y', row).  ``y`` is the policy's ``positive`` array on the graph: a deciding agent's ``y' =
+    hard * stage / stage.detach()``, everybody else's is the incoming one; ``row`` is the launch's newly confirmed cases,
+    ``sum due * y'``, a float32 scalar.  Forward = ``gj_testing_step`` on the policy's state, keeping its ``flags`` (1 B
+    per agent and step); backward = ``gj_adjoint_testing``, which sums the cotangents of the deciding agents per band in
+    fp64 in the order of the bands' ``SeedPlan`` (a straight-through estimator: ``d y / d probability := 1``) and hands
+    ``g * hard / stage`` to the stage.  ``env``: what ``policies.testing_launch`` takes, ``band`` with its ``plan`` and -
+    on a rank of a partitioned world - ``all_reduce`` (as ``VaccinationStep``)."""
+
+    @staticmethod
+    def forward(ctx, env, probability, stage, y):
+        from .policies import testing_launch
+
+        dev, n = env["cls"].device, env["n"]
+        flags = torch.empty(n, dtype=torch.uint8, device=dev)
+        counts = torch.zeros(2, dtype=torch.int64, device=dev)
+        testing_launch(dict(env, counts=counts), flags)
+        if env["counts"] is not None:
+            env["counts"].add_(counts)
+        ctx.env = {k: env[k] for k in ("band", "plan", "all_reduce")}
+        ctx.like = (probability.device, probability.dtype, probability.shape)
+        ctx.devices = (stage.device, y.device)
+        ctx.save_for_backward(env["stage"], flags)
+        return env["held"]["positive"].clone(), counts[0].to(torch.float32)
+
+    @staticmethod
+    def backward(ctx, g_y, g_row):
+        env = ctx.env
+        stage, flags = ctx.saved_tensors
+        plan, dev, n = env["plan"], stage.device, stage.numel()
+        g_y = _f32(g_y, dev)
+        g_row = None if g_row is None else _f32(g_row, dev).reshape(1)
+        B = plan.n_groups
+        contrib = torch.empty(max(1, n), dtype=torch.float64, device=dev)
+        partial = torch.empty(max(1, plan.n_chunks), dtype=torch.float64, device=dev)
+        sums = torch.empty(B, dtype=torch.float64, device=dev)
+        want_p, want_s, want_y = ctx.needs_input_grad[1:4]
+        g_stage = torch.empty(n, dtype=torch.float32, device=dev) if want_s else None
+        g_y_in = torch.empty(n, dtype=torch.float32, device=dev) if want_y else None
+        N.check(N.load().gj_adjoint_testing(n, N.ptr(flags), N.ptr(stage), N.ptr(g_y), N.ptr(g_row), N.ptr(env["band"]),
+                                            B, C.byref(plan.c), N.ptr(contrib), N.ptr(partial), N.ptr(sums),
+                                            N.ptr(g_stage), N.ptr(g_y_in), N.current_stream()), "gj_adjoint_testing")
+        g_prob = None
+        if want_p:
+            if env.get("all_reduce") is not None:
+                sums = env["all_reduce"](sums)      # fp64: the world's sums on every rank
+            like_dev, like_dtype, like_shape = ctx.like
+            g_prob = sums.to(device=like_dev, dtype=like_dtype).reshape(like_shape)
+        return (None, g_prob, *_to_devices((g_stage, g_y_in), ctx.devices))
+
+
 class SymptomsStep(torch.autograd.Function):
     """(new_infected, current_stage, next_stage, time_to_next_stage) -> the three updated arrays, with the
     reference's gradient paths (symptoms.py:98,105-124,231-236): a loss on the stages - the deaths series of

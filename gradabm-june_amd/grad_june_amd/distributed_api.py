@@ -45,6 +45,13 @@ def _refuse_contact_quarantine(policies):
                                   "run")
 
 
+def _refuse_isolating_testing(policies):
+    """The partitioned step reads the stage and the plain ``Quarantine`` threshold, not a mask."""
+    if getattr(getattr(policies, "testing_policies", None), "isolating", False):
+        raise NotImplementedError("testing: a Testing policy with isolation is not available in a partitioned run "
+                                  "(without isolation it is)")
+
+
 class DistributedGradJune(GradJune):
     """``GradJune`` whose hot path runs one rank's part of the world (``partition`` first)."""
 
@@ -56,6 +63,7 @@ class DistributedGradJune(GradJune):
         import torch.distributed as dist
 
         _refuse_contact_quarantine(self.policies)
+        _refuse_isolating_testing(self.policies)
         device = require_hip(self.device)
         if rank is None:
             rank, world_size = dist.get_rank(group), dist.get_world_size(group)
@@ -228,11 +236,14 @@ class DistributedRunner(Runner):
         # (and the immunity series: int64 [rows, 2] reinfections and susceptibility sums, fp64 reinfections by group)
         vaccine = getattr(self, "_vaccine_series", None)
         immunity = getattr(self, "_immunity_series", None)
+        confirmed = getattr(self, "_confirmed_series", None)      # (and the testing series: int64 [rows, 2], fp64 by group)
         for series in [self._series, *getattr(self, "_group_series", {}).values(),
                        *getattr(self, "_stage_series", {}).values(), *([vaccine] if vaccine is not None else []),
                        *getattr(self, "_vaccine_group_series", {}).values(),
                        *([immunity] if immunity is not None else []),
-                       *getattr(self, "_reinfection_group_series", {}).values()]:
+                       *getattr(self, "_reinfection_group_series", {}).values(),
+                       *([confirmed] if confirmed is not None else []),
+                       *getattr(self, "_confirmed_group_series", {}).values()]:
             if dist.get_backend(self.group) == "gloo":            # tests: staged through the host
                 host = series[:n_rows].cpu()
                 dist.all_reduce(host, group=self.group)

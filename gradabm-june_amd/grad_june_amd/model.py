@@ -82,10 +82,19 @@ class GradJune(torch.nn.Module):
         step = self.n_steps
         self.n_steps += 1
         betas = self._betas(engine, active, timer)
+        # testing: decisions, reports and - for a policy that isolates - the mask, on the stage the step starts from
+        # (without a Testing policy nothing is launched); a ContactQuarantine active in the step overrides the mask
+        testing = getattr(self.policies, "testing_policies", None)
+        if testing is not None and len(testing.policies):
+            agent_offset, all_reduce = self._vaccination_env()
+            self.policies.test(data, timer, seed=self.rng_seed, agent_offset=agent_offset, all_reduce=all_reduce)
         # contact quarantine: mark, then mask, on the stage the step starts from; the step then takes the mask in the
         # place of the stage (None while no ContactQuarantine is active: nothing launched, the threshold path as it was)
         if has_q:
+            isolating = self._qstate()
             self._contact_quarantine(data, timer, engine)
+            if isolating is not None and self._qstate() is None:
+                self.policies.quarantine_policies.qstate = isolating
         where = self._launch_env(engine, timer, active, betas, has_q, step)
         exp_noise = self._exp_noise(engine, exp_noise)
         # infection-location series: what forward() launches gj_location_stats with after the step (s0 and stage are

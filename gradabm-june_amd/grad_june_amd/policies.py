@@ -13,6 +13,10 @@ Not in the reference:
                          the threshold 0.5
   * Vaccination       -> ``susceptibility[a] *= 1 - efficacy[band]`` for the agents a campaign's age-banded rollout
                          reaches in the step (``gj_vaccinate``); differentiable in the efficacy
+  * Testing           -> confirmed cases - a share of the infections that reach a stage, by age, reported some days
+                         later (``gj_testing_step``) - and, with ``isolation``, the mask ``qstate`` (3: isolating on a
+                         positive result) that the step takes as it takes a ContactQuarantine's; differentiable in the
+                         probability
 """
 from __future__ import annotations
 
@@ -446,15 +450,294 @@ class VaccinationPolicies(PolicyCollection):
                 self.on_newly(c, newly)
 
 
+# ---- testing (not in the reference) --------------------------------------------------------------
+#: Philox streams of Testing policy c: bit 58 set; a decision's is ``c << 32 | bits(infection_time)`` below it, the
+#: compliance uniform's has bit 57 set and c below (bits 59 to 63 are the other policies', the sampler's and the symptoms')
+TESTING_STREAM = 1 << 58
+TESTING_COMPLY_STREAM = TESTING_STREAM | 1 << 57
+TESTING_MAX_DELAYS = 16
+
+
+class Testing(Policy):
+    """An observation model: while the policy is active, an infection that reaches ``stage_threshold`` (``!(stage <
+    stage_threshold)``, the step's own rule) is tested and found with the probability of the agent's age, once per
+    infection, and the result arrives ``delay`` days later.  A positive result is a confirmed case - what surveillance
+    data count - and, with ``isolation``, keeps a complying agent away from the step for ``days`` days.
+
+    ``probability``: ascertainment, a number (one band, every age) or ``{"lo-hi": p}``: ``self.probability`` is a float32
+    tensor [B], one value per band in file order, and ``band_of_age`` maps an age to its band (-1: none, p = 0).  It may be
+    replaced by an ``nn.Parameter`` of the same shape: a loss on the confirmed series then leaves its gradient in
+    ``.grad`` (a straight-through estimator: every decision counts 1, so the sum is the exact derivative of the expected
+    count).  ``delay``: a number of days >= 0, or ``{days: share}`` with at most 16 entries whose shares sum to 1;
+    ``delay_days`` and ``delay_cum`` hold the days and the cumulative shares, each an fp32 value rounded once.
+    ``isolation``: ``{days: > 0, compliance: share in [0, 1], default 1}`` or None; who complies is one Philox uniform per
+    agent for the whole run (``u < fp32(compliance)``).  Neither the delay nor the compliance is differentiable, and the
+    isolation mask is hard: no gradient flows from ``probability`` into the epidemic.  The launches and their state live
+    in ``TestingPolicies``."""
+
+    spec = "testing"
+
+    def __init__(self, start_date, end_date, stage_threshold, probability, delay=0, isolation=None, device="cpu"):
+        super().__init__(start_date, end_date, device)
+        from .utils import parse_age_probabilities
+
+        self.stage_threshold = float(stage_threshold)
+        if isinstance(probability, dict):
+            bands = [_age_band(k) for k in probability]
+            by_lo = sorted(bands)
+            for (_, hi), (lo, _) in zip(by_lo, by_lo[1:]):
+                if lo < hi:
+                    raise ValueError(f"testing: overlapping probability bands ({sorted(map(str, probability))})")
+            values = list(probability.values())
+            self.band_of_age = [int(b) for b in parse_age_probabilities(
+                {str(k): i for i, k in enumerate(probability)}, fill_value=-1)]
+        else:
+            values, self.band_of_age = [probability], [0] * N_AGES
+        if any(isinstance(v, torch.Tensor) and v.requires_grad for v in values):
+            self.probability = torch.stack([torch.as_tensor(v, dtype=torch.float32).reshape(()) for v in values])
+        else:
+            self.probability = torch.tensor([float(v) for v in values], dtype=torch.float32)
+        self._host_probability()
+        entries = list(delay.items()) if isinstance(delay, dict) else [(delay, 1.0)]
+        if not 1 <= len(entries) <= TESTING_MAX_DELAYS:
+            raise ValueError(f"testing: delay has {len(entries)} entries, expected 1 to {TESTING_MAX_DELAYS}")
+        days, shares = [float(d) for d, _ in entries], [float(s) for _, s in entries]
+        for d in days:
+            if not (d >= 0.0 and math.isfinite(d)):
+                raise ValueError(f"testing: delay of {d} days, expected days >= 0")
+        for s in shares:
+            if not s >= 0.0:
+                raise ValueError(f"testing: delay share {s}, expected a share >= 0")
+        if abs(sum(shares) - 1.0) > 1e-6:
+            raise ValueError(f"testing: the delay shares sum to {sum(shares)}, expected 1")
+        self.delay_days = torch.tensor(days, dtype=torch.float32)
+        self.delay_cum = torch.tensor([sum(shares[:k + 1]) for k in range(len(shares))], dtype=torch.float64).to(torch.float32)
+        self.isolation_days, self.compliance = None, 1.0
+        if isolation is not None:
+            if not isinstance(isolation, dict) or "days" not in isolation or set(isolation) - {"days", "compliance"}:
+                raise ValueError(f"testing: isolation = {isolation}, expected {{days: .., compliance: ..}}")
+            self.isolation_days = float(isolation["days"])
+            if not (self.isolation_days > 0.0 and math.isfinite(self.isolation_days)):
+                raise ValueError(f"testing: isolation days = {self.isolation_days}, expected days > 0")
+            compliance = isolation.get("compliance", 1.0)
+            if isinstance(compliance, torch.Tensor) and compliance.requires_grad:
+                raise NotImplementedError("testing: gradients w.r.t. the compliance are not implemented (pass a plain "
+                                          "number)")
+            self.compliance = float(compliance)
+            if not 0.0 <= self.compliance <= 1.0:
+                raise ValueError(f"testing: compliance = {self.compliance}, expected a share in [0, 1]")
+        self._bands = None
+
+    @property
+    def isolates(self) -> bool:
+        return self.isolation_days is not None
+
+    @property
+    def n_bands(self) -> int:
+        return max(self.band_of_age) + 1
+
+    def window(self) -> str:
+        return f"[{self.start_date:%Y-%m-%d}, {self.end_date:%Y-%m-%d})"
+
+    def _host_probability(self):
+        """The probabilities as Python doubles of the float32 values, checked."""
+        p = [float(v) for v in self.probability.detach().to(torch.float32).cpu().tolist()]
+        if len(p) != self.n_bands:
+            raise ValueError(f"testing: probability of shape {tuple(self.probability.shape)}, expected [{self.n_bands}] "
+                             "(one value per band)")
+        for v in p:
+            if not 0.0 <= v <= 1.0:
+                raise ValueError(f"testing: probability = {v}, expected a value in [0, 1]")
+        return p
+
+    def tables(self):
+        """The launch's tables (``gj_testing_tables``), each value rounded once: the probability per age (0 for an age in
+        no band), the cumulative shares and the days of the delay."""
+        from . import _native as N
+
+        p = self._host_probability()
+        t = N.TestingTables()
+        for age in range(N_AGES):
+            b = self.band_of_age[age]
+            t.probability[age] = p[b] if b >= 0 else 0.0
+        t.n_delays = self.delay_days.numel()
+        for k in range(t.n_delays):
+            t.delay_cum[k], t.delay_days[k] = float(self.delay_cum[k]), float(self.delay_days[k])
+        return t
+
+    def bands(self, ages: torch.Tensor):
+        """(int32 band per agent on the agents' device, its ``groups.SeedPlan``): what the adjoint sums through; built
+        once per world."""
+        if self._bands is None or self._bands[0].numel() != ages.numel() or self._bands[0].device != ages.device:
+            from .groups import SeedPlan
+
+            table = torch.tensor(self.band_of_age, dtype=torch.int32, device=ages.device)
+            band = table[ages.long().clamp(0, N_AGES - 1)].contiguous()
+            self._bands = (band, SeedPlan(band, self.n_bands, device=ages.device))
+        return self._bands
+
+
+class TestingPolicies(PolicyCollection):
+    """The ``Testing`` policies, in list order: a policy's index is its Philox stream; their windows must not overlap.
+    ``step`` - called by whoever launches the step, after ``Policies.apply`` and on the stage the step starts from -
+    launches ``gj_testing_step`` for every policy from its first active step to the end of the run (results keep
+    arriving after ``end_date``; decisions are made only while the policy is active).  Per-agent state, allocated at a
+    policy's first active step and put back by ``reset``: ``decided`` / ``result_time`` / ``positive`` per policy (12 B
+    an agent) and ``isolate_until`` / ``confirmed_time`` for the run (8 B).  ``qstate``: the mask of the last launch of
+    an isolating policy (fp32 per agent: 0 free, 1 at or above the plain ``Quarantine`` threshold, 3 isolating), or None.
+    ``sink``: set by the Runner for its time loop - ``{"counts": device int64 [2], "on_newly": callable or None, "rows":
+    list}``: the launches add their newly confirmed cases and decisions to ``counts``, hand ``on_newly`` their 0 / 1
+    mask, and a differentiable launch appends its row (a scalar on the graph) to ``rows``."""
+
+    def __init__(self, policies):
+        super().__init__(policies)
+        for i, a in enumerate(self.policies):
+            for b in self.policies[i + 1:]:
+                if a.start_date < b.end_date and b.start_date < a.end_date:
+                    raise ValueError(f"testing: the windows {a.window()} and {b.window()} overlap")
+        self.sink = None
+        self.qstate = None
+        self.isolate_until = self.confirmed_time = None
+        self._state = {}            # policy index -> its per-agent arrays, from its first active step on
+        self._cls = self._qstate_buffer = None
+
+    @property
+    def isolating(self) -> bool:
+        return any(p.isolates for p in self.policies)
+
+    def requires_grad(self) -> bool:
+        return any(isinstance(p.probability, torch.Tensor) and p.probability.requires_grad for p in self.policies)
+
+    def reset(self):
+        """Forget a run: every policy waits for its first active step again, and the arrays go back to their initial
+        values."""
+        self._state = {}
+        self.qstate = None
+        if self.isolate_until is not None:
+            self.isolate_until.zero_()
+            self.confirmed_time.fill_(-1.0)
+
+    def _agent_class(self, ag, device):
+        n = ag["age"].numel()
+        if self._cls is None or self._cls.numel() != n or self._cls.device != device:
+            sex = ag["sex"] if "sex" in ag else torch.zeros_like(ag["age"])
+            self._cls = (sex.to(device).long() * 100 + ag["age"].to(device).long()).to(torch.uint8).contiguous()
+        return self._cls
+
+    def _started(self, c, n, dev):
+        if self.isolate_until is None or self.isolate_until.numel() != n or self.isolate_until.device != dev:
+            self.isolate_until = torch.zeros(n, dtype=torch.float32, device=dev)
+            self.confirmed_time = torch.full((n,), -1.0, dtype=torch.float32, device=dev)
+        held = self._state.get(c)
+        if held is None or held["decided"].numel() != n or held["decided"].device != dev:
+            held = self._state[c] = {
+                # (int32 -1: the bit pattern 0xFFFFFFFF)
+                "decided": torch.full((n,), -1, dtype=torch.int32, device=dev),
+                "result_time": torch.full((n,), math.inf, dtype=torch.float32, device=dev),
+                "positive": torch.zeros(n, dtype=torch.float32, device=dev), "y": None}
+        return held
+
+    def state(self, c=0):
+        """Policy c's per-agent arrays (``decided`` as int32 bit patterns), or None before its first active step."""
+        return self._state.get(c)
+
+    def step(self, data, timer, seed, q_threshold=math.inf, agent_offset=0, all_reduce=None):
+        """See the class.  ``seed``: the run's Philox key; ``q_threshold``: the active plain ``Quarantine`` minimum
+        (``QuarantinePolicies.threshold``); ``agent_offset``: the global id of local agent 0 and ``all_reduce``: the sum
+        over the ranks of the probability's gradient, on a rank of a partitioned world.  Returns ``qstate``.  Without a
+        policy that has started: nothing launched, nothing allocated."""
+        self.qstate = None
+        running = [(c, p) for c, p in enumerate(self.policies) if c in self._state or p.is_active(timer.date)]
+        if not running:
+            return None
+        from . import _native as N
+        from .world import require_hip
+
+        now = float(timer.now)
+        if now < 0.0:
+            raise ValueError(f"testing: timer.now = {now}, expected a time >= 0")
+        ag = data["agent"]
+        stage_in, inf_time = ag["symptoms"]["current_stage"], ag["infection_time"]
+        dev = require_hip(inf_time.device)
+        n = inf_time.numel()
+        f32 = lambda t: (t if t.dtype == torch.float32 and t.device == dev and t.is_contiguous() and not t.requires_grad
+                         else t.detach().to(device=dev, dtype=torch.float32).contiguous())
+        stage, inf_time = f32(stage_in), f32(inf_time)
+        if stage.numel() != n:
+            raise ValueError(f"testing: {stage.numel()} stages for {n} agents")
+        cls = self._agent_class(ag, dev)
+        sink = self.sink or {}
+        want_newly = sink.get("on_newly") is not None
+        for c, policy in running:
+            held = self._started(c, n, dev)
+            qstate = None
+            if policy.isolates:
+                if self._qstate_buffer is None or self._qstate_buffer.numel() != n or self._qstate_buffer.device != dev:
+                    self._qstate_buffer = torch.empty(n, dtype=torch.float32, device=dev)
+                qstate = self._qstate_buffer
+            newly = torch.empty(n, dtype=torch.float32, device=dev) if want_newly else None
+            env = {"n": n, "cls": cls, "tables": policy.tables(), "stage": stage, "inf_time": inf_time,
+                   "threshold": policy.stage_threshold, "active": int(policy.is_active(timer.date)), "now": now,
+                   "q_threshold": float(q_threshold),
+                   "release": now + policy.isolation_days if policy.isolates else 0.0,      # (ctypes rounds to fp32: once)
+                   "compliance": policy.compliance, "seed": int(seed) & 0xFFFFFFFFFFFFFFFF,
+                   "decide_stream": TESTING_STREAM | c << 32, "comply_stream": TESTING_COMPLY_STREAM | c,
+                   "agent_offset": int(agent_offset), "held": held,
+                   "isolate_until": self.isolate_until if policy.isolates else None,
+                   "confirmed_time": self.confirmed_time, "newly": newly, "qstate": qstate,
+                   "counts": sink.get("counts"), "all_reduce": all_reduce}
+            prob = policy.probability
+            if torch.is_grad_enabled() and (prob.requires_grad or stage_in.requires_grad):
+                from .autograd import TestingStep
+
+                env["band"], env["plan"] = policy.bands(ag["age"].to(dev))
+                y_prev = held["y"] if held["y"] is not None else held["positive"].clone()
+                held["y"], row = TestingStep.apply(env, prob, stage_in, y_prev)
+                if "rows" in sink:
+                    sink["rows"].append(row)
+            else:
+                testing_launch(env, None)
+            if want_newly:
+                sink["on_newly"](newly)
+            if qstate is not None:
+                self.qstate = qstate
+        return self.qstate
+
+
+def testing_launch(env, flags):
+    """One ``gj_testing_step`` from what ``TestingPolicies.step`` put together."""
+    from . import _native as N
+
+    held = env["held"]
+    N.check(N.load().gj_testing_step(
+        env["n"], N.ptr(env["cls"]), env["tables"], N.ptr(env["stage"]), N.ptr(env["inf_time"]), env["threshold"],
+        env["active"], env["now"], env["q_threshold"], env["release"], env["compliance"], env["seed"],
+        env["decide_stream"], env["comply_stream"], env["agent_offset"], N.ptr(held["decided"]),
+        N.ptr(held["result_time"]), N.ptr(held["positive"]), N.ptr(env["isolate_until"]), N.ptr(env["confirmed_time"]),
+        N.ptr(env["newly"]), N.ptr(env["qstate"]), N.ptr(flags), N.ptr(env["counts"]), N.current_stream()),
+        "gj_testing_step")
+
+
+def _refuse_isolation_beside_contact_quarantine(quarantine_policies, testing_policies):
+    """Both write the step's mask: an isolating ``Testing`` and a ``ContactQuarantine`` must not share a date."""
+    for t in getattr(testing_policies, "policies", None) or []:
+        for q in getattr(quarantine_policies, "contact_policies", None) or []:
+            if t.isolates and t.start_date < q.end_date and q.start_date < t.end_date:
+                raise ValueError(f"testing: the window {t.window()} of a Testing with isolation overlaps the "
+                                 f"ContactQuarantine's {q.window()}")
+
+
 # ---- container ---------------------------------------------------------------------------------
 class Policies(torch.nn.Module):
     def __init__(self, interaction_policies=None, quarantine_policies=None, close_venue_policies=None,
-                 vaccination_policies=None):
+                 vaccination_policies=None, testing_policies=None):
         super().__init__()
         self.interaction_policies = interaction_policies
         self.quarantine_policies = quarantine_policies
         self.close_venue_policies = close_venue_policies
         self.vaccination_policies = vaccination_policies
+        self.testing_policies = testing_policies
+        _refuse_isolation_beside_contact_quarantine(quarantine_policies, testing_policies)
 
     @classmethod
     def from_policy_list(cls, policies):
@@ -468,6 +751,7 @@ class Policies(torch.nn.Module):
             quarantine_policies=QuarantinePolicies(of("quarantine")),
             close_venue_policies=CloseVenuePolicies(of("close_venue")),
             vaccination_policies=VaccinationPolicies(of("vaccination")),
+            testing_policies=TestingPolicies(of("testing")),
         )
 
     @classmethod
@@ -515,6 +799,23 @@ class Policies(torch.nn.Module):
             self.vaccination_policies.reset()
         if self.quarantine_policies is not None and hasattr(self.quarantine_policies, "reset"):
             self.quarantine_policies.reset()
+        if getattr(self, "testing_policies", None) is not None:
+            self.testing_policies.reset()
+
+    def test(self, data, timer, seed, agent_offset=0, all_reduce=None):
+        """The ``Testing`` policies' launch (``TestingPolicies.step``) on the stage the step starts from: call it after
+        ``apply``.  The mask of an isolating policy is left in ``quarantine_policies.qstate``, where the step reads a
+        ``ContactQuarantine``'s.  Without a ``Testing`` policy: nothing."""
+        tp = getattr(self, "testing_policies", None)
+        if tp is None or len(tp.policies) == 0:
+            return
+        qp = self.quarantine_policies
+        if tp.isolating and qp is None:
+            raise ValueError("testing: isolation needs Policies.quarantine_policies (an empty QuarantinePolicies will do)")
+        qstate = tp.step(data, timer, seed, q_threshold=qp.threshold if qp is not None else math.inf,
+                         agent_offset=agent_offset, all_reduce=all_reduce)
+        if qp is not None:
+            qp.qstate = qstate
 
     def vaccinate(self, data, timer, seed, agent_offset=0, all_reduce=None):
         """Move ``data["agent"].susceptibility`` for every campaign whose ramp rose since it was last applied

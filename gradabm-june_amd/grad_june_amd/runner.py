@@ -498,15 +498,34 @@ class Runner(torch.nn.Module):
         return qp if getattr(qp, "contact_policies", None) else None
 
     def _quarantine_stats(self):
-        """{None or labelling name: groups.StageStats} over the mask's three values (0 free, 1 index case, 2 contact)."""
+        """{None or labelling name: groups.StageStats} over the mask's values: three (0 free, 1 index case, 2 contact),
+        and a fourth (3 isolating on a positive test) where a ``Testing`` policy isolates."""
         if getattr(self, "_q_stats", None) is None:
             from .groups import StageStats
 
             dev = require_hip(self.device)
-            self._q_stats = {None: StageStats(None, 1, 3, device=dev)}
+            values = self._mask_values()
+            self._q_stats = {None: StageStats(None, 1, values, device=dev)}
             for name, st in self._groups().items():
-                self._q_stats[name] = StageStats(st.labels, st.n_groups, 3, device=dev)
+                self._q_stats[name] = StageStats(st.labels, st.n_groups, values, device=dev)
         return self._q_stats
+
+    # testing series: the launches' own counts, one gj_group_stats pass per labelling on a launch's mask of the newly
+    # confirmed, and - where a policy isolates - the fourth value of the mask in the contact quarantine's gj_stage_stats ----
+    def _testing(self):
+        """The model's ``policies.TestingPolicies``, or None without a ``Testing`` policy (nothing is recorded)."""
+        tp = getattr(self.model.policies, "testing_policies", None)
+        return tp if tp is not None and len(tp.policies) else None
+
+    def _mask_values(self) -> int:
+        tp = self._testing()
+        return 4 if tp is not None and tp.isolating else 3
+
+    def _record_confirmed(self, newly):
+        """``TestingPolicies.sink["on_newly"]``: this launch's newly confirmed cases, added by group to the current row
+        (the cases half of gj_group_stats' output, as ``_record_newly``)."""
+        for name, stats in self._groups().items():
+            stats.add(newly, newly, 2, self._confirmed_group_series[name][self._confirmed_row])
 
     def _record_quarantined(self, qstate, row):
         """The occupancy plane of gj_stage_stats on ``qstate``: exact int64 counts, so a by-group row sums to the national
@@ -541,7 +560,8 @@ class Runner(torch.nn.Module):
             isinstance(n.log_beta, torch.Tensor) and n.log_beta.requires_grad
             for n in model.infection_networks.networks.values()) or profile_requires_grad(data)
             or self._seed_requires_grad() or (campaigns is not None and campaigns.requires_grad())
-            or (self._immunity() is not None and self._immunity().requires_grad()))
+            or (self._immunity() is not None and self._immunity().requires_grad())
+            or (self._testing() is not None and self._testing().requires_grad()))
         diff_rows = []
         groups = self._groups()
         self._group_series = {name: torch.zeros(n_rows, 2 * st.n_groups, dtype=torch.float64,
@@ -586,10 +606,24 @@ class Runner(torch.nn.Module):
         # and the rows of steps without an active ContactQuarantine are zero (a plain Quarantine is not counted); no
         # gradient
         contact_quarantine = self._contact_quarantine()
+        # testing series (not in the reference), whenever the model has a Testing policy: each step's newly confirmed
+        # cases - the launches' own count, and by every labelling gj_group_stats on their 0 / 1 masks - and, where a
+        # policy isolates, the agents the step's mask holds as isolating: the fourth value of the pass that counts the
+        # contact quarantine's three.  Integer counts; row 0 is zero; a row lags the stage by one step (the launch of row
+        # k sees the stages row k - 1 left).  In a differentiable run the national row stays on the graph
+        testing = self._testing()
+        isolating = testing is not None and testing.isolating
+        self._confirmed_series, self._confirmed_group_series, confirmed_diff_rows = None, {}, []
+        if testing is not None:
+            dev = require_hip(self.device)
+            self._confirmed_series = torch.zeros(n_rows, 2, dtype=torch.int64, device=dev)      # confirmed, decisions
+            self._confirmed_group_series = {name: torch.zeros(n_rows, 2 * st.n_groups, dtype=torch.float64, device=dev)
+                                            for name, st in groups.items()}
+            confirmed_diff_rows.append(torch.zeros((), dtype=torch.float32, device=dev))
         self._quarantine_series = {}
-        if contact_quarantine is not None:
+        if contact_quarantine is not None or isolating:
             self._quarantine_series = {
-                key: torch.zeros(n_rows, 2, st.n_groups, 3, dtype=torch.int64, device=st.device)
+                key: torch.zeros(n_rows, 2, st.n_groups, self._mask_values(), dtype=torch.int64, device=st.device)
                 for key, st in self._quarantine_stats().items()}
 
         # waning-immunity series (not in the reference), whenever the model has an Immunity: each step's reinfections -
@@ -648,9 +682,15 @@ class Runner(torch.nn.Module):
             if immunity is not None:
                 model.immunity_stats = {"reinfected": reinfected, "count": self._immunity_series[row, 0:1],
                                         "susc_sum": self._immunity_series[row, 1:2]}
+            if testing is not None:
+                self._confirmed_row = row
+                testing.sink = {"counts": self._confirmed_series[row], "rows": [],
+                                "on_newly": self._record_confirmed if groups else None}
             try:
                 data = model(data, timer)
             finally:
+                if testing is not None:
+                    step_rows, testing.sink = testing.sink["rows"], None
                 model.immunity_stats = None
                 model.step_stats = None
                 model.location_stats = None
@@ -663,8 +703,12 @@ class Runner(torch.nn.Module):
             if reinfected is not None:      # this step's mask, by group (the cases half of gj_group_stats' output)
                 for name, stats in groups.items():
                     stats.add(reinfected, reinfected, 2, self._reinfection_group_series[name][row])
-            if contact_quarantine is not None:      # the mask the step just ran with
-                self._record_quarantined(contact_quarantine.qstate, row)
+            if contact_quarantine is not None or isolating:      # the mask the step just ran with
+                self._record_quarantined(getattr(model.policies.quarantine_policies, "qstate", None), row)
+            if testing is not None and differentiable:      # the launches' rows, on the graph
+                on_graph = torch.stack(step_rows).sum() if step_rows else torch.zeros_like(confirmed_diff_rows[0])
+                # (a launch that was no autograd node - nothing required a gradient yet - counts as a constant)
+                confirmed_diff_rows.append(on_graph + (self._confirmed_series[row, 0].to(torch.float32) - on_graph.detach()))
             record(row, done=bool(sink and sink.get("done")))
             dates.append(timer.date)
         self._finalize_series(row + 1)
@@ -760,14 +804,33 @@ class Runner(torch.nn.Module):
             results["susceptibility_per_timestep"] = (counts[1].to(torch.float64) / float(1 << 30)).to(torch.float32)
             for name, st in groups.items():
                 results[f"reinfections_by_{name}"] = self._reinfection_group_series[name][: row + 1, : st.n_groups].clone()
-        if contact_quarantine is not None:      # int64 counts: [T] nationally, [T, G] by labelling
-            contact_quarantine.check("contact quarantine")
+        if contact_quarantine is not None or isolating:      # int64 counts: [T] nationally, [T, G] by labelling
+            if contact_quarantine is not None:
+                contact_quarantine.check("contact quarantine")
             for key, st in self._quarantine_stats().items():
-                st.check("contact-quarantine series" + (f" by {key}" if key else ""))
-                counts = self._quarantine_series[key][: row + 1, 0]      # the occupancy plane, [T, G, 3]
+                st.check("quarantine-mask series" + (f" by {key}" if key else ""))
+                counts = self._quarantine_series[key][: row + 1, 0]      # the occupancy plane, [T, G, 3 or 4]
                 tail = "per_timestep" if key is None else f"by_{key}"
-                results[f"quarantined_index_{tail}"] = counts[:, 0, 1] if key is None else counts[:, :, 1]
-                results[f"quarantined_contacts_{tail}"] = counts[:, 0, 2] if key is None else counts[:, :, 2]
+                if contact_quarantine is not None:
+                    results[f"quarantined_index_{tail}"] = counts[:, 0, 1] if key is None else counts[:, :, 1]
+                    results[f"quarantined_contacts_{tail}"] = counts[:, 0, 2] if key is None else counts[:, :, 2]
+                if isolating:
+                    results[f"isolating_{tail}"] = counts[:, 0, 3] if key is None else counts[:, :, 3]
+        if testing is not None:      # int64 counts (a differentiable run: the national row as float32 on the graph)
+            results["confirmed_cases_per_timestep"] = self._confirmed_series[: row + 1, 0].clone()
+            if differentiable and len(confirmed_diff_rows) == row + 1:
+                results["confirmed_cases_per_timestep"] = self._reduce_differentiable(torch.stack(confirmed_diff_rows))
+            for name, st in groups.items():
+                results[f"confirmed_cases_by_{name}"] = self._confirmed_group_series[name][: row + 1, : st.n_groups].to(torch.int64)
+            confirmed_time = testing.confirmed_time
+            if confirmed_time is None:      # no policy ever started
+                confirmed_time = torch.full((self.n_agents,), -1.0, dtype=torch.float32, device=require_hip(self.device))
+            confirmed_time = confirmed_time.clone()
+            if "original_index" in data["agent"]:      # per agent, in the file's order like is_infected below
+                moved = torch.empty_like(confirmed_time)
+                moved[data["agent"].original_index.to(moved.device).long()] = confirmed_time
+                confirmed_time = moved
+            data["agent"]["confirmed_time"] = confirmed_time
         is_infected = data["agent"].is_infected
         if "original_index" in data["agent"]:
             out = torch.empty_like(is_infected)
@@ -806,6 +869,10 @@ class Runner(torch.nn.Module):
                 saved.append("reinfections")
             if f"quarantined_index_by_{name}" in results:
                 saved += ["quarantined_index", "quarantined_contacts"]
+            if f"confirmed_cases_by_{name}" in results:
+                saved.append("confirmed_cases")
+            if f"isolating_by_{name}" in results:
+                saved.append("isolating")
             cols = {c: results[f"{c}_by_{name}"].detach().cpu().numpy().reshape(-1)
                     for c in ("cases", "daily_cases", "deaths", *saved)}
             pd.DataFrame({"date": np.repeat(np.asarray(results["dates"], dtype=object), len(keys)),
@@ -856,6 +923,14 @@ class Runner(torch.nn.Module):
                               ag["infection_location"].detach().cpu().numpy()[infected]],
                           "venue": ag["infection_venue"].detach().cpu().numpy()[infected]}
                          ).to_csv(self.save_path / "results_infection_tree.csv", index=False)
+        if "confirmed_cases_per_timestep" in results:      # one line per confirmed agent
+            import datetime
+
+            when = self.data["agent"]["confirmed_time"].detach().cpu().numpy()
+            agents = np.nonzero(when >= 0)[0]
+            pd.DataFrame({"agent": agents,
+                          "date": [results["dates"][0] + datetime.timedelta(days=float(t)) for t in when[agents]]}
+                         ).to_csv(self.save_path / "results_confirmed.csv", index=False)
         pd.DataFrame({"is_infected": is_infected.detach().cpu().numpy()}).to_csv(
             self.save_path / "results_is_infected.csv")
 

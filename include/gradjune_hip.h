@@ -941,6 +941,76 @@ int gj_contact_mask(int64_t n, const float* current_stage, float q_threshold,
                     uint64_t seed, uint64_t stream, int64_t agent_offset, float* qstate, uint32_t* err,
                     void* hip_stream);
 
+/* ---- testing: confirmed cases with a reporting delay, isolation on a positive result ------------------------------------
+ * A pure addition to ABI 7 (not in the reference, whose Quarantine finds every symptomatic agent at once).  One launch
+ * BEFORE a step, on the current_stage the step starts from, keeps five per-agent arrays (20 B an agent, the caller's):
+ *   decided        uint32  bits of the infection_time the agent's decision was made for      (start: 0xFFFFFFFF)
+ *   result_time    fp32    when the result is due                                            (start: +inf)
+ *   positive       fp32    0 / 1                                                             (start: 0)
+ *   isolate_until  fp32    end of the isolation; NULL for a policy that does not isolate     (start: 0)
+ *   confirmed_time fp32    when the case was confirmed                                       (start: -1, never)
+ * Per agent, with age = agent_class % 100 and g = agent_offset + a, in this order:
+ *   decide  if active && !(current_stage[a] < stage_threshold) && bits(infection_time[a]) != decided[a]   (a NaN stage
+ *           qualifies, as in the step; 0.0 and -0.0 are two infections):
+ *             decided[a] = bits(infection_time[a]);  r = Philox4x32-10(counter = (g, decide_stream | bits), key = seed)
+ *             - ONE block per decision, the agent's own: the counter's low half is g itself, not g >> 2, because the
+ *             decision takes two words;  positive[a] = u01(r[0]) < probability[age];  d = days[k], k the first entry
+ *             with cum[k] > u01(r[1]), the last entry where there is none;  result_time[a] = now + d  (one fp32 add)
+ *   report  if result_time[a] <= now:  result_time[a] = +inf, and where positive[a]: the case is newly confirmed,
+ *           confirmed_time[a] = now, and, where isolate_until is given and infection_uniform(seed, comply_stream, g) <
+ *           compliance (ONE uniform per agent for the whole run, as gj_contact_mask draws it),  isolate_until[a] =
+ *           isolate_release - fp32(now + days), formed once by the host.  A delay of 0 reports in the deciding launch.
+ *   mask    where qstate_out is given:  qstate[a] = 1 if !(current_stage[a] < q_threshold), else 3 if now <
+ *           isolate_until[a], else 0 - what the step then takes in the place of the stage with q_threshold = 0.5.
+ * The three tables are formed by the host, each value rounded once; the kernel compares and adds once, so a numpy
+ * restatement gives its bits (tests/gj_testing_ref.py).  Nothing is stored where nothing changed.
+ * Optional outputs (each may be NULL: not written):
+ *   newly_confirmed_out  device fp32 [n], 0 / 1
+ *   qstate_out           device fp32 [n]; needs isolate_until
+ *   flags_out            device uint8 [n]: GJ_TESTING_DECIDED | GJ_TESTING_POSITIVE (the value of `positive` of an agent
+ *                        that decided or reported) | GJ_TESTING_DUE - what gj_adjoint_testing replays
+ *   counts_out           device int64 [2]: the launch ADDS its newly confirmed cases to [0] and its decisions to [1]
+ * Four agents per lane where the 4-byte arrays are 16-byte and agent_class / flags_out 4-byte aligned, one per lane
+ * otherwise; both forms give the same bits.
+ * Returns GJ_E_RANGE for n < 0, agent_offset < 0, n_delays outside 1 .. GJ_TESTING_MAX_DELAYS, a `now` that is negative
+ * or NaN and a decide_stream with any of its low 32 bits set; GJ_E_NULL for a NULL `tables`, a NULL required array with
+ * n > 0, and qstate_out without isolate_until - all before any device work.  n == 0 launches nothing.                */
+#define GJ_TESTING_MAX_DELAYS 16
+#define GJ_TESTING_DECIDED 1u
+#define GJ_TESTING_POSITIVE 2u
+#define GJ_TESTING_DUE 4u
+typedef struct gj_testing_tables {
+  float probability[100];                 /* per age: the chance that an infection is found (0 for an age in no band) */
+  float delay_cum[GJ_TESTING_MAX_DELAYS]; /* cumulative shares of the delays, fp32 each                               */
+  float delay_days[GJ_TESTING_MAX_DELAYS];
+  int32_t n_delays;
+  int32_t _pad;
+} gj_testing_tables;
+int gj_testing_step(int64_t n, const uint8_t* agent_class, const gj_testing_tables* tables /* host */,
+                    const float* current_stage, const float* infection_time, float stage_threshold, int32_t active,
+                    float now, float q_threshold, float isolate_release, float compliance, uint64_t seed,
+                    uint64_t decide_stream, uint64_t comply_stream, int64_t agent_offset, uint32_t* decided,
+                    float* result_time, float* positive, float* isolate_until, float* confirmed_time,
+                    float* newly_confirmed_out, float* qstate_out, uint8_t* flags_out, int64_t* counts_out,
+                    void* hip_stream);
+
+/* gj_adjoint_testing: adjoint of one gj_testing_step, whose `positive` travels on the graph as y: a deciding agent's
+ * y = hard * stage / stage.detach() (the reference's own form for deaths), everybody else's y is the incoming one, and
+ * the launch's row is sum over due agents of y.  flags: the forward's flags_out; g_y: the cotangent of the outgoing y
+ * (device fp32 [n], NULL = zeros); g_row: the cotangent of the row (device fp32 [1], NULL = zero); band: device int32
+ * [n], each agent's probability band, or a label outside [0, n_bands) for none.  With g = g_y[a] + (due ? *g_row : 0):
+ *   g_stage[a] = decided ? g * hard / current_stage[a] : 0        g_y_in[a] = decided ? 0 : g       (fp32; each may be NULL)
+ *   grad_probability[b] = sum over deciding agents of band b of g      (device double [n_bands]; d y / d probability := 1
+ *                         for every deciding agent, positive or negative: a straight-through estimator whose sum is the
+ *                         exact derivative of the expected count)
+ * The terms are summed in fp64 without atomics in the order `plan` fixes, through gj_adjoint_seed's two summing kernels:
+ * two launches on the same inputs give the same bits.  contrib_workspace: device double [n]; partial_workspace: device
+ * double [plan->n_chunks].                                                                                            */
+int gj_adjoint_testing(int64_t n, const uint8_t* flags, const float* current_stage, const float* g_y, const float* g_row,
+                       const int32_t* band, int32_t n_bands, const gj_seed_plan* plan, double* contrib_workspace,
+                       double* partial_workspace, double* grad_probability, float* g_stage, float* g_y_in,
+                       void* hip_stream);
+
 /* d loss / d log_beta of the networks on ONE edge set, from the forward's and the transposed passes' per-venue sums:
  *   col0 + k :  ln(10) * scale * sum_v [p_contact[v] > 0]  cum_fwd[v][k] * cum_bwd[v][k] / (beta[k] * p_contact[v]) * weight[v]
  * (reference: autograd through base.py:36-42,78-83; `weights` - fp64 [n_venues] or NULL = 1 - is a rank's share of
