@@ -250,7 +250,7 @@ __global__ __launch_bounds__(kThreads) void k_venue_reduce(const P1Args A) {
     acc[k] = 0.0f;
     y[k] = (k < nk) ? S.beta[k] * pc : 0.0f;
   }
-  if (!S.leisure) {
+  if (!S.leisure && nk == 1) {
     float a0 = 0.0f;
     int e = b.e0 + tid;
     for (; e + 3 * kThreads < b.e1; e += 4 * kThreads) {
@@ -264,6 +264,16 @@ __global__ __launch_bounds__(kThreads) void k_venue_reduce(const P1Args A) {
     }
     for (; e < b.e1; e += kThreads) a0 += src[S.v_agent[e]] * y[0];
     acc[0] = a0;
+  } else if (!S.leisure) {
+    // several networks on a set without tables (do_venue_reduce accepts them): the STREAM loop's term per network.
+    // (Until the CSR kernels were pinned per venue this case fell into the branch above, which sums network 0 only:
+    // a long venue's cum of every further network was 0.)
+    for (int e = b.e0 + tid; e < b.e1; e += kThreads) {
+      const float x = src[S.v_agent[e]];
+#pragma unroll
+      for (int k = 0; k < GJ_MAX_NETS_PER_SET; ++k)
+        if (k < nk) acc[k] += x * y[k];
+    }
   } else {
     const float* tabs = A.tables + A.day_type * 200;
     for (int e = b.e0 + tid; e < b.e1; e += kThreads) {

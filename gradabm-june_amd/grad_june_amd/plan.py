@@ -14,7 +14,10 @@ venue, unsorted; /root/reference/grad_june/june_world_loader/network_loader.py:3
   partial sums combined in chunk order by a second kernel - deterministic, no float atomics).
 
 Both CSR views keep the COO order inside a row (stable sort), so a sum taken in row order has the
-reference's ``scatter_add_`` order.  All indices are int32.
+reference's ``scatter_add_`` order.  Pass 2 takes every agent's sum so; pass 1 does for the venues of
+the STREAM blocks with ``lanes == 1`` (mean degree <= 6).  A block with 4, 16 or 64 lanes and a LONG
+venue add strided partial sums and combine them in a fixed tree: another order, the same on every
+run (``tests/gj_csr_ref.py`` states all of them).  All indices are int32.
 
 Host part is numpy/torch-CPU only and is covered by the CPU test-suite; :class:`DevicePlan`
 uploads it and owns the per-step workspaces.
