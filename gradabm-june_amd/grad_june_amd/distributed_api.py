@@ -191,10 +191,7 @@ class DistributedRunner(Runner):
     @classmethod
     def from_parameters(cls, params, group=None, rank: Optional[int] = None, world_size: Optional[int] = None,
                         collectives: bool = True):
-        cls._refuse_locations(params.get("locations_to_save"))
-        cls._refuse_infectors(params.get("infectors_to_save"))
-        cls._refuse_matrices(params.get("infection_matrices_to_save"))
-        cls._refuse_tree(params.get("infection_tree_to_save"))
+        cls._refuse_unpartitionable(params)
         model = DistributedGradJune.from_parameters(params)
         _refuse_contact_quarantine(model.policies)
         full = Runner.get_data(params)                # the whole world, identical on every rank (same torch seed)
@@ -230,20 +227,11 @@ class DistributedRunner(Runner):
 
         if not self.collectives or not dist.is_initialized() or dist.get_world_size(self.group) == 1:
             return
-        # (the series by agent group too: the labels were encoded on the whole world before the partition cut it, so the
-        # columns are the same on every rank; the symptom-stage counts are int64 and go the same way)
-        # (the vaccination doses too: every rank counted its own agents' - int64 by campaign, fp64 by group)
-        # (and the immunity series: int64 [rows, 2] reinfections and susceptibility sums, fp64 reinfections by group)
-        vaccine = getattr(self, "_vaccine_series", None)
-        immunity = getattr(self, "_immunity_series", None)
-        confirmed = getattr(self, "_confirmed_series", None)      # (and the testing series: int64 [rows, 2], fp64 by group)
-        for series in [self._series, *getattr(self, "_group_series", {}).values(),
-                       *getattr(self, "_stage_series", {}).values(), *([vaccine] if vaccine is not None else []),
-                       *getattr(self, "_vaccine_group_series", {}).values(),
-                       *([immunity] if immunity is not None else []),
-                       *getattr(self, "_reinfection_group_series", {}).values(),
-                       *([confirmed] if confirmed is not None else []),
-                       *getattr(self, "_confirmed_group_series", {}).values()]:
+        # ``_summed``: every series that ``Runner._open_series`` allocated as a sum over this rank's agents - the national
+        # series, and the series by agent group (the labels were encoded on the whole world before the partition cut it,
+        # so the columns are the same on every rank), the symptom-stage counts, the vaccination doses, the immunity and
+        # the testing series (int64 counts, fp64 by group)
+        for series in self._summed:
             if dist.get_backend(self.group) == "gloo":            # tests: staged through the host
                 host = series[:n_rows].cpu()
                 dist.all_reduce(host, group=self.group)

@@ -183,50 +183,42 @@ class GradJune(torch.nn.Module):
         return new_infected, None
 
     @staticmethod
-    def location_edges(data, plan):
+    def location_edges(data, plan, held="_location_rows"):
         """What ``DevicePlan.location_rows`` builds the by-agent rows from - the world's COO edge lists, in the agent
         order in use - or None once the plan holds them (built once, kept with the plan)."""
-        if getattr(plan, "_location_rows", None) is not None:
+        if getattr(plan, held, None) is not None:
             return None
         return {s: data["attends_" + s].edge_index for s in plan.host.set_index if "attends_" + s in data}
-
-    def _record_locations(self, sink, data, new_infected):
-        """gj_location_stats on the step just run (the plan's ``cum`` workspaces still hold its sums), for every
-        ``groups.LocationStats`` of the sink: from detached tensors, so the series carry no gradient."""
-        step = self._location_step
-        plan = step["engine"].plan
-        nu = new_infected.detach().to(device=plan.device, dtype=torch.float32).contiguous()
-        edges = self.location_edges(data, plan)
-        for stats in sink["stats"]:
-            stats.add(plan, step["params"], nu, step["s0"], step["stage"], active=step["active"],
-                      background="background", row=sink["row"], edges=edges)
-
-    def _record_infectors(self, sink, data, new_infected):
-        """gj_infector_scatter and gj_infector_gather on the step just run, for the ``groups.InfectorStats`` of the sink:
-        the location series' launch point and record, and the step's own transmissions.  No gradient."""
-        step = self._location_step
-        plan = step["engine"].plan
-        nu = new_infected.detach().to(device=plan.device, dtype=torch.float32).contiguous()
-        sink["stats"].record(plan, step["params"], nu, step["s0"], step["stage"], step["transmission"].detach(),
-                             row=sink["row"], edges=self.location_edges(data, plan))
-
-    def _record_tree(self, sink, data, new_infected):
-        """gj_infection_tree on the step just run, for the ``groups.InfectionTree`` of the sink: the infector series'
-        launch point, record and transmissions, and the step's own Philox key and stream.  No gradient."""
-        step = self._location_step
-        plan = step["engine"].plan
-        nu = new_infected.detach().to(device=plan.device, dtype=torch.float32).contiguous()
-        edges = self.location_edges(data, plan) or self.venue_edges(data, plan)
-        sink["stats"].record(plan, step["params"], nu, step["s0"], step["stage"], step["transmission"].detach(),
-                             active=step["active"], background="background", row=sink["row"], edges=edges,
-                             seed=step["seed"], step=step["step"])
 
     @staticmethod
     def venue_edges(data, plan):
         """``location_edges`` for ``DevicePlan.venue_rows``: the COO edge lists, or None once the plan holds the rows."""
-        if getattr(plan, "_venue_rows", None) is not None:
-            return None
-        return {s: data["attends_" + s].edge_index for s in plan.host.set_index if "attends_" + s in data}
+        return GradJune.location_edges(data, plan, held="_venue_rows")
+
+    def _record_attribution(self, data, new_infected):
+        """The step just run, attributed for the sinks the Runner set for its time loop (like ``step_stats``; without one
+        nothing is cloned and nothing is launched), from detached tensors, so the series carry no gradient.
+        ``location_stats``: gj_location_stats for every ``groups.LocationStats`` (the plan's ``cum`` workspaces still
+        hold the step's sums); ``infector_stats``: gj_infector_scatter and gj_infector_gather for the
+        ``groups.InfectorStats``, with the step's own transmissions; ``tree_stats``: gj_infection_tree for the
+        ``groups.InfectionTree``, with the step's own Philox key and stream too."""
+        locations, infectors, tree = self.location_stats, self.infector_stats, self.tree_stats
+        if locations is None and infectors is None and tree is None:
+            return
+        step = self._location_step
+        plan = step["engine"].plan
+        nu = new_infected.detach().to(device=plan.device, dtype=torch.float32).contiguous()
+        edges = self.location_edges(data, plan)
+        record = (plan, step["params"], nu, step["s0"], step["stage"])
+        if locations is not None:
+            for stats in locations["stats"]:
+                stats.add(*record, active=step["active"], background="background", row=locations["row"], edges=edges)
+        if infectors is not None:
+            infectors["stats"].record(*record, step["transmission"].detach(), row=infectors["row"], edges=edges)
+        if tree is not None:
+            tree["stats"].record(*record, step["transmission"].detach(), active=step["active"], background="background",
+                                 row=tree["row"], edges=edges or self.venue_edges(data, plan), seed=step["seed"],
+                                 step=step["step"])
 
     def _vaccination_env(self):
         """(global id of local agent 0, sum over the ranks of the efficacy's gradient or None): a rank of a partitioned
@@ -245,20 +237,10 @@ class GradJune(torch.nn.Module):
             agent_offset, all_reduce = self._vaccination_env()
             self.policies.vaccinate(data, timer, seed=self.rng_seed, agent_offset=agent_offset, all_reduce=all_reduce)
         new_infected, _ = self.hot_path(data, timer, exp_noise=exp_noise)
-        # location_stats: set by the Runner for the duration of its time loop, like step_stats - the step's new
-        # infections are attributed to the networks BEFORE the symptoms update, while current_stage is still the stage
-        # the quarantine mask was formed from.  Without it nothing is cloned and nothing is launched
-        sink = getattr(self, "location_stats", None)
-        if sink is not None:
-            self._record_locations(sink, data, new_infected)
-        # infector_stats: the same for the infector series (groups.InfectorStats), at the same point
-        sink = getattr(self, "infector_stats", None)
-        if sink is not None:
-            self._record_infectors(sink, data, new_infected)
-        # tree_stats: the same for the transmission tree (groups.InfectionTree), at the same point
-        sink = getattr(self, "tree_stats", None)
-        if sink is not None:
-            self._record_tree(sink, data, new_infected)
+        # location_stats, infector_stats, tree_stats: the step's new infections are attributed to the networks, to the
+        # infectors and to one sampled infector BEFORE the symptoms update, while current_stage is still the stage the
+        # quarantine mask was formed from
+        self._record_attribution(data, new_infected)
         # waning immunity: after the records above (they read the step's own outcome) and before the symptoms update,
         # so the stage is still the one the step started from.  immunity_stats: set by the Runner for its time loop -
         # the launch's optional outputs.  Without an Immunity nothing is launched

@@ -53,10 +53,11 @@ class Runner(torch.nn.Module):
                  age_bins=(0, 18, 65, 100), groups=None, seed_group=None, stages=None, locations=None, infectors=None,
                  matrices=None, tree=None):
         super().__init__()
-        self._refuse_locations(locations)
-        self._refuse_infectors(infectors)
-        self._refuse_matrices(matrices)
-        self._refuse_tree(tree)
+        from .groups import (attach_groups, infection_tree_to_save, infectors_to_save, location_keys, locations_to_save,
+                             stages_to_save)
+
+        self._refuse_unpartitionable({"locations_to_save": locations, "infectors_to_save": infectors,
+                                      "infection_matrices_to_save": matrices, "infection_tree_to_save": tree})
         self.model = model
         self.data = data
         self.data_backup = self.backup_infection_data(data)
@@ -73,8 +74,6 @@ class Runner(torch.nn.Module):
         # result series by agent group (not in the reference): ``groups`` = attribute names of data["agent"] or a dict
         # name -> integer labels in the order of data["agent"]; the YAML key ``groups_to_save`` is encoded by get_data
         if groups is not None:
-            from .groups import attach_groups
-
             attach_groups(data["agent"], groups)
         self.group_keys = {k: np.asarray(v) for k, v in (data["agent"].get("group_keys", None) or {}).items()}
         self._group_stats = None
@@ -86,23 +85,17 @@ class Runner(torch.nn.Module):
         self._seed_plan = None
         # symptom-stage series (not in the reference): ``stages`` = names of ``symptoms.stages`` or "all" (the YAML key
         # ``stages_to_save``): the occupancy of each stage and the entries into it, nationally and by every labelling
-        from .groups import stages_to_save
-
         self.stage_names = [str(s) for s in model.symptoms_updater.symptoms_sampler.stages] if stages else []
         self.stages_saved = stages_to_save(stages, self.stage_names)
         self._stage_stats = None
         # infection-location series (not in the reference): ``locations=True`` (the YAML key ``locations_to_save``):
         # each step's new infections attributed to the networks they came through, nationally and by every labelling
-        from .groups import location_keys, locations_to_save
-
         self.locations_saved = locations_to_save(locations)
         self.location_keys = location_keys(model.infection_networks.networks) if self.locations_saved else []
         self._location_stats = None
         # infector series (not in the reference): ``infectors=True`` (the YAML key ``infectors_to_save``): each step's new
         # infections attributed to the agents who transmitted - infections caused per step, nationally and by every
         # labelling of the INFECTOR, per agent over the run, and the case reproduction number by cohort
-        from .groups import infectors_to_save
-
         self.infectors_saved = infectors_to_save(infectors)
         self._infector_stats = None
         # who-infects-whom matrices (not in the reference): ``matrices=[name, ...]`` (the YAML key
@@ -112,8 +105,6 @@ class Runner(torch.nn.Module):
         # transmission tree (not in the reference): ``tree=True`` (the YAML key ``infection_tree_to_save``): ONE sampled
         # infector per infection - who infected whom, through which location and venue, and in which row - with the
         # exact counts by location and the mean generation interval per row
-        from .groups import infection_tree_to_save
-
         self.tree_saved = infection_tree_to_save(tree)
         if self.tree_saved and not self.location_keys:
             self.location_keys = location_keys(model.infection_networks.networks)
@@ -123,35 +114,21 @@ class Runner(torch.nn.Module):
     _supports_locations = True
 
     @classmethod
-    def _refuse_locations(cls, spec):
-        from .groups import locations_to_save
+    def _refuse_unpartitionable(cls, specs):
+        """``specs``: {YAML key: value} (the parameters themselves will do).  The series a partitioned run cannot form."""
+        from . import groups
 
-        if locations_to_save(spec) and not cls._supports_locations:
-            raise NotImplementedError("locations_to_save: the infection-location series is not available in a "
-                                      "partitioned run")
-
-    @classmethod
-    def _refuse_infectors(cls, spec):
-        from .groups import infectors_to_save
-
-        if infectors_to_save(spec) and not cls._supports_locations:      # a halo infector's credit belongs to another rank
-            raise NotImplementedError("infectors_to_save: the infector series is not available in a partitioned run")
-
-    @classmethod
-    def _refuse_matrices(cls, spec):
-        from .groups import infection_matrices_to_save
-
-        if infection_matrices_to_save(spec) and not cls._supports_locations:      # they are sums of the infector series' terms
-            raise NotImplementedError("infection_matrices_to_save: the infection matrices are not available in a "
-                                      "partitioned run")
-
-    @classmethod
-    def _refuse_tree(cls, spec):
-        from .groups import infection_tree_to_save
-
-        if infection_tree_to_save(spec) and not cls._supports_locations:      # a venue's members live on other ranks
-            raise NotImplementedError("infection_tree_to_save: the transmission tree is not available in a partitioned "
-                                      "run")
+        for key, parse, message in (
+                ("locations_to_save", groups.locations_to_save,
+                 "locations_to_save: the infection-location series is not available in a partitioned run"),
+                ("infectors_to_save", groups.infectors_to_save,      # a halo infector's credit belongs to another rank
+                 "infectors_to_save: the infector series is not available in a partitioned run"),
+                ("infection_matrices_to_save", groups.infection_matrices_to_save,      # sums of the infector series' terms
+                 "infection_matrices_to_save: the infection matrices are not available in a partitioned run"),
+                ("infection_tree_to_save", groups.infection_tree_to_save,      # a venue's members live on other ranks
+                 "infection_tree_to_save: the transmission tree is not available in a partitioned run")):
+            if parse(specs.get(key)) and not cls._supports_locations:
+                raise NotImplementedError(message)
 
     def _check_matrices(self, spec):
         """The labellings that get an infection matrix: each a labelling with result series (``groups_to_save``) of at
@@ -362,6 +339,21 @@ class Runner(torch.nn.Module):
                                  for name in self.group_keys if name not in skip}
         return self._group_stats
 
+    def _series_by_group(self, n_rows):
+        """{name: float64 [n_rows, 2 G]} zeros, one per labelling: the rows of gj_group_stats (cases, then deaths).  Sums
+        over this rank's agents (``_summed``)."""
+        series = {name: torch.zeros(n_rows, 2 * st.n_groups, dtype=torch.float64, device=require_hip(self.device))
+                  for name, st in self._groups().items()}
+        self._summed += series.values()
+        return series
+
+    def _add_mask(self, series, row, mask):
+        """A 0 / 1 mask per agent (a launch's newly vaccinated, newly confirmed, reinfected) counted by every labelling into
+        ``row`` of a ``_series_by_group``: the cases half of gj_group_stats' output (no stage equals the ``dead`` given, so
+        the other half stays zero)."""
+        for name, stats in self._groups().items():
+            stats.add(mask, mask, 2, series[name][row])
+
     def _record_groups(self, data, row, diff_rows=None):
         ag = data["agent"]
         dead = int(self.model.symptoms_updater.stages_ids[-1])
@@ -429,16 +421,14 @@ class Runner(torch.nn.Module):
         params = engine.params(now=self.timer.now, delta_time=self.timer.duration, day_type=0, active=[], betas={})
         f = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
         nu, s0 = f(self._seed_new_infected), f(self.data_backup["susceptibility"])
+        edges = self.model.location_edges(self.data, engine.plan)
         for stats in locations.values():
-            stats.add(engine.plan, params, nu, s0, None, active=(), background="seed", row=0,
-                      edges=self.model.location_edges(self.data, engine.plan))
+            stats.add(engine.plan, params, nu, s0, None, active=(), background="seed", row=0, edges=edges)
         if infectors is not None:      # nobody transmitted a seed: all unattributed; the seeds are the cohort of row 0
             infectors.clear(engine.plan)      # (U is zero between steps; a run that was interrupted may have left some)
-            infectors.record(engine.plan, params, nu, s0, None, None, row=0,
-                             edges=self.model.location_edges(self.data, engine.plan))
+            infectors.record(engine.plan, params, nu, s0, None, None, row=0, edges=edges)
         if tree is not None:      # nobody transmitted a seed: every seeded agent gets -2 and the column ``seed``
-            tree.record(engine.plan, params, nu, s0, None, None, active=(), background="seed", row=0,
-                        edges=self.model.location_edges(self.data, engine.plan))
+            tree.record(engine.plan, params, nu, s0, None, None, active=(), background="seed", row=0, edges=edges)
         self._seed_new_infected = None
 
     # per-step infector series: gj_infector_scatter once, gj_infector_gather for the nation and once per labelling -------
@@ -484,12 +474,6 @@ class Runner(torch.nn.Module):
         """The model's ``immunity.Immunity``, or None without the ``immunity`` key (nothing is recorded)."""
         return getattr(self.model, "immunity", None)
 
-    def _record_newly(self, campaign, newly):
-        """``VaccinationPolicies.on_newly``: this launch's newly vaccinated, added by group to the current row (the
-        cases half of gj_group_stats' output; no stage equals the ``dead`` given, so the other half stays zero)."""
-        for name, stats in self._groups().items():
-            stats.add(newly, newly, 2, self._vaccine_group_series[name][self._vaccine_row])
-
     # contact-quarantine series: one gj_stage_stats pass on the step's mask for the nation and one per labelling ----------
     def _contact_quarantine(self):
         """The model's ``policies.QuarantinePolicies`` if it holds a ``ContactQuarantine``, else None (nothing is
@@ -521,11 +505,9 @@ class Runner(torch.nn.Module):
         tp = self._testing()
         return 4 if tp is not None and tp.isolating else 3
 
-    def _record_confirmed(self, newly):
-        """``TestingPolicies.sink["on_newly"]``: this launch's newly confirmed cases, added by group to the current row
-        (the cases half of gj_group_stats' output, as ``_record_newly``)."""
-        for name, stats in self._groups().items():
-            stats.add(newly, newly, 2, self._confirmed_group_series[name][self._confirmed_row])
+    def _masked(self) -> bool:
+        """Whether the run has a quarantine-mask series: a ``ContactQuarantine``, or a ``Testing`` that isolates."""
+        return self._contact_quarantine() is not None or self._mask_values() == 4
 
     def _record_quarantined(self, qstate, row):
         """The occupancy plane of gj_stage_stats on ``qstate``: exact int64 counts, so a by-group row sums to the national
@@ -542,86 +524,126 @@ class Runner(torch.nn.Module):
             model.policies.reset()
         self.restore_initial_data()
         self.set_initial_cases()
-        n_bins = len(self.age_bins) - 1
-        n_rows = 1
-        probe = Timer.from_parameters(self.input_parameters) if isinstance(self.input_parameters, dict) else None
-        if probe is not None:
-            while probe.date < probe.final_date:
-                next(probe)
-                n_rows += 1
-        else:
-            n_rows = 4096
-        self._series = torch.zeros(n_rows, 2 + n_bins, dtype=torch.float64, device=require_hip(self.device))
-        # differentiable run (a log_beta is an nn.Parameter, a profile tensor, the seed, a vaccination efficacy or an
-        # immunity parameter requires a gradient, grad mode on): the case series must stay on the autograd graph, so they are formed with tensor ops
-        # instead of the fused reduction kernel
-        campaigns = self._campaigns()
-        differentiable = torch.is_grad_enabled() and (any(
+        self._open_series(self._count_rows(), self._is_differentiable())
+        self._record_row(data, 0)
+        dates = [timer.date]
+        row = 0
+        while timer.date < timer.final_date:
+            next(timer)
+            row += 1
+            sink = self._arm(row)
+            try:
+                data = model(data, timer)
+            finally:
+                step_rows = self._disarm()
+            self._after_step(row, step_rows)
+            self._record_row(data, row, done=bool(sink and sink.get("done")))
+            dates.append(timer.date)
+        T = row + 1
+        self._finalize_series(T)
+        results = {"dates": dates}
+        self._results_national(results, T, data)
+        self._results_groups(results, T)
+        self._results_stages(results, T)
+        self._results_locations(results, T)
+        self._results_infectors(results, T, data)
+        self._results_tree(results, T, data)
+        self._results_vaccination(results, T)
+        self._results_immunity(results, T)
+        self._results_quarantine(results, T)
+        self._results_testing(results, T, data)
+        return results, self._in_file_order(data["agent"].is_infected)
+
+    def _count_rows(self) -> int:
+        """The rows of the run's series: the seeding's and one per step of a probe timer (4096 without the parameters)."""
+        if not isinstance(self.input_parameters, dict):
+            return 4096
+        n_rows, probe = 1, Timer.from_parameters(self.input_parameters)
+        while probe.date < probe.final_date:
+            next(probe)
+            n_rows += 1
+        return n_rows
+
+    def _is_differentiable(self) -> bool:
+        """A differentiable run (a log_beta is an nn.Parameter, a profile tensor, the seed, a vaccination efficacy, an
+        immunity or a testing parameter requires a gradient, grad mode on): the case series must stay on the autograd
+        graph, so they are formed with tensor ops instead of the fused reduction kernel."""
+        campaigns, immunity, testing = self._campaigns(), self._immunity(), self._testing()
+        return torch.is_grad_enabled() and (any(
             isinstance(n.log_beta, torch.Tensor) and n.log_beta.requires_grad
-            for n in model.infection_networks.networks.values()) or profile_requires_grad(data)
+            for n in self.model.infection_networks.networks.values()) or profile_requires_grad(self.data)
             or self._seed_requires_grad() or (campaigns is not None and campaigns.requires_grad())
-            or (self._immunity() is not None and self._immunity().requires_grad())
-            or (self._testing() is not None and self._testing().requires_grad()))
-        diff_rows = []
+            or (immunity is not None and immunity.requires_grad())
+            or (testing is not None and testing.requires_grad()))
+
+    def _in_file_order(self, t):
+        """A per-agent array of the run in the order of the world's file (``system.locality_order`` renumbered the agents
+        at load time)."""
+        if "original_index" not in self.data["agent"]:
+            return t
+        out = torch.empty_like(t)
+        out[self.data["agent"].original_index.to(t.device)] = t
+        return out
+
+    def _open_series(self, n_rows, differentiable):
+        """Everything a run's series need before its first row: the allocations (``_summed``: those that are sums over
+        this rank's agents, which a partitioned run adds over the ranks), the seeding's row of the attribution series and
+        the susceptibility of row 0.  A differentiable run keeps the rows of its case, group, stage and confirmed series
+        on the graph, in the ``_*_diff_rows`` lists."""
+        dev = require_hip(self.device)
+        self._differentiable = differentiable
+        self._series = torch.zeros(n_rows, 1 + len(self.age_bins), dtype=torch.float64, device=dev)
+        self._summed = [self._series]
+        self._diff_rows = []
         groups = self._groups()
-        self._group_series = {name: torch.zeros(n_rows, 2 * st.n_groups, dtype=torch.float64,
-                                                device=require_hip(self.device)) for name, st in groups.items()}
-        group_diff_rows = {name: [] for name in groups} if differentiable else None
+        self._group_series = self._series_by_group(n_rows)
+        self._group_diff_rows = {name: [] for name in groups} if differentiable else None
         stages = self._stages()
         # (a differentiable run keeps its rows on the graph instead: no int64 series then)
         self._stage_series = {} if differentiable else {
             key: torch.zeros(n_rows, 2, st.n_groups, st.n_stages, dtype=torch.int64, device=st.device)
             for key, st in stages.items()}
-        stage_diff_rows = {key: [] for key in stages} if differentiable else None
+        self._summed += self._stage_series.values()
+        self._stage_diff_rows = {key: [] for key in stages} if differentiable else None
         if stages:      # row 0 counts its entries against the restored initial stage: the agents the seed moved
             self._stage_prev = self.data_backup["symptoms"]["current_stage"].detach().to(
-                device=require_hip(self.device), dtype=torch.float32, copy=True).contiguous()
+                device=dev, dtype=torch.float32, copy=True).contiguous()
 
-        locations = self._locations()
-        for st in locations.values():
-            st.reset(n_rows)
-        infectors = self._infectors()
-        if infectors is not None:
-            infectors.reset(n_rows)
-        tree = self._tree()
-        if tree is not None:
-            tree.reset(n_rows)
+        locations, infectors, tree = self._locations(), self._infectors(), self._tree()
+        for st in (*locations.values(), infectors, tree):
+            if st is not None:
+                st.reset(n_rows)
         if locations or infectors is not None or tree is not None:
             self._record_seed_locations(locations, infectors, tree)
         # vaccination series (not in the reference), whenever the model has a Vaccination policy: the doses given so far,
         # by campaign (the launches' own counts) and by every labelling (gj_group_stats on a launch's mask of the newly
         # vaccinated).  Integer counts, so a by-group row sums to the national row exactly; row 0 is zero; no gradient
+        campaigns = self._campaigns()
         self._vaccine_series, self._vaccine_group_series = None, {}
         if campaigns is not None:
             if "campaign" in groups:
                 raise ValueError("a labelling named 'campaign' would shadow the result key vaccine_doses_by_campaign")
-            self._vaccine_series = torch.zeros(n_rows, len(campaigns.policies), dtype=torch.int64,
-                                               device=require_hip(self.device))
-            self._vaccine_group_series = {name: torch.zeros(n_rows, 2 * st.n_groups, dtype=torch.float64,
-                                                            device=require_hip(self.device))
-                                          for name, st in groups.items()}
+            self._vaccine_series = torch.zeros(n_rows, len(campaigns.policies), dtype=torch.int64, device=dev)
+            self._summed.append(self._vaccine_series)
+            self._vaccine_group_series = self._series_by_group(n_rows)
 
-        # contact-quarantine series (not in the reference), whenever the model has a ContactQuarantine policy: the agents
-        # the step's mask holds as index cases and as contacts, nationally and by every labelling.  Integer counts; row 0
-        # and the rows of steps without an active ContactQuarantine are zero (a plain Quarantine is not counted); no
-        # gradient
-        contact_quarantine = self._contact_quarantine()
         # testing series (not in the reference), whenever the model has a Testing policy: each step's newly confirmed
         # cases - the launches' own count, and by every labelling gj_group_stats on their 0 / 1 masks - and, where a
         # policy isolates, the agents the step's mask holds as isolating: the fourth value of the pass that counts the
         # contact quarantine's three.  Integer counts; row 0 is zero; a row lags the stage by one step (the launch of row
         # k sees the stages row k - 1 left).  In a differentiable run the national row stays on the graph
-        testing = self._testing()
-        isolating = testing is not None and testing.isolating
-        self._confirmed_series, self._confirmed_group_series, confirmed_diff_rows = None, {}, []
-        if testing is not None:
-            dev = require_hip(self.device)
+        self._confirmed_series, self._confirmed_group_series, self._confirmed_diff_rows = None, {}, []
+        if self._testing() is not None:
             self._confirmed_series = torch.zeros(n_rows, 2, dtype=torch.int64, device=dev)      # confirmed, decisions
-            self._confirmed_group_series = {name: torch.zeros(n_rows, 2 * st.n_groups, dtype=torch.float64, device=dev)
-                                            for name, st in groups.items()}
-            confirmed_diff_rows.append(torch.zeros((), dtype=torch.float32, device=dev))
+            self._summed.append(self._confirmed_series)
+            self._confirmed_group_series = self._series_by_group(n_rows)
+            self._confirmed_diff_rows.append(torch.zeros((), dtype=torch.float32, device=dev))
+        # contact-quarantine series (not in the reference), whenever the model has a ContactQuarantine policy: the agents
+        # the step's mask holds as index cases and as contacts, nationally and by every labelling.  Integer counts; row 0
+        # and the rows of steps without an active ContactQuarantine are zero (a plain Quarantine is not counted); no
+        # gradient.  (No sum over the ranks: a partitioned run refuses both policies that write the mask)
         self._quarantine_series = {}
-        if contact_quarantine is not None or isolating:
+        if self._masked():
             self._quarantine_series = {
                 key: torch.zeros(n_rows, 2, st.n_groups, self._mask_values(), dtype=torch.int64, device=st.device)
                 for key, st in self._quarantine_stats().items()}
@@ -631,212 +653,211 @@ class Runner(torch.nn.Module):
         # susceptibility after the launch as an exact fixed-point sum.  Integer counts, so a by-group row sums to the
         # national row exactly; row 0 of the reinfections is zero, that of the susceptibility comes from one launch that
         # moves nobody; no gradient
-        immunity = self._immunity()
-        self._immunity_series, self._reinfection_group_series, reinfected = None, {}, None
-        if immunity is not None:
-            dev = require_hip(self.device)
+        self._immunity_series, self._reinfection_group_series, self._reinfected = None, {}, None
+        if self._immunity() is not None:
             self._immunity_series = torch.zeros(n_rows, 2, dtype=torch.int64, device=dev)      # reinfections, susc_sum
-            self._reinfection_group_series = {name: torch.zeros(n_rows, 2 * st.n_groups, dtype=torch.float64, device=dev)
-                                              for name, st in groups.items()}
+            self._summed.append(self._immunity_series)
+            self._reinfection_group_series = self._series_by_group(n_rows)
             if groups:
-                reinfected = torch.empty(self.n_agents, dtype=torch.float32, device=dev)
-            immunity.measure(data, self._immunity_series[0, 1:2])
+                self._reinfected = torch.empty(self.n_agents, dtype=torch.float32, device=dev)
+            self._immunity().measure(self.data, self._immunity_series[0, 1:2])
 
-        def record(row, done=False):
-            if not done:
-                self._record(data, row)
-            if groups:
-                self._record_groups(data, row, group_diff_rows)
-            if stages:
-                self._record_stages(data, row, stage_diff_rows)
-            if differentiable:
-                ag = data["agent"]
-                stage = ag.symptoms["current_stage"]
-                dead = float(self.model.symptoms_updater.stages_ids[-1])
-                deaths = ((stage == dead) * stage / dead).sum()          # store_differentiable_deaths' form
-                diff_rows.append(torch.cat((ag.is_infected.sum().reshape(1), self.get_cases_by_age(data),
-                                            deaths.reshape(1))))
+    def _record_row(self, data, row, done=False):
+        """Row ``row`` of the case, group and stage series from the state as it stands (``done``: the step's symptoms
+        update has filled the national row already)."""
+        if not done:
+            self._record(data, row)
+        if self._groups():
+            self._record_groups(data, row, self._group_diff_rows)
+        if self._stages():
+            self._record_stages(data, row, self._stage_diff_rows)
+        if self._differentiable:
+            ag = data["agent"]
+            stage = ag.symptoms["current_stage"]
+            dead = float(self.model.symptoms_updater.stages_ids[-1])
+            deaths = ((stage == dead) * stage / dead).sum()          # store_differentiable_deaths' form
+            self._diff_rows.append(torch.cat((ag.is_infected.sum().reshape(1), self.get_cases_by_age(data),
+                                              deaths.reshape(1))))
 
-        record(0)
-        dates = [timer.date]
-        row = 0
-        while timer.date < timer.final_date:
-            next(timer)
-            row += 1
-            sink = None
-            if not differentiable:      # rows f1 + f2 in one pass: the model's symptoms update fills this step's row
-                cls, edges, dead = self._stats_args(data)
-                sink = {"cls": cls, "edges": edges, "n_bins": n_bins, "dead": dead, "out": self._series[row]}
-            model.step_stats = sink
-            if locations:
-                model.location_stats = {"stats": list(locations.values()), "row": row}
-            if infectors is not None:
-                model.infector_stats = {"stats": infectors, "row": row}
-            if tree is not None:
-                model.tree_stats = {"stats": tree, "row": row}
-            if campaigns is not None:      # cumulative: a row starts from the one before it
-                for series in self._vaccine_group_series.values():
-                    series[row].copy_(series[row - 1])
-                self._vaccine_row = row
-                campaigns.on_newly = self._record_newly if groups else None
-            if immunity is not None:
-                model.immunity_stats = {"reinfected": reinfected, "count": self._immunity_series[row, 0:1],
-                                        "susc_sum": self._immunity_series[row, 1:2]}
-            if testing is not None:
-                self._confirmed_row = row
-                testing.sink = {"counts": self._confirmed_series[row], "rows": [],
-                                "on_newly": self._record_confirmed if groups else None}
-            try:
-                data = model(data, timer)
-            finally:
-                if testing is not None:
-                    step_rows, testing.sink = testing.sink["rows"], None
-                model.immunity_stats = None
-                model.step_stats = None
-                model.location_stats = None
-                model.infector_stats = None
-                model.tree_stats = None
-                if campaigns is not None:
-                    campaigns.on_newly = None
-            if campaigns is not None and campaigns.doses is not None:
-                self._vaccine_series[row].copy_(campaigns.doses)
-            if reinfected is not None:      # this step's mask, by group (the cases half of gj_group_stats' output)
-                for name, stats in groups.items():
-                    stats.add(reinfected, reinfected, 2, self._reinfection_group_series[name][row])
-            if contact_quarantine is not None or isolating:      # the mask the step just ran with
-                self._record_quarantined(getattr(model.policies.quarantine_policies, "qstate", None), row)
-            if testing is not None and differentiable:      # the launches' rows, on the graph
-                on_graph = torch.stack(step_rows).sum() if step_rows else torch.zeros_like(confirmed_diff_rows[0])
-                # (a launch that was no autograd node - nothing required a gradient yet - counts as a constant)
-                confirmed_diff_rows.append(on_graph + (self._confirmed_series[row, 0].to(torch.float32) - on_graph.detach()))
-            record(row, done=bool(sink and sink.get("done")))
-            dates.append(timer.date)
-        self._finalize_series(row + 1)
-        series = self._series[: row + 1].to(torch.float32)
-        if differentiable:
-            series = self._reduce_differentiable(torch.stack(diff_rows).to(torch.float32))
-        cases_per_timestep = series[:, 0]
+    def _arm(self, row):
+        """Before a step: where the model and the policies leave row ``row`` of the series they fill themselves.  Returns
+        the sink of the national row (None in a differentiable run)."""
+        model, groups = self.model, self._groups()
+        locations, infectors, tree = self._locations(), self._infectors(), self._tree()
+        campaigns, immunity, testing = self._campaigns(), self._immunity(), self._testing()
+        sink = None
+        if not self._differentiable:      # rows f1 + f2 in one pass: the model's symptoms update fills this step's row
+            cls, edges, dead = self._stats_args(self.data)
+            sink = {"cls": cls, "edges": edges, "n_bins": len(self.age_bins) - 1, "dead": dead, "out": self._series[row]}
+        model.step_stats = sink
+        if locations:
+            model.location_stats = {"stats": list(locations.values()), "row": row}
+        if infectors is not None:
+            model.infector_stats = {"stats": infectors, "row": row}
+        if tree is not None:
+            model.tree_stats = {"stats": tree, "row": row}
+        if campaigns is not None:      # cumulative: a row starts from the one before it
+            for series in self._vaccine_group_series.values():
+                series[row].copy_(series[row - 1])
+            campaigns.on_newly = (lambda campaign, newly: self._add_mask(self._vaccine_group_series, row, newly)
+                                  ) if groups else None
+        if immunity is not None:
+            model.immunity_stats = {"reinfected": self._reinfected, "count": self._immunity_series[row, 0:1],
+                                    "susc_sum": self._immunity_series[row, 1:2]}
+        if testing is not None:
+            testing.sink = {"counts": self._confirmed_series[row], "rows": [], "on_newly": (
+                lambda newly: self._add_mask(self._confirmed_group_series, row, newly)) if groups else None}
+        return sink
+
+    def _disarm(self):
+        """After a step, whether it came back or raised: everything ``_arm`` set is None again.  Returns the rows the
+        step's testing launches left on the graph (None without a Testing policy)."""
+        model, campaigns, testing = self.model, self._campaigns(), self._testing()
+        step_rows = None
+        if testing is not None:
+            step_rows, testing.sink = testing.sink["rows"], None
+        model.immunity_stats = model.step_stats = model.location_stats = model.infector_stats = model.tree_stats = None
+        if campaigns is not None:
+            campaigns.on_newly = None
+        return step_rows
+
+    def _after_step(self, row, step_rows):
+        """Row ``row`` of the series the runner reads off the step it just ran."""
+        campaigns = self._campaigns()
+        if campaigns is not None and campaigns.doses is not None:
+            self._vaccine_series[row].copy_(campaigns.doses)
+        if self._reinfected is not None:      # this step's mask, by group
+            self._add_mask(self._reinfection_group_series, row, self._reinfected)
+        if self._masked():      # the mask the step just ran with
+            self._record_quarantined(getattr(self.model.policies.quarantine_policies, "qstate", None), row)
+        if self._testing() is not None and self._differentiable:      # the launches' rows, on the graph
+            on_graph = torch.stack(step_rows).sum() if step_rows else torch.zeros_like(self._confirmed_diff_rows[0])
+            # (a launch that was no autograd node - nothing required a gradient yet - counts as a constant)
+            self._confirmed_diff_rows.append(on_graph + (self._confirmed_series[row, 0].to(torch.float32) - on_graph.detach()))
+
+    # the result keys, one family per method, in the order they enter ``results`` --------------------------------------
+    def _results_national(self, results, T, data):
+        n_bins = len(self.age_bins) - 1
+        series = self._series[:T].to(torch.float32)
+        if self._differentiable:
+            series = self._reduce_differentiable(torch.stack(self._diff_rows).to(torch.float32))
         data["results"]["deaths_per_timestep"] = series[:, 1 + n_bins]
-        results = {
-            "dates": dates,
-            "cases_per_timestep": cases_per_timestep,
-            "daily_cases_per_timestep": torch.diff(cases_per_timestep,
-                                                   prepend=torch.tensor([0.0], device=self.device)),
-            "deaths_per_timestep": data.results["deaths_per_timestep"],
-        }
+        results["cases_per_timestep"] = series[:, 0]
+        results["daily_cases_per_timestep"] = torch.diff(series[:, 0], prepend=torch.tensor([0.0], device=self.device))
+        results["deaths_per_timestep"] = data.results["deaths_per_timestep"]
         for i, key in enumerate(self.age_bins[1:]):
             results[f"cases_by_age_{int(key):02d}"] = series[:, 1 + i]
-        for name, st in groups.items():
+
+    def _results_groups(self, results, T):
+        for name, st in self._groups().items():
             st.check(f"result series by {name}")
-            by_group = self._group_series[name][: row + 1].to(torch.float32)
-            if differentiable:
-                by_group = self._reduce_differentiable(torch.stack(group_diff_rows[name]).to(torch.float32))
+            by_group = self._group_series[name][:T].to(torch.float32)
+            if self._differentiable:
+                by_group = self._reduce_differentiable(torch.stack(self._group_diff_rows[name]).to(torch.float32))
             G = st.n_groups
             results[f"cases_by_{name}"] = by_group[:, :G]
             results[f"daily_cases_by_{name}"] = torch.diff(by_group[:, :G], dim=0,
                                                            prepend=torch.zeros(1, G, device=by_group.device))
             results[f"deaths_by_{name}"] = by_group[:, G:]
-        for key, st in stages.items():      # every stage was counted: the columns asked for are selected here
+
+    def _results_stages(self, results, T):
+        for key, st in self._stages().items():      # every stage was counted: the columns asked for are selected here
             st.check("symptom-stage series" + (f" by {key}" if key else ""))
-            if differentiable:
-                counts = self._reduce_differentiable(torch.stack(stage_diff_rows[key]))
+            if self._differentiable:
+                counts = self._reduce_differentiable(torch.stack(self._stage_diff_rows[key]))
             else:
-                counts = self._stage_series[key][: row + 1].to(torch.float32)      # [T, 2, G, S]
+                counts = self._stage_series[key][:T].to(torch.float32)      # [T, 2, G, S]
             for name in self.stages_saved:
                 s = self.stage_names.index(name)
                 tail = "per_timestep" if key is None else f"by_{key}"
                 occupancy, entries = counts[:, 0, :, s], counts[:, 1, :, s]
                 results[f"{name}_{tail}"] = occupancy[:, 0] if key is None else occupancy
                 results[f"new_{name}_{tail}"] = entries[:, 0] if key is None else entries
-        for key, st in locations.items():      # out / 2^30 in fp64, then float32 like the other series; no gradient
+
+    def _results_locations(self, results, T):
+        for key, st in self._locations().items():      # out / 2^30 in fp64, then float32 like the other series; no gradient
             st.check("infection-location series" + (f" by {key}" if key else ""))
-            values = st.values(row + 1)
+            values = st.values(T)
             if key is None:
                 results["infections_by_location"] = values[:, 0, :]
             else:
                 results[f"infections_by_location_by_{key}"] = values
+
+    def _results_infectors(self, results, T, data):
+        infectors = self._infectors()
         if infectors is not None:      # by the infector's group; R by the cohort's row (and group); no gradient
             infectors.check("infector series")
-            T = row + 1
             results["infections_caused_per_timestep"] = infectors.values(None, T)[:, 0]
             results["infections_unattributed_per_timestep"] = infectors.unattributed[:T].to(torch.float64)      # counts: exact
             results["reproduction_number_per_timestep"] = infectors.reproduction(T)[:, 0]
-            for name in groups:
+            for name in self._groups():
                 results[f"infections_caused_by_{name}"] = infectors.values(name, T)
                 results[f"reproduction_number_by_{name}"] = infectors.reproduction(T, name)
             for name in self.matrices_saved:      # [t, infector's group, infected's group]; the counts are exact
                 results[f"infection_matrix_by_{name}"] = infectors.matrix_values(name, T)
                 results[f"infections_unattributed_by_{name}"] = infectors.unattributed_by[name][:T].to(torch.float64)
-            caused, infected_row = infectors.caused, infectors.infected_row
-            if "original_index" in data["agent"]:      # per agent, in the file's order like is_infected below
-                index = data["agent"].original_index.to(caused.device)
-                caused, infected_row = torch.empty_like(caused), torch.empty_like(infected_row)
-                caused[index], infected_row[index] = infectors.caused, infectors.infected_row
-            data["agent"]["infections_caused"], data["agent"]["infected_row"] = caused, infected_row
+            data["agent"]["infections_caused"] = self._in_file_order(infectors.caused)
+            data["agent"]["infected_row"] = self._in_file_order(infectors.infected_row)
+
+    def _results_tree(self, results, T, data):
+        tree = self._tree()
         if tree is not None:      # exact counts as float64; the per-agent arrays in the file's order; no gradient
             tree.check("transmission tree")
-            T = row + 1
             results["infections_sampled_by_location"] = tree.counts[:T].to(torch.float64)
             results["infections_unresolved_per_timestep"] = tree.unresolved[:T].to(torch.float64)
-            results["generation_interval_per_timestep"] = self._generation_interval(tree, dates)
+            results["generation_interval_per_timestep"] = self._generation_interval(tree, results["dates"])
             per_agent = {"infector": tree.infector, "infection_location": tree.via, "infection_venue": tree.venue,
                          "infected_row": tree.infected_row, "offspring": tree.offspring()}
-            if "original_index" in data["agent"]:      # positions and the ids held in ``infector``: the file's numbering
+            if "original_index" in data["agent"]:      # the ids held in ``infector`` too: the file's numbering
                 index = data["agent"].original_index.to(tree.device).long()
-                named = torch.where(tree.infector >= 0, index[tree.infector.clamp(min=0).long()].to(torch.int32),
-                                    tree.infector)
-                per_agent["infector"] = named
-                for key, values in per_agent.items():
-                    moved = torch.empty_like(values)
-                    moved[index] = values
-                    per_agent[key] = moved
+                per_agent["infector"] = torch.where(
+                    tree.infector >= 0, index[tree.infector.clamp(min=0).long()].to(torch.int32), tree.infector)
             for key, values in per_agent.items():
-                data["agent"][key] = values
-        if campaigns is not None:      # counts as float64: exact (float32 holds integers up to 2^24 only)
-            by_campaign = self._vaccine_series[: row + 1].to(torch.float64)
+                data["agent"][key] = self._in_file_order(values)
+
+    def _results_vaccination(self, results, T):
+        if self._campaigns() is not None:      # counts as float64: exact (float32 holds integers up to 2^24 only)
+            by_campaign = self._vaccine_series[:T].to(torch.float64)
             results["vaccine_doses_per_timestep"] = by_campaign.sum(1)
             results["vaccine_doses_by_campaign"] = by_campaign
-            for name, st in groups.items():
-                results[f"vaccine_doses_by_{name}"] = self._vaccine_group_series[name][: row + 1, : st.n_groups].clone()
-        if immunity is not None:      # counts as float64: exact; the susceptibility: sum / 2^30 in fp64, then float32
-            counts = self._immunity_series[: row + 1].t()
+            for name, st in self._groups().items():
+                results[f"vaccine_doses_by_{name}"] = self._vaccine_group_series[name][:T, : st.n_groups].clone()
+
+    def _results_immunity(self, results, T):
+        if self._immunity() is not None:      # counts as float64: exact; the susceptibility: sum / 2^30 in fp64, then float32
+            counts = self._immunity_series[:T].t()
             results["reinfections_per_timestep"] = counts[0].to(torch.float64)
             results["susceptibility_per_timestep"] = (counts[1].to(torch.float64) / float(1 << 30)).to(torch.float32)
-            for name, st in groups.items():
-                results[f"reinfections_by_{name}"] = self._reinfection_group_series[name][: row + 1, : st.n_groups].clone()
-        if contact_quarantine is not None or isolating:      # int64 counts: [T] nationally, [T, G] by labelling
+            for name, st in self._groups().items():
+                results[f"reinfections_by_{name}"] = self._reinfection_group_series[name][:T, : st.n_groups].clone()
+
+    def _results_quarantine(self, results, T):
+        contact_quarantine, isolating = self._contact_quarantine(), self._mask_values() == 4
+        if self._masked():      # int64 counts: [T] nationally, [T, G] by labelling
             if contact_quarantine is not None:
                 contact_quarantine.check("contact quarantine")
             for key, st in self._quarantine_stats().items():
                 st.check("quarantine-mask series" + (f" by {key}" if key else ""))
-                counts = self._quarantine_series[key][: row + 1, 0]      # the occupancy plane, [T, G, 3 or 4]
+                counts = self._quarantine_series[key][:T, 0]      # the occupancy plane, [T, G, 3 or 4]
                 tail = "per_timestep" if key is None else f"by_{key}"
                 if contact_quarantine is not None:
                     results[f"quarantined_index_{tail}"] = counts[:, 0, 1] if key is None else counts[:, :, 1]
                     results[f"quarantined_contacts_{tail}"] = counts[:, 0, 2] if key is None else counts[:, :, 2]
                 if isolating:
                     results[f"isolating_{tail}"] = counts[:, 0, 3] if key is None else counts[:, :, 3]
+
+    def _results_testing(self, results, T, data):
+        testing = self._testing()
         if testing is not None:      # int64 counts (a differentiable run: the national row as float32 on the graph)
-            results["confirmed_cases_per_timestep"] = self._confirmed_series[: row + 1, 0].clone()
-            if differentiable and len(confirmed_diff_rows) == row + 1:
-                results["confirmed_cases_per_timestep"] = self._reduce_differentiable(torch.stack(confirmed_diff_rows))
-            for name, st in groups.items():
-                results[f"confirmed_cases_by_{name}"] = self._confirmed_group_series[name][: row + 1, : st.n_groups].to(torch.int64)
+            results["confirmed_cases_per_timestep"] = self._confirmed_series[:T, 0].clone()
+            if self._differentiable and len(self._confirmed_diff_rows) == T:
+                results["confirmed_cases_per_timestep"] = self._reduce_differentiable(torch.stack(self._confirmed_diff_rows))
+            for name, st in self._groups().items():
+                results[f"confirmed_cases_by_{name}"] = self._confirmed_group_series[name][:T, : st.n_groups].to(torch.int64)
             confirmed_time = testing.confirmed_time
             if confirmed_time is None:      # no policy ever started
                 confirmed_time = torch.full((self.n_agents,), -1.0, dtype=torch.float32, device=require_hip(self.device))
-            confirmed_time = confirmed_time.clone()
-            if "original_index" in data["agent"]:      # per agent, in the file's order like is_infected below
-                moved = torch.empty_like(confirmed_time)
-                moved[data["agent"].original_index.to(moved.device).long()] = confirmed_time
-                confirmed_time = moved
-            data["agent"]["confirmed_time"] = confirmed_time
-        is_infected = data["agent"].is_infected
-        if "original_index" in data["agent"]:
-            out = torch.empty_like(is_infected)
-            out[data["agent"].original_index.to(out.device)] = is_infected
-            is_infected = out
-        return results, is_infected
+            data["agent"]["confirmed_time"] = self._in_file_order(confirmed_time.clone())
 
     def _finalize_series(self, n_rows: int) -> None:
         """Hook: a partitioned run sums the ranks' per-step reductions here (distributed_api.DistributedRunner)."""
@@ -845,9 +866,23 @@ class Runner(torch.nn.Module):
         """Hook: the same for the series kept on the autograd graph in a differentiable run."""
         return series
 
+    def _save_long(self, fname, dates, axes, cols):
+        """A [T, ...] series as a long-format CSV: one line per date and per key of every axis of ``axes`` = {column:
+        keys}, the last axis running fastest (the series' own row-major order), then ``cols`` = {column: flat values}."""
+        import pandas as pd
+
+        n = int(np.prod([len(keys) for keys in axes.values()]))
+        frame, inner = {"date": np.repeat(np.asarray(dates, dtype=object), n)}, n
+        for name, keys in axes.items():
+            inner //= len(keys)
+            frame[name] = np.tile(np.repeat(np.asarray(keys), inner), len(dates) * n // (len(keys) * inner))
+        pd.DataFrame({**frame, **cols}).to_csv(self.save_path / fname, index=False)
+
     def save_results(self, results, is_infected):
         import pandas as pd
 
+        flat = lambda key: results[key].detach().cpu().numpy().reshape(-1)
+        dates = results["dates"]
         self.save_path.mkdir(exist_ok=True, parents=True)
         df = pd.DataFrame(index=results["dates"])
         df.index.name = "date"
@@ -873,45 +908,30 @@ class Runner(torch.nn.Module):
                 saved.append("confirmed_cases")
             if f"isolating_by_{name}" in results:
                 saved.append("isolating")
-            cols = {c: results[f"{c}_by_{name}"].detach().cpu().numpy().reshape(-1)
-                    for c in ("cases", "daily_cases", "deaths", *saved)}
-            pd.DataFrame({"date": np.repeat(np.asarray(results["dates"], dtype=object), len(keys)),
-                          name: np.tile(keys, len(results["dates"])), **cols}).to_csv(
-                self.save_path / f"results_by_{name}.csv", index=False)
-        if "infections_by_location" in results:      # long format: date, location, infections
-            dates, L = np.asarray(results["dates"], dtype=object), len(self.location_keys)
-            pd.DataFrame({"date": np.repeat(dates, L), "location": np.tile(self.location_keys, len(dates)),
-                          "infections": results["infections_by_location"].detach().cpu().numpy().reshape(-1)}).to_csv(
-                self.save_path / "results_by_location.csv", index=False)
+            self._save_long(f"results_by_{name}.csv", dates, {name: keys},
+                            {c: flat(f"{c}_by_{name}") for c in ("cases", "daily_cases", "deaths", *saved)})
+        if "infections_by_location" in results:      # date, location, infections
+            self._save_long("results_by_location.csv", dates, {"location": self.location_keys},
+                            {"infections": flat("infections_by_location")})
             for name, keys in self.group_keys.items():
-                if f"infections_by_location_by_{name}" not in results:
-                    continue
-                G = len(keys)
-                pd.DataFrame({"date": np.repeat(dates, G * L), name: np.tile(np.repeat(np.asarray(keys), L), len(dates)),
-                              "location": np.tile(self.location_keys, len(dates) * G),
-                              "infections": results[f"infections_by_location_by_{name}"].detach().cpu().numpy().reshape(-1)}
-                             ).to_csv(self.save_path / f"results_by_location_by_{name}.csv", index=False)
-        if "infections_caused_per_timestep" in results:      # long format: date, series, value
-            dates = np.asarray(results["dates"], dtype=object)
+                if f"infections_by_location_by_{name}" in results:
+                    self._save_long(f"results_by_location_by_{name}.csv", dates, {name: keys, "location": self.location_keys},
+                                    {"infections": flat(f"infections_by_location_by_{name}")})
+        if "infections_caused_per_timestep" in results:      # date, series, value
             series = ("infections_caused", "infections_unattributed", "reproduction_number")
-            pd.DataFrame({"date": np.repeat(dates, len(series)), "series": np.tile(series, len(dates)),
-                          "value": np.stack([results[f"{k}_per_timestep"].detach().cpu().numpy() for k in series], 1).reshape(-1)}
-                         ).to_csv(self.save_path / "results_infectors.csv", index=False)
+            self._save_long("results_infectors.csv", dates, {"series": series}, {"value": np.stack(
+                [results[f"{k}_per_timestep"].detach().cpu().numpy() for k in series], 1).reshape(-1)})
             for name, keys in self.group_keys.items():
                 if f"infections_caused_by_{name}" not in results:
                     continue
-                flat = lambda key: results[key].detach().cpu().numpy().reshape(-1)
                 cols = {"infections_caused": flat(f"infections_caused_by_{name}"),
                         "reproduction_number": flat(f"reproduction_number_by_{name}")}
                 if f"infections_unattributed_by_{name}" in results:      # (a labelling with an infection matrix)
                     cols["infections_unattributed"] = flat(f"infections_unattributed_by_{name}")
-                pd.DataFrame({"date": np.repeat(dates, len(keys)), name: np.tile(keys, len(dates)), **cols}
-                             ).to_csv(self.save_path / f"results_infectors_by_{name}.csv", index=False)
-                if f"infection_matrix_by_{name}" in results:      # long format: date, infector, infected, infections
-                    G = len(keys)
-                    pd.DataFrame({"date": np.repeat(dates, G * G), "infector": np.tile(np.repeat(np.asarray(keys), G), len(dates)),
-                                  "infected": np.tile(keys, len(dates) * G), "infections": flat(f"infection_matrix_by_{name}")}
-                                 ).to_csv(self.save_path / f"results_infection_matrix_by_{name}.csv", index=False)
+                self._save_long(f"results_infectors_by_{name}.csv", dates, {name: keys}, cols)
+                if f"infection_matrix_by_{name}" in results:      # date, infector, infected, infections
+                    self._save_long(f"results_infection_matrix_by_{name}.csv", dates, {"infector": keys, "infected": keys},
+                                    {"infections": flat(f"infection_matrix_by_{name}")})
         if "infections_sampled_by_location" in results:      # one line per infected agent
             ag = self.data["agent"]
             row_of = ag["infected_row"].detach().cpu().numpy()
